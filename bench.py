@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- ORB extract throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--total-frames T] [--repeats R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--total-frames T] [--repeats R] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (RGBA frames in -> keypoints + BRIEF-256 descriptors out) over one batch of
 synthetic 1280x720 frames that are already resident in HBM (generated on the device).
@@ -16,11 +17,19 @@ kernels of the next).
 `python bench.py --gpus N` launches its own N rank processes (tinyslam_amd/launch.py) when it was not started by
 torch.distributed.run; the launcher never touches the GPU.
 
-The timed region is EXACTLY K steps between barrier + synchronize on both sides, max over ranks; it is repeated R
-times and `value` / `ms_per_step` are the median repeat (all repeats in `repeats_ms_per_step`).  Kernel durations for
-`roofline` come from a further pass of the same K steps with every launch bracketed by HIP events on its stream, so the
-events are outside the timed repeats.  `cpu_baseline` is the CPU restatement (oracle/, "port") timed on the host cores
-on a bounded sample of the same frames -- it is never the thing shipped.  Prints ONE JSON line on rank 0.
+The timed region is EXACTLY K steps between barrier + synchronize on both sides, max over ranks; it runs R times and
+`value` / `ms_per_step` are the median repeat (all repeats in `repeats_ms_per_step`).  A plain run does only what that
+line needs: set-up, untimed pre-heat steps, W warm-up steps, one K-step timed region (R = 1 unless --repeats says
+otherwise), the outputs if --dump-outputs is given, and the line.  Prints ONE JSON line on rank 0.
+
+--full adds everything else, each in runs of its own after the timed region: R = 5 by default; `roofline`, whose kernel
+durations come from a further pass of the same K steps with every launch bracketed by HIP events on its stream;
+`cpu_baseline`, the CPU restatement (oracle/, "port") timed on the host cores on a bounded sample of the same frames --
+it is never the thing shipped; the device-in -> host-out rate (N = 1), the single-frame latency, and at N > 1 (or
+--force-collate) the sharded repeats and the collate alone.
+
+--dump-outputs DIR writes what the timed path returned for its last step (dump_outputs()).  The frames come from fixed
+seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -54,9 +63,15 @@ def parse_args(argv=None):
     ap.add_argument("--total-frames", type=int, default=0,
                     help="strong scaling: a step is this many frames in all (BASELINE.json configs[4]: 2048), sharded "
                          "over the GPUs; 0 = weak scaling, --frames per GPU per step")
-    ap.add_argument("--repeats", type=int, default=5, help="how often the K-step timed region is repeated (median reported)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="frames for the CPU baseline (0 = skip)")
-    ap.add_argument("--no-host-out", action="store_true", help="skip the device-in -> host-out measurement (N = 1)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how often the K-step timed region is repeated (median reported; default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: roofline, CPU baseline, host-out, single-frame latency, "
+                         "sharded repeats and the collate alone (N > 1), five timed repeats")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="--full: frames for the CPU baseline (0 = skip)")
+    ap.add_argument("--no-host-out", action="store_true", help="--full: skip the device-in -> host-out measurement (N = 1)")
     ap.add_argument("--collate", choices=("transport", "padded", "none"), default="transport",
                     help="N > 1: what the gather to rank 0 carries -- 40-byte transport records packed back to back, or "
                          "the 48-byte record slabs padded to the fullest frame (round 1's form); none = the results stay "
@@ -94,11 +109,14 @@ def parse_args(argv=None):
     ap.add_argument("--angle-bins", type=int, default=0,
                     help="--mode intended only (IM-6b, OrbOptions::angle_bins): descriptors rotated by the centre of their keypoint's angle bin "
                          "instead of its milliradian code; 1024 bins = a 1 MB rotated-pattern table that stays in every XCD's L2")
-    ap.add_argument("--no-single-frame", action="store_true", help="skip the single-frame latency figure (profiling runs)")
+    ap.add_argument("--no-single-frame", action="store_true", help="--full: skip the single-frame latency figure (profiling runs)")
     ap.add_argument("--preheat-ms", type=float, default=300.0,
                     help="untimed steps run for this long before the W warm-up steps, so that the clocks are up (the "
                          "first of five repeats used to read 10 %% slow)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def cpu_baseline(n_sample, gpu_counts, intended=False, y8=False, syn_flags=15, threshold=THRESHOLD, fp=0, angle_bins=0):
@@ -187,6 +205,34 @@ def workload_text(args, world, B, strong):
                "orientation + separable Gaussian + BRIEF-256"))
 
 
+DUMP_SAMPLE_FRAMES, DUMP_SEED = 32, 20240601
+
+
+def dump_outputs(dirname, counts, read_frame):
+    """--dump-outputs: what the timed path returned for its last step, every array float64 (each 32-bit field exact).
+    counts.npy holds every frame's keypoint counter (frames of the step in order; a frame stores min(count, max_features)
+    records).  The records of all frames would pass 64 MB, so they are written for a fixed sample of frames drawn with a
+    fixed seed (sample_frames.npy): keypoints.npy (x, y, angle, octave) and descriptors.npy (the eight 32-bit words of
+    BRIEF-256), frame after frame, sampled frame i owning rows keypoint_offsets[i]:keypoint_offsets[i + 1].  Within a frame
+    the records are sorted by (octave, y, x): the order the device stores them in is not fixed (the tests sort alike).
+    read_frame(f, n) -> (corners as CORNER_DTYPE, descriptors as uint32 (n, 8)): the n stored records of frame f."""
+    import numpy as np
+    counts = np.asarray(counts, dtype=np.int64)
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(len(counts), size=min(len(counts), DUMP_SAMPLE_FRAMES), replace=False))
+    kps, descs, offsets = [], [], [0]
+    for f in sample:
+        c, d = read_frame(int(f), int(min(counts[f], MAX_FEATURES)))
+        order = np.lexsort((c["x"], c["y"], c["octave"]))
+        kps.append(np.stack([c[k][order] for k in ("x", "y", "angle", "octave")], axis=1).reshape(-1, 4))
+        descs.append(np.asarray(d).reshape(-1, 8)[order])
+        offsets.append(offsets[-1] + len(order))
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"counts": counts, "sample_frames": sample, "keypoint_offsets": offsets,
+              "keypoints": np.concatenate(kps), "descriptors": np.concatenate(descs)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def single_frame_latency(orb, cfg_kwargs, n=200, n_loop=2000):
     """The reference's only call shape (orb.rs:469-557): one blocking extract_corners per frame, 1280x720.  Returns
     the keys of the bench line: mean microseconds of orb_extract_corners alone on a resident frame; frames/s of the reference's loop
@@ -268,7 +314,9 @@ def run_node(args):
     world, B = args.gpus, args.frames
     if args.total_frames:
         raise SystemExit("--host node runs the weak-scaling workload (one B-frame shard per GPU per step)")
-    loop = os.environ.get("TINYORB_NODE_LOOPBACK", "0") not in ("", "0")
+    if args.dump_outputs and args.collate == "none":
+        raise SystemExit("--dump-outputs reads the job collated on the first device: not with --collate none")
+    loop =os.environ.get("TINYORB_NODE_LOOPBACK", "0") not in ("", "0")
     devices = [0] * world if loop else list(range(world))
     syn_flags, threshold = content_of(args)
     cfg_kwargs = dict(max_features=MAX_FEATURES, hierarchy_depth=DEPTH, initial_threshold=threshold,
@@ -322,9 +370,19 @@ def run_node(args):
         host.update(extract=0.0, begin=0.0, end=0.0, jobs=0)
         repeats = [timed(args.steps) for _ in range(max(1, args.repeats))]
         host_ms = {k: host[k] / max(1, host["jobs"]) * 1e3 for k in ("extract", "begin", "end")}
+        if args.dump_outputs:
+            _, offsets, c_dev, d_dev = last["r"]  # the last job, collated on the first device: records packed in frame order
+
+            def read_frame(f, n):
+                at = int(offsets[f])
+                assert at + n == int(offsets[f + 1]), (f, n, at, int(offsets[f + 1]))
+                c = progs[0].copy_to_host(c_dev + at * orb.CORNER_DTYPE.itemsize, n * orb.CORNER_DTYPE.itemsize)
+                d = progs[0].copy_to_host(d_dev + at * 32, n * 32)
+                return c.view(orb.CORNER_DTYPE), d.view(np.uint32).reshape(n, 8)
+            dump_outputs(args.dump_outputs, last["r"][0], read_frame)
         # the same repeats with the results left sharded (orb_node_set_results): kernel scaling without the links into the first device
         sharded = None
-        if args.collate != "none":
+        if args.full and args.collate != "none":
             drain()
             node.set_results(True)
             rs = [timed(args.steps) for _ in range(max(1, args.repeats))]
@@ -332,11 +390,12 @@ def run_node(args):
             node.set_results(False)
             sharded = sorted(rs)[len(rs) // 2]
             steps(2)  # the profiled pass below is of the collated form again
-        progs[0].profile_enable(True)
-        progs[0].profile_reset()
-        profiled = timed(args.steps)
-        prof = progs[0].profile()
-        progs[0].profile_enable(False)
+        if args.full:
+            progs[0].profile_enable(True)
+            progs[0].profile_reset()
+            profiled = timed(args.steps)
+            prof = progs[0].profile()
+            progs[0].profile_enable(False)
         elapsed = sorted(repeats)[len(repeats) // 2]
         counts, offsets, _, _ = last["r"]
         kp_per_step = float(offsets[F])
@@ -365,24 +424,25 @@ def run_node(args):
             "mkeypoints_per_s": kp_per_step * args.steps / elapsed / 1e6,
             "keypoints_per_frame": n_mean,
             "hbm_algorithmic_gbs": bytes_per_frame * fps / 1e9,
-            "roofline": roofline_of(args, prof, B * args.steps, bytes_per_frame, profiled),
             "collate": {"host_extract_ms_per_job": host_ms["extract"], "host_collate_begin_ms_per_job": host_ms["begin"],
                         "host_collate_end_ms_per_job": host_ms["end"],
                         "host_ms_what": "the host thread inside orb_node_extract_batch (enqueue of kernels and packs on every device), "
                                         "orb_node_collate_begin (waits for the OLDEST job's pack events, enqueues its exchange) and "
                                         "orb_node_collate_end (waits for that exchange) per job of the timed repeats; a step's budget is ms_per_step"},
         }
+        if args.full:
+            out["roofline"] = roofline_of(args, prof, B * args.steps, bytes_per_frame, profiled)
         if sharded is not None:
             out["value_sharded"] = F * args.steps / sharded
             out["ms_per_step_sharded"] = sharded / args.steps * 1e3
             out["sharded_what"] = ("the same K steps x %d repeats with orb_node_set_results(ORB_NODE_RESULTS_SHARDED): every rank packs its own "
                                    "records, nothing crosses a link -- kernel scaling alone; `value` is the collated figure" % max(1, args.repeats))
-        if world == 1:
+        if args.full and world == 1:
             n_cpu = args.cpu_sample if args.cpu_sample >= 0 else 128
             if n_cpu > 0:
                 out["cpu_baseline"] = cpu_baseline(n_cpu, counts[:B], intended=args.mode == "intended", y8=args.input == "y8",
                                                    syn_flags=syn_flags, threshold=threshold, fp=args.contract, angle_bins=args.angle_bins)
-    if args.mode == "literal" and args.content == "default" and not args.staged and not args.no_single_frame:
+    if args.full and args.mode == "literal" and args.content == "default" and not args.staged and not args.no_single_frame:
         out.update(single_frame_latency(orb, cfg_kwargs))
     emit(out)
 
@@ -430,6 +490,9 @@ def run_rank(args):
     n_local = hi - lo
     batches = [(b0, min(B, n_local - b0)) for b0 in range(0, n_local, B)]  # (first local frame, frames)
     job_frames = args.total_frames if strong else B * world
+    if args.dump_outputs and (len(batches) > 1 or (collating and args.collate != "transport")):
+        raise SystemExit("--dump-outputs: a step must be one batch per rank (the buffers keep the last batch only), "
+                         "collated in the transport form at N > 1")
 
     syn_flags, threshold = content_of(args)
     cfg = orb.OrbConfig(orb.Extent3d(W, H), max_features=MAX_FEATURES, hierarchy_depth=DEPTH,
@@ -589,6 +652,20 @@ def run_rank(args):
     if collator is not None:
         collator.wait_s = 0.0
     repeats = [timed(args.steps) for _ in range(max(1, args.repeats))]
+    if args.dump_outputs and rank == 0:
+        if transport:  # the job's records, expanded on rank 0 into the two record arrays in frame order
+            _, counts_all, _, corners_job, desc_job = state["last"]
+            counts_job = counts_all.numpy()
+            at = np.concatenate([[0], np.cumsum(np.minimum(counts_job, MAX_FEATURES))])
+
+            def read_frame(f, n):
+                lo = int(at[f])
+                c = corners_job[lo:lo + n].cpu().numpy().view(np.uint32).view(orb.CORNER_DTYPE).reshape(-1)
+                return c, desc_job[lo:lo + n].cpu().numpy().view(np.uint32)
+            dump_outputs(args.dump_outputs, counts_job, read_frame)
+        else:  # N = 1: the step's one batch, on the program that ran it last
+            p_last = fly_progs[(state["k"] - 1) % fly]
+            dump_outputs(args.dump_outputs, p_last.batch_counts(batches[0][1]), p_last.batch_read)
     n_collates = max(1, len(repeats) * args.steps * max(1, len(batches)))
     collate_host_ms = state["host_s"] / n_collates * 1e3
     # of which: waiting for the lagged counters' copy (TransportCollator.exchange; normally an event that is long set) -- the rest is
@@ -597,7 +674,7 @@ def run_rank(args):
     # The same timed repeats with the results left sharded (nothing packed, gathered or exchanged; the stream ordering stays): what the
     # kernels scale like, beside `value`, which at N > 1 also carries the links into rank 0 -- one line separates the two.
     sharded = None
-    if collating and args.collate != "none":
+    if args.full and collating and args.collate != "none":
         fence()
         state["sharded"] = True
         rs = [timed(args.steps) for _ in range(max(1, args.repeats))]
@@ -605,12 +682,13 @@ def run_rank(args):
         state["sharded"] = False
         sharded = sorted(rs)[len(rs) // 2]
     state["gathered_bytes"] = 0
-    prog.profile_enable(True)
-    prog.profile_reset()
-    state["serial"] = True  # --in-flight n: the per-kernel figures come from one program on one stream (no kernel shares the chip)
-    profiled = timed(args.steps)  # same K steps with HIP events around every launch
-    prof = prog.profile()
-    prog.profile_enable(False)
+    if args.full:
+        prog.profile_enable(True)
+        prog.profile_reset()
+        state["serial"] = True  # --in-flight n: the per-kernel figures come from one program on one stream (no kernel shares the chip)
+        profiled = timed(args.steps)  # same K steps with HIP events around every launch
+        prof = prog.profile()
+        prog.profile_enable(False)
     gathered_per_step = state["gathered_bytes"] / max(1, args.steps)
     elapsed = sorted(repeats)[len(repeats) // 2]
 
@@ -632,7 +710,7 @@ def run_rank(args):
 
     # collate alone (N > 1): the same gather, serialised, to price the links into rank 0
     collate_info = None
-    if collating:
+    if args.full and collating:
         fence()
         prog.batch_select_output(0)
         prog.extract_batch_device(frames_t.data_ptr(), batches[0][1] if batches else 0, stream=compute_stream.cuda_stream)
@@ -685,7 +763,7 @@ def run_rank(args):
     # into pinned host memory by two exact-size DMA copies on a second stream (orb_batch_fetch) while the next batch
     # computes; two output sets, two host buffers
     host_out = None
-    if world == 1 and not collating and not args.no_host_out and batches:
+    if args.full and world == 1 and not collating and not args.no_host_out and batches:
         copy_stream = torch.cuda.Stream(device=dev)
         cs = torch.cuda.current_stream(dev)
         hbs = [orb.HostBatch(B, B * MAX_FEATURES) for _ in range(2)]
@@ -743,7 +821,6 @@ def run_rank(args):
         n_mean = kp_per_step / job_frames
         # the frame read once (RGBA: 4 B per pixel, Y8: 1) + records + counter
         bytes_per_frame = frame_bytes + 48 * n_mean + 4
-        roofline = roofline_of(args, prof, launches_frames, bytes_per_frame, profiled)
         out = {
             "metric": "ORB extract throughput, 1280x720 (frames/sec; Mkeypoints/sec alongside)",
             "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -765,8 +842,9 @@ def run_rank(args):
             "mkeypoints_per_s": kp_per_step * args.steps / elapsed / 1e6,
             "keypoints_per_frame": n_mean,
             "hbm_algorithmic_gbs": bytes_per_frame * fps / 1e9,
-            "roofline": roofline,
         }
+        if args.full:
+            out["roofline"] = roofline_of(args, prof, launches_frames, bytes_per_frame, profiled)
         if collate_info:
             out["collate"] = collate_info
         if sharded is not None:
@@ -777,7 +855,7 @@ def run_rank(args):
         if host_out:
             out["host_out_frames_per_s"] = host_out["frames_per_s"]
             out["host_out"] = host_out
-        if world == 1:
+        if args.full and world == 1:
             n_cpu = args.cpu_sample if args.cpu_sample >= 0 else 128
             if n_cpu > 0:
                 out["cpu_baseline"] = cpu_baseline(n_cpu, counts_first, intended=args.mode == "intended", y8=args.input == "y8",

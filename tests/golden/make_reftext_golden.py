@@ -10,6 +10,7 @@ and the kernels with them.  Not a pin to an adapter: DESIGN.md section 2.
     python tests/golden/make_reftext_golden.py config0    # BASELINE.json configs[0]'s 640x480 frame (nine minutes: the interpreter runs
                                                           # 1.9 million fragment and 0.4 million compute invocations)
     python tests/golden/make_reftext_golden.py config1    # configs[1]'s 1280x720 frame (half an hour)
+    python tests/golden/make_reftext_golden.py cases      # the record tests/test_reference_text.py and test_oracle.py read (two minutes)
 """
 import os
 import sys
@@ -45,8 +46,22 @@ CONFIG1 = ("t1280x720_d2_config1", 1280, 720, 2, 2, 15)
 NOISY0 = ("t640x480_d2_noisy", 640, 480, 2, 2, 15)
 
 
+def record_cases():
+    """`cases`: what the text yields for every case of tests/test_reference_text.py, and the constants of it that
+    tests/test_oracle.py compares, as digests (tests/golden/reftext_record/)."""
+    import json
+    t0 = time.time()
+    np.savez_compressed(rt.CASES_NPZ, **rt.record_cases(orb_oracle))
+    with open(rt.CONSTANTS_JSON, "w") as f:
+        json.dump(rt.record_constants(), f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("cases: %.0f s" % (time.time() - t0), flush=True)
+
+
 def main():
     orb_oracle.build()
+    if sys.argv[1:2] == ["cases"]:
+        return record_cases()
     os.makedirs(os.path.join(HERE, "reftext"), exist_ok=True)
     big = {"config0": CONFIG0, "config1": CONFIG1, "noisy0": NOISY0}.get(sys.argv[1] if len(sys.argv) > 1 else "")
     config0 = big is not None

@@ -75,7 +75,7 @@ def test_bench_ranks_path_collates_through_nccl_world1():
     env = dict(os.environ, TINYORB_QUIET="1")
     env.pop("TINYORB_DIST_BACKEND", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collate", "--frames", "32", "--steps", "4",
-           "--warmup", "1", "--repeats", "2", "--cpu-sample", "0", "--no-single-frame", "--preheat-ms", "20"]
+           "--warmup", "1", "--repeats", "2", "--cpu-sample", "0", "--no-single-frame", "--preheat-ms", "20", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]

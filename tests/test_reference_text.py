@@ -1,11 +1,14 @@
 """The reference's shader TEXT, executed (tests/wgsl_interp.py), against the two restatements that were written by reading it.
 
-What is mechanical here: every expression, constant, loop, guard, bit order and index of the six shaders -- read from the reference checkout at
-test time (these tests are skipped where it is absent: the GPU box, a bare clone).  What is not: the fixed-function parts around the shaders,
+What is mechanical here: every expression, constant, loop, guard, bit order and index of the six shaders -- executed where the reference
+checkout is at hand by tests/golden/make_reftext_golden.py cases (record_cases() below), which stores what they yield for every case as data
+(tests/golden/reftext_record/); the tests compare the restatements with that record, so they run in
+any checkout.  What is not: the fixed-function parts around the shaders,
 restated below with the lines of orb.rs they follow (which shader runs over which view, dispatch sizes, the rasteriser's interpolation, the
 R16Float store) and the points WGSL leaves to the implementation, bound to the restatement's documented decisions (the
 sampler, atan2, cos / sin, u32() of a negative float, loads outside a level).  So this removes TRANSCRIPTION as a source of error between the
 shaders and the oracle; it does not pin the oracle to an adapter (parity unpinned)."""
+import hashlib
 import math
 import os
 import sys
@@ -18,8 +21,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import wgsl_interp as wi  # noqa: E402
 
 SHADERS = "/root/reference/src/shaders"
-pytestmark = pytest.mark.skipif(not os.path.isdir(SHADERS), reason="the reference checkout is not on this machine")
 F = np.float32
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CASES_NPZ = os.path.join(GOLDEN, "reftext_record", "cases.npz")
+CONSTANTS_JSON = os.path.join(GOLDEN, "reftext_record", "constants.json")
 
 
 def shader(name, edits=None):
@@ -173,19 +178,127 @@ def run_reference_text(oracle, rgba, depth, thr, cap, edits=None, **adapter):
     return gray, blur, total, c, d
 
 
-def test_known_answers_from_the_text_itself():
-    """SURVEY.md section 8c's known answers, evaluated on the reference's own functions instead of their restatement."""
+# The cases of the tests below; record_cases() executes the text for each of them.
+FRAMES = [(64, 48, 2, 5, 15), (80, 56, 2, 9, 15)]
+SLIPS = [
+    ({"grayscale": ("0.229", "0.299")}, "grey level 0"),                          # the red weight (Q1)
+    ({"gaussian_blur_x": ("1.3243948342247673", "1.3243948342247")}, None),      # a literal that rounds to the same binary32: no difference
+    ({"gaussian_blur_x": ("0.5037756553768409", "0.50378")}, "blur level 0"),     # ... and one that does not
+    ({"fast": ("vec2i(-3, -1)", "vec2i(-3, 1)")}, "corners"),                     # one ring offset
+    ({"brief": ("global_id.x << 5u | i", "global_id.x << 4u | i")}, "descriptors"),  # the descriptor's bit order
+]
+SWITCHES = [
+    dict(oob="clamp"), dict(oob="umin"), dict(weight_bits=8), dict(dot_order=1), dict(contract=7), dict(contract=7, dot_order=1),
+    dict(contract=2, weight_bits=8, oob="clamp"), dict(neg_angle="wrap"),
+]
+LUMA_FORMS = [(0, 0), (1, 0), (0, 1), (1, 1)]
+STREAK_X = [0x0FFF, 0x07FF, 0xF0FF, 0xFFFF] + list(range(0, 1 << 16, 97))
+THR, CAP = F(20.0 / 255.0), 256
+
+
+def digest(a):
+    """dtype, shape and SHA-256 of an array: how the record names a constant of the text without holding it."""
+    a = np.ascontiguousarray(a)
+    return "%s%s:%s" % (a.dtype.str, list(a.shape), hashlib.sha256(a.tobytes()).hexdigest())
+
+
+def case_key(kind, case):
+    return "%s_%s" % (kind, hashlib.sha256(repr(case).encode()).hexdigest()[:16])
+
+
+def record_cases(oracle):
+    """Executes the shader text for every case of this module; returns the record (tests/golden/reftext_record/cases.npz): per run the input
+    frame's digest, the counter, the records and every grey and blur level as binary16 bit patterns; the luminance forms' grey levels;
+    detect_streak_16 at STREAK_X; digests of the 16-point ring and of the BRIEF pattern."""
+    out = {}
+
+    def put(key, rgba, got):
+        gray, blur, total, c, d = got
+        out.update({key + "_rgba": np.array(digest(rgba)), key + "_total": np.uint32(total),
+                    key + "_corners": c.astype(np.uint32), key + "_descriptors": d.astype(np.uint32)})
+        for m in range(len(gray)):
+            out[key + "_gray%d" % m] = gray[m].a.astype(np.float16).view(np.uint16)
+            out[key + "_blur%d" % m] = blur[m].a.astype(np.float16).view(np.uint16)
+    for W, H, depth, seed, flags in FRAMES:
+        rgba = frame_with_corners(oracle, W, H, seed, flags)
+        put(case_key("frame", (W, H, depth, seed, flags)), rgba, run_reference_text(oracle, rgba, depth, THR, CAP))
+    rgba = frame_with_corners(oracle, 64, 48, 5, 15)
+    for edits, _ in SLIPS:
+        put(case_key("slip", edits), rgba, run_reference_text(oracle, rgba, 2, THR, CAP, edits))
+    for switches in SWITCHES:
+        put(case_key("switches", switches), rgba, run_reference_text(oracle, rgba, 2, THR, CAP, **switches))
+    rgba = luminance_texels(oracle)
+    out["luma_rgba"] = np.array(digest(rgba))
+    for contract, order in LUMA_FORMS:
+        got = render(wi.Module(shader("grayscale"), Adapter(oracle, contract=contract, dot_order=order)), "texture_sampler", "texture",
+                     Plane(rgba), "texel", 16, 4)
+        out["luma_%d%d" % (contract, order)] = got.a.astype(np.float16).view(np.uint16)
     fast = wi.Module(shader("fast"))
-    streak = lambda x: fast.call("detect_streak_16", [wi.V("u32", x)]).v  # noqa: E731
-    assert [streak(x) for x in (0x0FFF, 0x07FF, 0xF0FF, 0xFFFF)] == [0x0001, 0, 0x1000, 0xFFFF]
+    out["streak"] = np.array([fast.call("detect_streak_16", [wi.V("u32", x)]).v for x in STREAK_X], dtype=np.uint32)
+    out["ring16"] = np.array(digest(np.array([tuple(v.e) for v in fast.globals["CORNERS_16"]], dtype=np.int32)))
+    brief = wi.Module(shader("brief"))
+    out["pattern"] = np.array(digest(np.array([v.e for v in brief.globals["brief_descriptors"]], dtype=np.int8)))
+    return out
+
+
+def record_constants():
+    """The numeric constants of the text that test_oracle.py::test_constants_match_the_reference_text compares with the restatements,
+    parsed from it (tests/golden/reftext_record/constants.json): digests, counts and yes / no answers."""
+    import re
+    num = r"[-+]?\d+\.?\d*(?:[eE][-+]?\d+)?"
+    g = shader("grayscale")
+    coefs = [float(v) for v in re.search(r"rgba_coefs\s*=\s*vec4f\(([^)]*)\)", g).group(1).split(",")]
+    b = shader("gaussian_blur_x")
+    offs = [float(v) for v in re.findall(num, re.search(r"offsets[^=]*=\s*array\(([^;]*)\);", b, re.S).group(1))]
+    wgts = [float(v) for v in re.findall(num, re.search(r"weights[^=]*=\s*array\(([^;]*)\);", b, re.S).group(1))]
+    f = shader("fast")
+    ring = lambda name: [(int(x), int(y)) for x, y in re.findall(r"vec2i\((-?\d+),\s*(-?\d+)\)", re.search(name + r"[^=]*=\s*array\((.*?)\);", f, re.S).group(1))]  # noqa: E731
+    body = re.search(r"fn detect_streak_16.*?\n}", f, re.S).group(0)
+    guard = re.search(r"global_id\.xy\s*>\s*vec2u\((\d+),\s*(\d+)\).*?-\s*vec2u\((\d+),\s*(\d+)\)", f)  # fast.wgsl:77
+    bt = shader("brief")
+    rows = re.findall(r"vec4i\(\s*(-?\d+)\s*,\s*(-?\d+)\s*,\s*(-?\d+)\s*,\s*(-?\d+)\s*\)", bt[bt.index("brief_descriptors"):])
+    return {"luminance_weights": digest(np.array(coefs, dtype=np.float64)),
+            "blur_offsets": digest(np.array(offs, dtype=np.float32)), "blur_weights": digest(np.array(wgts, dtype=np.float32)),
+            "blur_sample_count": [len(offs), int(re.search(r"SAMPLE_COUNT\s*:\s*u32\s*=\s*(\d+)u", b).group(1))],
+            "ring4": digest(np.array(ring("CORNERS_4"), dtype=np.int32)), "ring16": digest(np.array(ring("CORNERS_16"), dtype=np.int32)),
+            "streak_shifts": digest(np.array([int(v) for v in re.findall(r"rotate_bits_16\(\w+,\s*(\d+)u\)", body)], dtype=np.int32)),
+            "guard": digest(np.array([int(v) for v in guard.groups()], dtype=np.int32)) if guard else None,
+            "fast_milliradians": bool(re.search(r"angle\s*\*\s*1000(\.0)?", f)), "brief_milliradians": bool(re.search(r"/\s*1000(\.0)?", bt)),
+            "brief_pattern": digest(np.array(rows, dtype=np.int32)),
+            "workgroups": bool(re.search(r"@workgroup_size\(8,\s*8(,\s*1)?\)", f) and re.search(r"@workgroup_size\(8", bt))}
+
+
+_RECORD = {}
+
+
+def recorded():
+    if not _RECORD:
+        with np.load(CASES_NPZ) as z:
+            _RECORD.update((k, z[k]) for k in z.files)
+    return _RECORD
+
+
+def executed(key, rgba):
+    """run_reference_text()'s result for one case, as the record holds it; the frame must be the one it was executed on."""
+    r = recorded()
+    assert str(r[key + "_rgba"]) == digest(rgba), "the frame differs from the one the record was made on"
+    planes = lambda kind: [Plane(r["%s_%s%d" % (key, kind, m)].view(np.float16).astype(F))  # noqa: E731
+                           for m in range(16) if "%s_%s%d" % (key, kind, m) in r]
+    return planes("gray"), planes("blur"), int(r[key + "_total"]), r[key + "_corners"], r[key + "_descriptors"]
+
+
+def test_known_answers_from_the_text_itself(numpy_ref):
+    """SURVEY.md section 8c's known answers, evaluated on the reference's own functions instead of their restatement (as recorded)."""
+    streak = dict(zip(STREAK_X, recorded()["streak"].tolist()))
+    assert [streak[x] for x in (0x0FFF, 0x07FF, 0xF0FF, 0xFFFF)] == [0x0001, 0, 0x1000, 0xFFFF]
     for x in range(0, 1 << 16, 97):  # "a circular run of twelve" by brute force
         run = any(all((x >> ((s + k) & 15)) & 1 for k in range(12)) for s in range(16))
-        assert (streak(x) != 0) == run, hex(x)
-    ring = [tuple(v.e) for v in fast.globals["CORNERS_16"]]
+        assert (streak[x] != 0) == run, hex(x)
+    assert str(recorded()["ring16"]) == digest(np.array(numpy_ref.RING16, dtype=np.int32))  # the text's ring is the restatement's
+    ring = [tuple(v) for v in numpy_ref.RING16]
     assert ring[0] == (-3, 0) and ring[4] == (0, -3) and len(set(ring)) == 16 and all(x * x + y * y in (8, 9, 10) for x, y in ring)
-    brief = wi.Module(shader("brief"))
-    pat = np.array([v.e for v in brief.globals["brief_descriptors"]], dtype=np.int8)
-    import hashlib
+    pat = np.asarray(numpy_ref.PATTERN, dtype=np.int8)
+    assert str(recorded()["pattern"]) == digest(pat)
     assert pat.shape == (256, 4) and hashlib.sha256(pat.tobytes()).hexdigest() == "2164181aea6ff9ac426ca512d5130d15e1f6e3cd47b1cbdd568bbe1e55d49023"
 
 
@@ -223,14 +336,14 @@ def differences(oracle, rgba, depth, thr, cap, got, **switches):
     return out
 
 
-@pytest.mark.parametrize("W,H,depth,seed,flags", [(64, 48, 2, 5, 15), (80, 56, 2, 9, 15)])
+@pytest.mark.parametrize("W,H,depth,seed,flags", FRAMES)
 def test_the_shader_text_executed_equals_both_restatements(oracle, numpy_ref, W, H, depth, seed, flags):
     """grey, mip, both blur passes, FAST with orientation, BRIEF: the interpreted shaders against oracle/orb_oracle.c, plane by plane and
     record by record, bit for bit -- on frames that put keypoints on both octaves, give a third of them a non-zero angle, and leave the
     blur varying in its last eighth of the columns only (the property of the literal blur the fused kernels lean on)."""
     rgba = frame_with_corners(oracle, W, H, seed, flags)
-    thr, cap = np.float32(20.0 / 255.0), 256
-    got = run_reference_text(oracle, rgba, depth, thr, cap)
+    thr, cap = THR, CAP
+    got = executed(case_key("frame", (W, H, depth, seed, flags)), rgba)
     assert differences(oracle, rgba, depth, thr, cap, got) == []
     gray, blur, total, c, d = got
     assert 0 < total <= cap and (c[:, 2] > 0).sum() >= 10, "too few keypoints with a non-zero angle: the rotation was not exercised"
@@ -241,58 +354,52 @@ def test_the_shader_text_executed_equals_both_restatements(oracle, numpy_ref, W,
     assert numpy_ref.extract(rgba, depth=depth, threshold=thr, max_features=cap)["total"] == total
 
 
-@pytest.mark.parametrize("edits,expect", [
-    ({"grayscale": ("0.229", "0.299")}, "grey level 0"),                          # the red weight (Q1)
-    ({"gaussian_blur_x": ("1.3243948342247673", "1.3243948342247")}, None),      # a literal that rounds to the same binary32: no difference
-    ({"gaussian_blur_x": ("0.5037756553768409", "0.50378")}, "blur level 0"),     # ... and one that does not
-    ({"fast": ("vec2i(-3, -1)", "vec2i(-3, 1)")}, "corners"),                     # one ring offset
-    ({"brief": ("global_id.x << 5u | i", "global_id.x << 4u | i")}, "descriptors"),  # the descriptor's bit order
-])
+@pytest.mark.parametrize("edits,expect", SLIPS)
 def test_a_slip_in_the_text_is_noticed(oracle, edits, expect):
     """The comparison has teeth: one edited token in one shader shows up in the stage it belongs to (and an edit that does not change the
     binary32 constant does not)."""
-    W, H, depth, thr, cap = 64, 48, 2, np.float32(20.0 / 255.0), 256
+    W, H, depth, thr, cap = 64, 48, 2, THR, CAP
     rgba = frame_with_corners(oracle, W, H, 5, 15)
-    diff = differences(oracle, rgba, depth, thr, cap, run_reference_text(oracle, rgba, depth, thr, cap, edits))
+    diff = differences(oracle, rgba, depth, thr, cap, executed(case_key("slip", edits), rgba))
     if expect is None:
         assert diff == []
     else:
         assert expect in diff, diff
 
 
-@pytest.mark.parametrize("switches", [
-    dict(oob="clamp"), dict(oob="umin"), dict(weight_bits=8), dict(dot_order=1), dict(contract=7), dict(contract=7, dot_order=1),
-    dict(contract=2, weight_bits=8, oob="clamp"), dict(neg_angle="wrap"),
-], ids=lambda s: ",".join("%s=%s" % kv for kv in s.items()))
+@pytest.mark.parametrize("switches", SWITCHES, ids=lambda s: ",".join("%s=%s" % kv for kv in s.items()))
 def test_the_switches_mean_the_same_in_the_interpreter_and_the_oracle(oracle, switches):
     """The implementation-defined points (orc_impl_t) modelled a second time, around the interpreted text: out-of-level loads, sampler weight
     bits, the three contractions with both reduction orders, the conversion of a negative angle -- the oracle under a switch equals the
     interpreter under the same reading; the policies and the weight bits change something on this frame (that equality is not vacuous), the
     arithmetic forms are too rare for 64 x 48 texels and are compared texel by texel in test_oracle.py."""
-    W, H, depth, thr, cap = 64, 48, 2, np.float32(20.0 / 255.0), 256
+    W, H, depth, thr, cap = 64, 48, 2, THR, CAP
     rgba = frame_with_corners(oracle, W, H, 5, 15)
-    got = run_reference_text(oracle, rgba, depth, thr, cap, **switches)
+    got = executed(case_key("switches", switches), rgba)
     assert differences(oracle, rgba, depth, thr, cap, got, **switches) == []
     if set(switches) & {"oob", "weight_bits", "neg_angle"}:  # (the arithmetic forms move a dozen texels of a 1280 x 720 frame: none of these 3072)
         assert differences(oracle, rgba, depth, thr, cap, got) != [], "this frame does not tell %r from the defaults" % (switches,)
 
 
-def test_the_luminance_forms_on_texels_that_tell_them_apart(oracle):
-    """grayscale.wgsl's dot() interpreted under the four forms a shader compiler may give it (CRD-2 / CRD-13: fused or not, first or last
-    component first), on a frame made of the colours on which the forms disagree -- each form equals the oracle's, and no two forms agree."""
+def luminance_texels(oracle):
+    """A 16 x 4 frame of the colours on which the four luminance forms disagree."""
     rng = np.random.default_rng(11)
     cols = rng.integers(0, 256, size=(1, 1 << 21, 4), dtype=np.uint8)  # (one row: the stage mirrors rows)  # the forms disagree on 5 colours in 100 000
     cols[..., 3] = 255
-    forms = [(0, 0), (1, 0), (0, 1), (1, 1)]
-    grey = {f: oracle.grayscale_fp(cols, f[0], f[1]).ravel() for f in forms}
+    grey = {f: oracle.grayscale_fp(cols, f[0], f[1]).ravel() for f in LUMA_FORMS}
     pick = np.flatnonzero((grey[0, 0] != grey[1, 0]) | (grey[0, 0] != grey[0, 1]) | (grey[1, 0] != grey[1, 1]))[:64]
     assert len(pick) == 64
-    rgba = np.ascontiguousarray(cols[0, pick].reshape(4, 16, 4))
+    return np.ascontiguousarray(cols[0, pick].reshape(4, 16, 4))
+
+
+def test_the_luminance_forms_on_texels_that_tell_them_apart(oracle):
+    """grayscale.wgsl's dot() interpreted under the four forms a shader compiler may give it (CRD-2 / CRD-13: fused or not, first or last
+    component first), on a frame made of the colours on which the forms disagree -- each form equals the oracle's, and no two forms agree."""
+    rgba = luminance_texels(oracle)
+    assert str(recorded()["luma_rgba"]) == digest(rgba), "the frame differs from the one the record was made on"
     seen = {}
-    for contract, order in forms:
-        hooks = Adapter(oracle, contract=contract, dot_order=order)
-        got = render(wi.Module(shader("grayscale"), hooks), "texture_sampler", "texture", Plane(rgba), "texel", 16, 4)
-        bits = got.a.astype(np.float16).view(np.uint16)
+    for contract, order in LUMA_FORMS:
+        bits = recorded()["luma_%d%d" % (contract, order)]
         assert np.array_equal(bits, oracle.grayscale_fp(rgba, contract, order)), (contract, order)
         seen[contract, order] = bits.tobytes()
     assert len(set(seen.values())) == 4

@@ -2,7 +2,7 @@
 # A/B of a compile-time experiment on the bench line (GPU box): bash tools/ab_build.sh "<extra hipcc flags>"
 # default build -> bench; build with the flags -> GPU parity tests + bench; again both; the tree's library is rebuilt at the end.
 out=gpurun_out/abb; mkdir -p $out
-run() { name=$1; python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-host-out --no-single-frame > $out/$name.json 2> $out/$name.err || { echo "bench $name failed"; tail -3 $out/$name.err; exit 1; }
+run() { name=$1; python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --no-host-out --no-single-frame > $out/$name.json 2> $out/$name.err || { echo "bench $name failed"; tail -3 $out/$name.err; exit 1; }
 python - <<PY
 import json
 d=json.loads(open("$out/$name.json").read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ if [ "${AB_TESTS:-0}" = "1" ]; then
 fi
 run() { # name, env...
   name=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-host-out --no-single-frame $BENCH_ARGS > $out/bench_$name.json 2> $out/bench_$name.err || { echo "bench $name failed"; tail -5 $out/bench_$name.err; exit 1; }
+  env "$@" timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --no-host-out --no-single-frame $BENCH_ARGS > $out/bench_$name.json 2> $out/bench_$name.err || { echo "bench $name failed"; tail -5 $out/bench_$name.err; exit 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/bench_$name.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@
 out=gpurun_out/abso; mkdir -p $out
 export TINYORB_ALLOW_ABI=1  # libraries of older commits report an older ABI version; the bench uses nothing that changed
 cp tinyslam_amd/libtinyorb.so $out/keep.so
-run() { python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-host-out --no-single-frame > $out/$1.json 2> $out/$1.err || { echo fail $1; tail -3 $out/$1.err; cp $out/keep.so tinyslam_amd/libtinyorb.so; exit 1; }
+run() { python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --no-host-out --no-single-frame > $out/$1.json 2> $out/$1.err || { echo fail $1; tail -3 $out/$1.err; cp $out/keep.so tinyslam_amd/libtinyorb.so; exit 1; }
 python - <<PY
 import json
 d=json.loads(open("$out/$1.json").read().strip().splitlines()[-1])

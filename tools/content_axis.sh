@@ -4,7 +4,7 @@ OUT=${1:-gpurun_out/r04_content_axis.txt}
 : > $OUT
 for mode in ${MODES:-literal intended}; do
 for c in flat sparse default dense overflow; do
-  python3 bench.py --mode $mode --content $c --cpu-sample 0 --no-single-frame --no-host-out --repeats 3 2>/dev/null | python3 -c "
+  python3 bench.py --full --mode $mode --content $c --cpu-sample 0 --no-single-frame --no-host-out --repeats 3 2>/dev/null | python3 -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):
