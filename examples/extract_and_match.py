@@ -39,3 +39,11 @@ with orb.OrbProgram(cfg) as prog:  # == OrbProgram { config, .. }.init() in the 
     good = m["distance"] < 0.8 * m["second"]                        # ratio test on the two best Hamming distances
     print("frame 0 -> 1: %d of %d keypoints pass the ratio test (the two synthetic frames are unrelated scenes)"
           % (int(good.sum()), int(counts[0])))
+
+    # --- geometric verification: a RANSAC homography per pair, refit over its inliers -----------
+    prog.verify_consecutive(2)
+    model, inlier = prog.verify_read(0, int(counts[0]))
+    status = {orb.ORB_VERIFY_OK: "ok", orb.ORB_VERIFY_FEW: "fewer than 4 candidates", orb.ORB_VERIFY_DEGENERATE: "degenerate",
+              orb.ORB_VERIFY_MINIMAL: "minimal model"}[int(model["status"])]
+    print("frame 0 -> 1 verified: %d candidates, %d inliers (%s), H =\n%s"
+          % (int(model["candidates"]), int(model["inliers"]), status, model["h"].reshape(3, 3)))

@@ -353,6 +353,53 @@ int orb_match_consecutive(OrbProgram *p, uint32_t n_frames, void *stream);
 /* Copy up to n matches of the queries of `frame` to the host (synchronises). */
 int orb_match_read(OrbProgram *p, uint32_t frame, OrbMatch *dst, size_t n);
 
+/* ---- geometric verification of the matches (NOT in the reference; definition GV-1..GV-7 in DESIGN.md section 13) ----
+ * For every consecutive pair (f, f+1) of the last orb_match_consecutive call: the matches that pass a distance and ratio
+ * filter are the candidates; a RANSAC over minimal 4-point homographies picks the model with the most inliers (one-way
+ * transfer error below inlier_px), a least-squares refit over its inliers replaces it unless it loses 1/16 of them or more,
+ * and every candidate gets an inlier byte.  Coordinates are the level-0 pixel centres of orb_corner_level0_xy: in the
+ * default (literal) mode y is therefore in the reference's vertically mirrored frame (row 0 = the image's bottom row);
+ * with ORB_FLAG_INTENDED there is no mirror.  Integer and binary32 arithmetic only (+ - * /, no sqrt), in a fixed order:
+ * a CPU restatement gives the same bits. */
+typedef struct {           /* zero-initialised = the defaults */
+    uint32_t hypotheses;   /* minimal samples per pair, 1..4096 (0: 512) */
+    uint32_t max_distance; /* Hamming distance a candidate may have, 0..256 (0: 64) */
+    float ratio;           /* candidate iff distance < ratio * second, in binary32 (0: 0.8); finite, >= 0 */
+    float inlier_px;       /* one-way transfer error threshold in level-0 pixels (0: 3.0); finite, >= 0 */
+    uint32_t seed;         /* of the sample draws */
+    uint32_t reserved[3];  /* must be 0 (ORB_EINVAL otherwise) */
+} OrbVerifyParams;         /* 32 bytes */
+
+typedef struct {
+    float h[9];            /* row-major, level-0 keypoint coordinates of frame f -> frame f+1, divided by its [2][2] entry:
+                            * h[8] == 1 when status is OK / MINIMAL (unless that entry of the kept model is 0 -- a model that
+                            * sends the pixel (0, 0) to infinity -- and then every h is inf / NaN; the inliers and the bytes
+                            * stay valid); all 0 for FEW / DEGENERATE */
+    uint32_t candidates;   /* matches that passed the filters */
+    uint32_t inliers;      /* candidates that are inliers of the model in h */
+    uint32_t hypothesis;   /* index of the winning minimal sample, ORB_MATCH_NONE if none was valid */
+    uint32_t status;       /* ORB_VERIFY_* */
+    uint32_t reserved[3];  /* 0 */
+} OrbPairModel;            /* 64 bytes */
+
+#define ORB_VERIFY_OK 0u         /* the least-squares refit over the winner's inliers */
+#define ORB_VERIFY_FEW 1u        /* fewer than 4 candidates: no model */
+#define ORB_VERIFY_DEGENERATE 2u /* no hypothesis drew a valid (non-degenerate) sample: no model */
+#define ORB_VERIFY_MINIMAL 3u    /* the refit failed or kept fewer than 15/16 of the inliers: the winning minimal model */
+
+/* Verifies the pairs (f, f+1), f in [0, n_frames - 1), of the last orb_match_consecutive call (params NULL: the defaults).
+ * ORB_ESTATE when there was no such call, when a batch was extracted after it or when orb_batch_select_output changed the
+ * output set since; ORB_EINVAL when n_frames exceeds the matched frame count (or is < 2) or a parameter is out of range.
+ * Asynchronous on `stream` -- NULL: the stream of the program's last batched call, match or verification (its own stream
+ * before any), as the matcher chooses -- and ordered behind the matcher's last call and the last verification when they ran
+ * on another stream.  ONE result buffer per program (allocated by the first call): a call overwrites the results of the
+ * call before. */
+int orb_verify_consecutive(OrbProgram *p, uint32_t n_frames, const OrbVerifyParams *params, void *stream);
+/* Synchronises, copies the record of `pair` and min(n, max_features) inlier bytes (may be NULL when n == 0), indexed like
+ * orb_match_read's output (query i of frame `pair`): 1 for a candidate that is an inlier of the model in the record, 0
+ * for every other query. */
+int orb_verify_read(OrbProgram *p, uint32_t pair, OrbPairModel *model, uint8_t *inlier, size_t n);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */
@@ -376,7 +423,7 @@ int orb_debug_angle_code(OrbProgram *p, const float *cy, const float *cx, uint32
 int orb_debug_rot_table(OrbProgram *p, int16_t *dst, size_t n_entries, uint32_t *codes, uint32_t *pitch);
 
 /* ---- measurement ---- */
-#define ORB_KERNEL_COUNT 22
+#define ORB_KERNEL_COUNT 25
 /* When enabled every kernel launch is bracketed by hipEvents on its stream. */
 int orb_profile_enable(OrbProgram *p, int enable);
 int orb_profile_reset(OrbProgram *p);

@@ -6,6 +6,7 @@
 // instead of 3*D render passes + D+1 compute dispatches + 3 staging copies.
 #include <hip/hip_runtime.h>
 #include <chrono>
+#include <cmath>
 
 #include <cstdarg>
 #include <cstdio>
@@ -24,17 +25,19 @@
 #include "orb_kernels_staged.h"
 #include "orb_kernels_collate.h"
 #include "orb_kernels_match.h"
+#include "orb_kernels_verify.h"
 
 using namespace orb;
 
 namespace {
 
-enum KernelId { KID_GRAY = 0, KID_MIP, KID_BLUR, KID_FAST, KID_BRIEF, KID_FUSED_L0, KID_FUSED_LN, KID_SYNTH, KID_BRIEF_ROWS, KID_PREFIX, KID_FRONT_I, KID_SELECT_I, KID_BRIEF_I, KID_MATCH, KID_COMPACT, KID_BRIEF_T, KID_BRIEF_NF, KID_PACK_T, KID_UNPACK_T, KID_BRIEF_ONE, KID_FRONT_I_LN, KID_DESC_EXPAND };
+enum KernelId { KID_GRAY = 0, KID_MIP, KID_BLUR, KID_FAST, KID_BRIEF, KID_FUSED_L0, KID_FUSED_LN, KID_SYNTH, KID_BRIEF_ROWS, KID_PREFIX, KID_FRONT_I, KID_SELECT_I, KID_BRIEF_I, KID_MATCH, KID_COMPACT, KID_BRIEF_T, KID_BRIEF_NF, KID_PACK_T, KID_UNPACK_T, KID_BRIEF_ONE, KID_FRONT_I_LN, KID_DESC_EXPAND, KID_VERIFY_GATHER, KID_VERIFY_SCORE, KID_VERIFY_REFINE };
 const char* const kKernelNames[ORB_KERNEL_COUNT] = {"k_grayscale", "k_mip",      "k_blur_rows", "k_fast",       "k_brief",
                                                     "k_front_l0",  "k_front_ln", "k_synth",     "k_brief_rows", "k_slot_prefix",
                                                     "k_front_i_l0", "k_select_i", "k_brief_i",   "k_match",      "k_compact",
                                                     "k_brief_t",   "k_brief_nf",  "k_compact_transport", "k_unpack_transport",
-                                                    "k_brief_one", "k_front_i_ln", "k_desc_expand"};
+                                                    "k_brief_one", "k_front_i_ln", "k_desc_expand", "k_verify_gather",
+                                                    "k_verify_score", "k_verify_refine"};
 
 thread_local std::string g_create_error;
 
@@ -110,6 +113,20 @@ struct OrbProgram {
     // on another stream is ordered behind the one before (its expand kernel would overwrite rows the earlier match still reads)
     hipEvent_t match_done = nullptr;
     hipStream_t match_stream = nullptr;
+    uint64_t batch_seq = 0;    // batched calls so far (every call that sets last_batch); the matcher records which one it read
+    uint64_t match_seq = 0;    // batch_seq at the last orb_match_consecutive (0: none)
+    uint32_t match_set = 0;    // output set it read
+    uint32_t match_frames = 0; // frames it matched
+    // orb_verify_consecutive (orb_kernels_verify.h): one set of buffers per program, allocated by the first call
+    float4* d_vrec = nullptr;             // [max_batch][max_features] candidates (u, v, u2, v2)
+    uint32_t* d_vcand = nullptr;          // [max_batch][max_features] candidate of each query
+    uint32_t* d_vn = nullptr;             // [max_batch] candidates per pair
+    unsigned long long* d_vkeys = nullptr;  // [max_batch][kVerifyMaxHyp]
+    uint32_t* d_vmodel = nullptr;         // [max_batch] OrbPairModel
+    uint8_t* d_vmask = nullptr;           // [max_batch][max_features] inlier bytes
+    hipEvent_t verify_done = nullptr;
+    hipStream_t verify_stream = nullptr;
+    uint32_t verify_pairs = 0;            // pairs of the last verify call (0: none)
     uint32_t* d_prov2_counts = nullptr;
     CornerData* d_prov2 = nullptr;
     float* d_prov2_scores = nullptr;
@@ -1297,6 +1314,13 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_stamps);
     (void)hipFree(p->d_desc8);
     if (p->match_done) (void)hipEventDestroy(p->match_done);
+    (void)hipFree(p->d_vrec);
+    (void)hipFree(p->d_vcand);
+    (void)hipFree(p->d_vn);
+    (void)hipFree(p->d_vkeys);
+    (void)hipFree(p->d_vmodel);
+    (void)hipFree(p->d_vmask);
+    if (p->verify_done) (void)hipEventDestroy(p->verify_done);
     if (p->single_done_ev) (void)hipEventDestroy(p->single_done_ev);
     if (p->h_count) (void)hipHostFree(p->h_count);
     if (p->d_single_done) (void)hipFree(p->d_single_done);
@@ -1530,6 +1554,7 @@ int orb_extract_corners(OrbProgram* p, uint32_t* corner_count) {
 #endif
         p->single_valid = true;
         p->last_batch = 1;
+        p->batch_seq++;
         p->last_stream = s;
         *corner_count = *p->h_count;  // raw counter, orb.rs:550-556
         if (*corner_count > cap) return fail(p, ORB_ECAPACITY, "%u corners detected, max_features is %zu", *corner_count, cap);
@@ -1538,6 +1563,7 @@ int orb_extract_corners(OrbProgram* p, uint32_t* corner_count) {
     if (int rc = run_pipeline(p, d_in, 1, s)) return rc;
     if (direct) {
         p->last_batch = 1;
+        p->batch_seq++;
         p->last_stream = s;
         if (int rc = launch_compact(p, 1, static_cast<uint32_t*>(dc), nullptr, static_cast<CornerData*>(dk),
                                     static_cast<CornerDescriptor*>(dd), cap, s, nullptr))
@@ -1551,6 +1577,7 @@ int orb_extract_corners(OrbProgram* p, uint32_t* corner_count) {
     HIP_TRY(p, hipStreamSynchronize(s));
     p->single_valid = true;
     p->last_batch = 1;
+    p->batch_seq++;
     p->last_stream = s;
     *corner_count = *p->h_count;  // raw counter, orb.rs:550-556
     if (*corner_count > cap) return fail(p, ORB_ECAPACITY, "%u corners detected, max_features is %zu", *corner_count, cap);
@@ -1584,6 +1611,7 @@ int orb_extract_batch_device(OrbProgram* p, const uint8_t* frames_dev, uint32_t 
     hipStream_t s = stream ? (hipStream_t)stream : p->stream;
     if (int rc = run_pipeline(p, frames_dev, n_frames, s)) return rc;
     p->last_batch = n_frames;
+    p->batch_seq++;
     p->last_stream = s;
     p->single_valid = false;
     return ORB_OK;
@@ -1633,6 +1661,7 @@ int orb_extract_batch_pinned(OrbProgram* p, const uint8_t* frames_pinned, uint32
     if (int rc = ensure_input(p)) return rc;
     if (int rc = upload_chunked_and_run(p, frames_pinned, n_frames, p->stream)) return rc;
     p->last_batch = n_frames;
+    p->batch_seq++;
     p->last_stream = p->stream;
     p->single_valid = false;
     return ORB_OK;
@@ -1673,6 +1702,7 @@ int orb_extract_batch_host(OrbProgram* p, const uint8_t* frames_host, uint32_t n
     }
     if (rc) return rc;
     p->last_batch = n_frames;
+    p->batch_seq++;
     p->last_stream = s;
     p->single_valid = false;
     return ORB_OK;
@@ -1938,6 +1968,8 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     // one result buffer and one expanded-descriptor buffer per program: a match on another stream than the last one waits for it
     if (!p->match_done) HIP_TRY(p, hipEventCreateWithFlags(&p->match_done, hipEventDisableTiming));
     if (p->match_stream && p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
+    // and behind a verification on another stream, which still reads the matches this call overwrites
+    if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
     if (mfma && !i8) {
         {
             LaunchScope ls(p, s, KID_DESC_EXPAND);
@@ -1961,6 +1993,9 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     HIP_TRY(p, hipEventRecord(p->match_done, s));
     p->match_stream = s;
     p->last_stream = s;
+    p->match_seq = p->batch_seq;
+    p->match_set = p->cur_set;
+    p->match_frames = n_frames;
     return ORB_OK;
 }
 
@@ -1972,6 +2007,108 @@ int orb_match_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
     if (n > cap) n = cap;
     static_assert(sizeof(OrbMatch) == sizeof(MatchRecord), "OrbMatch layout");
     HIP_TRY(p, hipMemcpy(dst, p->d_matches + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbVerifyParams v{};
+    if (params) v = *params;
+    if (v.reserved[0] || v.reserved[1] || v.reserved[2]) return fail(p, ORB_EINVAL, "verify_consecutive: reserved words must be 0");
+    if (v.hypotheses > kVerifyMaxHyp || v.max_distance > 256u)
+        return fail(p, ORB_EINVAL, "verify_consecutive: hypotheses must be 0..%u and max_distance 0..256", kVerifyMaxHyp);
+    if (!(std::isfinite(v.ratio) && v.ratio >= 0.0f) || !(std::isfinite(v.inlier_px) && v.inlier_px >= 0.0f))
+        return fail(p, ORB_EINVAL, "verify_consecutive: ratio and inlier_px must be finite and >= 0");
+    if (!p->match_seq || p->match_seq != p->batch_seq)
+        return fail(p, ORB_ESTATE, "verify_consecutive: no orb_match_consecutive since the last batch");
+    if (p->match_set != p->cur_set)
+        return fail(p, ORB_ESTATE, "verify_consecutive: the output set changed since orb_match_consecutive");
+    if (n_frames < 2u || n_frames > p->match_frames)
+        return fail(p, ORB_EINVAL, "verify_consecutive: need 2..%u frames (the matched ones)", p->match_frames);
+    if (!v.hypotheses) v.hypotheses = 512u;
+    if (!v.max_distance) v.max_distance = 64u;
+    if (v.ratio == 0.0f) v.ratio = 0.8f;
+    if (v.inlier_px == 0.0f) v.inlier_px = 3.0f;
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    if (!p->d_vrec) {  // all six or none: a failure frees what was allocated, so the next call allocates again
+        void* buf[6] = {};
+        const size_t bytes[6] = {B * cap * sizeof(float4), B * cap * sizeof(uint32_t), B * sizeof(uint32_t),
+                                 B * kVerifyMaxHyp * sizeof(unsigned long long), B * sizeof(OrbPairModel), B * cap};
+        for (int i = 0; i < 6; i++) {
+            const hipError_t e = hipMalloc(&buf[i], bytes[i]);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
+                return fail(p, ORB_EHIP, "verify_consecutive: hipMalloc of %zu bytes failed: %s", bytes[i], hipGetErrorString(e));
+            }
+        }
+        p->d_vcand = static_cast<uint32_t*>(buf[1]);
+        p->d_vn = static_cast<uint32_t*>(buf[2]);
+        p->d_vkeys = static_cast<unsigned long long*>(buf[3]);
+        p->d_vmodel = static_cast<uint32_t*>(buf[4]);
+        p->d_vmask = static_cast<uint8_t*>(buf[5]);
+        p->d_vrec = static_cast<float4*>(buf[0]);
+    }
+    if (!p->verify_done) HIP_TRY(p, hipEventCreateWithFlags(&p->verify_done, hipEventDisableTiming));
+    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
+    // the matches come from the matcher's stream; the buffers are the last verification's, which may run on another one
+    if (p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
+    if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
+    // GV-2: coordinates centred on the level-0 image and scaled by 2 / max(W, H)
+    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    VerifyArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.matches = p->d_matches;
+    a.cap = (uint32_t)cap;
+    a.hyps = v.hypotheses;
+    a.max_distance = v.max_distance;
+    a.ratio = v.ratio;
+    a.cx = 0.5f * (float)(W - 1u);
+    a.cy = 0.5f * (float)(H - 1u);
+    a.k = 2.0f / (float)(W > H ? W : H);
+    const float t = v.inlier_px * a.k;
+    a.t2 = t * t;
+    a.seed_mix = lowbias32(v.seed);
+    a.rec = p->d_vrec;
+    a.cand_of = p->d_vcand;
+    a.n_cand = p->d_vn;
+    a.keys = p->d_vkeys;
+    a.model = p->d_vmodel;
+    a.mask = p->d_vmask;
+    const uint32_t pairs = n_frames - 1u;
+    {
+        LaunchScope ls(p, s, KID_VERIFY_GATHER);
+        hipLaunchKernelGGL(k_verify_gather, dim3(pairs), dim3(256), 0, s, a);
+    }
+    {
+        LaunchScope ls(p, s, KID_VERIFY_SCORE);
+        hipLaunchKernelGGL(k_verify_score, dim3(pairs, (v.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a);
+    }
+    {
+        LaunchScope ls(p, s, KID_VERIFY_REFINE);
+        hipLaunchKernelGGL(k_verify_refine, dim3(pairs), dim3(256), 0, s, a);
+    }
+    HIP_TRY(p, hipGetLastError());
+    HIP_TRY(p, hipEventRecord(p->verify_done, s));
+    p->verify_stream = s;
+    p->verify_pairs = pairs;
+    p->last_stream = s;
+    return ORB_OK;
+}
+
+int orb_verify_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
+    if (!p) return ORB_EINVAL;
+    if (!p->verify_pairs) return fail(p, ORB_ESTATE, "verify_read before verify_consecutive");
+    if (pair >= p->verify_pairs || (!inlier && n)) return fail(p, ORB_EINVAL, "verify_read: pair %u of %u, or inlier is NULL", pair, p->verify_pairs);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(p->verify_done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    static_assert(sizeof(OrbPairModel) == kVerifyModelWords * sizeof(uint32_t) && sizeof(OrbVerifyParams) == 32, "verify layouts");
+    if (model) HIP_TRY(p, hipMemcpy(model, p->d_vmodel + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(inlier, p->d_vmask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("TINYORB_LIB") or os.path.join(os.path.dirname(os.path
 
 ORB_OK, ORB_EINVAL, ORB_EHIP, ORB_ECAPACITY, ORB_ESTATE = 0, 1, 2, 3, 4
 ORB_PLANE_GRAY, ORB_PLANE_BLUR = 0, 1
-ORB_KERNEL_COUNT = 22
+ORB_KERNEL_COUNT = 25
 ORB_FLAG_STAGED = 1
 ORB_FLAG_DOUBLE_OUTPUT = 2
 ORB_FLAG_NMS = 4
@@ -40,6 +40,11 @@ CORNER_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("angle", "<u4"), ("octave"
 MATCH_DTYPE = np.dtype([("index", "<u4"), ("distance", "<u2"), ("second", "<u2")])
 ORB_MATCH_NONE = 0xFFFFFFFF
 DESCRIPTOR_DTYPE = np.dtype([("bits", "u1", (32,))])
+# geometric verification (orb_verify_consecutive): OrbPairModel (64 B) and its status codes
+VERIFY_MODEL_DTYPE = np.dtype([("h", "<f4", (9,)), ("candidates", "<u4"), ("inliers", "<u4"), ("hypothesis", "<u4"),
+                               ("status", "<u4"), ("reserved", "<u4", (3,))])
+ORB_VERIFY_OK, ORB_VERIFY_FEW, ORB_VERIFY_DEGENERATE, ORB_VERIFY_MINIMAL = 0, 1, 2, 3
+ORB_VERIFY_MAX_HYPOTHESES = 4096
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -58,6 +63,7 @@ EXPORTS = [
     "orb_node_read_collated", "orb_node_collate_begin", "orb_node_collate_end", "orb_node_pending",
     "orb_extract_batch_pinned", "orb_upload_sync", "orb_node_exchange_backend", "orb_node_rccl_pairs",
     "orb_write_input_image_pinned", "orb_node_set_results", "orb_node_shard_result",
+    "orb_verify_consecutive", "orb_verify_read",
 ]
 
 
@@ -81,6 +87,12 @@ class _Extent3d(ctypes.Structure):
 class _Config(ctypes.Structure):
     _fields_ = [("image_size", _Extent3d), ("max_features", ctypes.c_uint32), ("hierarchy_depth", ctypes.c_uint32),
                 ("initial_threshold", ctypes.c_float)]
+
+
+class _VerifyParams(ctypes.Structure):
+    """OrbVerifyParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("hypotheses", ctypes.c_uint32), ("max_distance", ctypes.c_uint32), ("ratio", ctypes.c_float),
+                ("inlier_px", ctypes.c_float), ("seed", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
 class _Options(ctypes.Structure):
@@ -153,6 +165,8 @@ def load_library(path=None):
     L.orb_debug_rot_table.argtypes = [vp, vp, sz, vp, vp]
     L.orb_match_consecutive.argtypes = [vp, u32, vp]
     L.orb_match_read.argtypes = [vp, u32, vp, ctypes.c_size_t]
+    L.orb_verify_consecutive.argtypes = [vp, u32, ctypes.POINTER(_VerifyParams), vp]
+    L.orb_verify_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_profile_enable.argtypes = [vp, ctypes.c_int]
     L.orb_profile_reset.argtypes = [vp]
     L.orb_profile_get.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
@@ -477,6 +491,26 @@ class OrbProgram:
         out = np.zeros(n, dtype=MATCH_DTYPE)
         self._check(self._lib.orb_match_read(self._handle(), frame, _ptr(out), n))
         return out
+
+    def verify_consecutive(self, n_frames, hypotheses=0, max_distance=0, ratio=0.0, inlier_px=0.0, seed=0, stream=None, reserved=(0, 0, 0)):
+        """Geometric verification of the last match_consecutive (not in the reference): per pair
+        (f, f+1), f < n_frames - 1, a RANSAC fit of a homography over `hypotheses` minimal samples (0: 512) of the candidates --
+        matches with distance <= max_distance (0: 64) and distance < ratio * second (0: 0.8) -- a least-squares refit over the
+        winner's inliers (transfer error below inlier_px level-0 pixels, 0: 3.0) and an inlier byte per query.  Asynchronous on
+        `stream` (None: the stream of the program's last batched call, match or verification, as the matcher chooses); raises OrbError(ORB_ESTATE) without a match of the current batch and output set."""
+        prm = _VerifyParams(hypotheses, max_distance, float(np.float32(ratio)), float(np.float32(inlier_px)), seed & 0xFFFFFFFF,
+                            (ctypes.c_uint32 * 3)(*reserved))
+        self._check(self._lib.orb_verify_consecutive(self._handle(), n_frames, ctypes.byref(prm),
+                                                     ctypes.c_void_p(stream) if stream else None))
+
+    def verify_read(self, pair, n):
+        """(record of VERIFY_MODEL_DTYPE, uint8[min(n, max_features)] inlier bytes of pair's queries) -- synchronises.  The record's
+        h maps level-0 keypoint coordinates of frame `pair` to frame `pair` + 1 (row-major; literal mode: the mirrored y of the
+        keypoints)."""
+        rec = np.zeros((), dtype=VERIFY_MODEL_DTYPE)
+        mask = np.zeros(min(n, self.config.max_features), dtype=np.uint8)
+        self._check(self._lib.orb_verify_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
+        return rec, mask
 
     def batch_select_output(self, slot):
         self._check(self._lib.orb_batch_select_output(self._handle(), slot))
