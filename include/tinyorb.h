@@ -400,6 +400,43 @@ int orb_verify_consecutive(OrbProgram *p, uint32_t n_frames, const OrbVerifyPara
  * for every other query. */
 int orb_verify_read(OrbProgram *p, uint32_t pair, OrbPairModel *model, uint8_t *inlier, size_t n);
 
+/* ---- guided matching, "search by projection" (NOT in the reference; definition GM-1..GM-6 in DESIGN.md section 14) ----
+ * For every consecutive pair (f, f+1) of the last batch: each stored keypoint i of frame f is sent through a row-major 3 x 3
+ * model M (level-0 coordinates of orb_corner_level0_xy, binary32, no fused operations, in the order
+ * w = (m6 x + m7 y) + m8, px = ((m0 x + m1 y) + m2) / w, py = ((m3 x + m4 y) + m5) / w) and matched against the stored
+ * keypoints j of frame f+1 with fabsf(x_j - px) <= r and fabsf(y_j - py) <= r (and, with octave_window n > 0,
+ * |octave_j - octave_i| < n) only.  The record is orb_match_consecutive's restricted to that window: the smallest
+ * popcount(desc_f[i] ^ desc_f+1[j]), ties to the smallest j, `second` the smallest distance over the window's other j;
+ * ORB_MATCH_NONE / 0xffff / 0xffff without a target or without a prediction (w not > 0, px or py not finite, no model).
+ * Queries past a frame's stored keypoints get ORB_MATCH_NONE records.  With ORB_GUIDE_IDENTITY, octave_window 0 and a radius
+ * that covers the frame every record equals orb_match_consecutive's. */
+typedef struct {              /* zero-initialised = the defaults */
+    uint32_t source;          /* ORB_GUIDE_VERIFIED (0), ORB_GUIDE_IDENTITY (1), ORB_GUIDE_HOST (2) */
+    float radius_px;          /* window half-size r in level-0 pixels, finite, >= 0 (0: 16) */
+    uint32_t octave_window;   /* 0: any octave; n: |octave_j - octave_i| < n */
+    uint32_t flags;           /* ORB_GUIDE_SCALE_RADIUS */
+    uint32_t reserved[4];     /* must be 0 (ORB_EINVAL otherwise) */
+} OrbGuideParams;             /* 32 bytes */
+
+#define ORB_GUIDE_VERIFIED 0u     /* the h of the pair's record from the last orb_verify_consecutive, if its status is OK or MINIMAL */
+#define ORB_GUIDE_IDENTITY 1u     /* the unit matrix: a window around the keypoint's own position */
+#define ORB_GUIDE_HOST 2u         /* models_host: (n_frames - 1) x 9 floats, read during the call */
+#define ORB_GUIDE_SCALE_RADIUS 1u /* r = radius_px * 2^octave_i */
+
+/* Matches the pairs (f, f+1), f in [0, n_frames - 1), of the last batch (params NULL: the defaults).  ORB_EINVAL when n_frames is
+ * not 2..frames of the last batch, max_features > 2^23, models_host is NULL with ORB_GUIDE_HOST or not NULL with another source,
+ * or a parameter is out of range; with ORB_GUIDE_VERIFIED, ORB_ESTATE when the last orb_verify_consecutive was not of the
+ * current batch and output set, ORB_EINVAL when n_frames - 1 exceeds its pairs.  Asynchronous on `stream` (NULL: the stream of
+ * the program's last batched call, match or verification, as the matcher chooses; the guided call does not change it), ordered
+ * behind the last verification and the last guided call when they ran on another stream.  ONE result buffer per program
+ * (allocated by the first call), apart from orb_match_consecutive's: a call overwrites the results of the call before and
+ * leaves the matcher's and the verifier's untouched.  Environment: TINYORB_GUIDE_CELL (read once per program) sets the
+ * cell size of the acceleration grid, which changes no record. */
+int orb_match_guided(OrbProgram *p, uint32_t n_frames, const OrbGuideParams *params, const float *models_host, void *stream);
+/* Copy up to n records of the queries of frame `frame` of the last orb_match_guided call to the host (synchronises);
+ * ORB_ESTATE before any call, ORB_EINVAL for a frame outside its pairs. */
+int orb_match_guided_read(OrbProgram *p, uint32_t frame, OrbMatch *dst, size_t n);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

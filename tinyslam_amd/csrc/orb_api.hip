@@ -26,6 +26,7 @@
 #include "orb_kernels_collate.h"
 #include "orb_kernels_match.h"
 #include "orb_kernels_verify.h"
+#include "orb_kernels_guide.h"
 
 using namespace orb;
 
@@ -127,6 +128,19 @@ struct OrbProgram {
     hipEvent_t verify_done = nullptr;
     hipStream_t verify_stream = nullptr;
     uint32_t verify_pairs = 0;            // pairs of the last verify call (0: none)
+    uint64_t verify_seq = 0;              // batch_seq of the batch the last verify call read (its match's)
+    uint32_t verify_set = 0;              // output set it read
+    // orb_match_guided (orb_kernels_guide.h): one set of buffers per program, allocated by the first call
+    uint4* d_gsrec = nullptr;             // [max_batch][max_features] records in cell order (x0, y0, index, octave)
+    uint4* d_gsdesc = nullptr;            // [max_batch][max_features][2] descriptors in cell order
+    uint32_t* d_gcell = nullptr;          // [max_batch][kGuideMaxCells + 1] cell starts
+    MatchRecord* d_gmatch = nullptr;      // [max_batch][max_features] results
+    float* d_gmodel = nullptr;            // [max_batch][9] the caller's models (ORB_GUIDE_HOST)
+    float* h_gmodel = nullptr;            // pinned staging of the same
+    hipEvent_t guide_done = nullptr;
+    hipStream_t guide_stream = nullptr;
+    uint32_t guide_pairs = 0;             // pairs of the last guided call (0: none)
+    int guide_cell = -1;                  // log2 of the grid's cell size (TINYORB_GUIDE_CELL); -1 until the first call
     uint32_t* d_prov2_counts = nullptr;
     CornerData* d_prov2 = nullptr;
     float* d_prov2_scores = nullptr;
@@ -1321,6 +1335,13 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_vmodel);
     (void)hipFree(p->d_vmask);
     if (p->verify_done) (void)hipEventDestroy(p->verify_done);
+    (void)hipFree(p->d_gsrec);
+    (void)hipFree(p->d_gsdesc);
+    (void)hipFree(p->d_gcell);
+    (void)hipFree(p->d_gmatch);
+    (void)hipFree(p->d_gmodel);
+    if (p->h_gmodel) (void)hipHostFree(p->h_gmodel);
+    if (p->guide_done) (void)hipEventDestroy(p->guide_done);
     if (p->single_done_ev) (void)hipEventDestroy(p->single_done_ev);
     if (p->h_count) (void)hipHostFree(p->h_count);
     if (p->d_single_done) (void)hipFree(p->d_single_done);
@@ -2055,6 +2076,8 @@ int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyPara
     // the matches come from the matcher's stream; the buffers are the last verification's, which may run on another one
     if (p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
     if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
+    // and behind a guided match on another stream, which may still read the models this call overwrites
+    if (p->guide_stream && p->guide_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->guide_done, 0));
     // GV-2: coordinates centred on the level-0 image and scaled by 2 / max(W, H)
     const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
     VerifyArgs a{};
@@ -2094,6 +2117,8 @@ int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyPara
     HIP_TRY(p, hipEventRecord(p->verify_done, s));
     p->verify_stream = s;
     p->verify_pairs = pairs;
+    p->verify_seq = p->match_seq;
+    p->verify_set = p->match_set;
     p->last_stream = s;
     return ORB_OK;
 }
@@ -2109,6 +2134,117 @@ int orb_verify_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* 
     static_assert(sizeof(OrbPairModel) == kVerifyModelWords * sizeof(uint32_t) && sizeof(OrbVerifyParams) == 32, "verify layouts");
     if (model) HIP_TRY(p, hipMemcpy(model, p->d_vmodel + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
     if (n) HIP_TRY(p, hipMemcpy(inlier, p->d_vmask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbGuideParams g{};
+    if (params) g = *params;
+    if (g.reserved[0] || g.reserved[1] || g.reserved[2] || g.reserved[3]) return fail(p, ORB_EINVAL, "match_guided: reserved words must be 0");
+    if (g.source > ORB_GUIDE_HOST || (g.flags & ~ORB_GUIDE_SCALE_RADIUS))
+        return fail(p, ORB_EINVAL, "match_guided: unknown source %u or flags 0x%x", g.source, g.flags);
+    if (!(std::isfinite(g.radius_px) && g.radius_px >= 0.0f)) return fail(p, ORB_EINVAL, "match_guided: radius_px must be finite and >= 0");
+    if (n_frames < 2u || n_frames > p->last_batch)
+        return fail(p, ORB_EINVAL, "match_guided: need 2..%u frames of the last batch", p->last_batch);
+    if (p->cfg.max_features > (1u << 23)) return fail(p, ORB_EINVAL, "match_guided: max_features must be <= 2^23");
+    if ((g.source == ORB_GUIDE_HOST) != (models_host != nullptr))
+        return fail(p, ORB_EINVAL, "match_guided: models_host is required with ORB_GUIDE_HOST and only then");
+    if (g.source == ORB_GUIDE_VERIFIED) {
+        if (!p->verify_pairs || p->verify_seq != p->batch_seq || p->verify_set != p->cur_set)
+            return fail(p, ORB_ESTATE, "match_guided: no orb_verify_consecutive of the current batch and output set");
+        if (n_frames - 1u > p->verify_pairs)
+            return fail(p, ORB_EINVAL, "match_guided: %u pairs, the last verification has %u", n_frames - 1u, p->verify_pairs);
+    }
+    if (g.radius_px == 0.0f) g.radius_px = 16.0f;
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    if (p->guide_cell < 0) {  // the smallest cell (8, or TINYORB_GUIDE_CELL: a power of two 1..256) that keeps the frame within kGuideMaxCells
+        int sh = 3;
+        if (const char* e = getenv("TINYORB_GUIDE_CELL")) {
+            const int c = atoi(e);
+            if (c >= 1 && c <= 256 && (c & (c - 1)) == 0) sh = __builtin_ctz((unsigned)c);
+        }
+        while ((size_t)((W + (1u << sh) - 1u) >> sh) * ((H + (1u << sh) - 1u) >> sh) > kGuideMaxCells) sh++;
+        p->guide_cell = sh;
+    }
+    if (!p->d_gsrec) {  // all or none: a failure frees what was allocated, so the next call allocates again
+        void* buf[5] = {};
+        const size_t bytes[5] = {B * cap * sizeof(uint4), B * cap * 2u * sizeof(uint4), B * (kGuideMaxCells + 1u) * sizeof(uint32_t),
+                                 B * cap * sizeof(MatchRecord), B * 9u * sizeof(float)};
+        for (int i = 0; i < 5; i++) {
+            const hipError_t e = hipMalloc(&buf[i], bytes[i]);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
+                return fail(p, ORB_EHIP, "match_guided: hipMalloc of %zu bytes failed: %s", bytes[i], hipGetErrorString(e));
+            }
+        }
+        void* h = nullptr;
+        const hipError_t e = hipHostMalloc(&h, B * 9u * sizeof(float), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            for (int j = 0; j < 5; j++) (void)hipFree(buf[j]);
+            return fail(p, ORB_EHIP, "match_guided: hipHostMalloc failed: %s", hipGetErrorString(e));
+        }
+        p->d_gsdesc = static_cast<uint4*>(buf[1]);
+        p->d_gcell = static_cast<uint32_t*>(buf[2]);
+        p->d_gmatch = static_cast<MatchRecord*>(buf[3]);
+        p->d_gmodel = static_cast<float*>(buf[4]);
+        p->h_gmodel = static_cast<float*>(h);
+        p->d_gsrec = static_cast<uint4*>(buf[0]);
+    }
+    if (!p->guide_done) HIP_TRY(p, hipEventCreateWithFlags(&p->guide_done, hipEventDisableTiming));
+    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
+    // the models come from the last verification; the buffers are the last guided call's, which may run on another stream
+    if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
+    if (p->guide_stream && p->guide_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->guide_done, 0));
+    const uint32_t pairs = n_frames - 1u;
+    if (g.source == ORB_GUIDE_HOST) {  // through the pinned staging buffer, once the previous call's copy out of it is done
+        if (p->guide_stream) HIP_TRY(p, hipEventSynchronize(p->guide_done));
+        memcpy(p->h_gmodel, models_host, (size_t)pairs * 9u * sizeof(float));
+        HIP_TRY(p, hipMemcpyAsync(p->d_gmodel, p->h_gmodel, (size_t)pairs * 9u * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    GuideArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.desc = p->d_desc;
+    a.cap = (uint32_t)cap;
+    a.shift = (uint32_t)p->guide_cell;
+    a.gw = (W + (1u << a.shift) - 1u) >> a.shift;
+    a.gh = (H + (1u << a.shift) - 1u) >> a.shift;
+    a.srec = p->d_gsrec;
+    a.sdesc = p->d_gsdesc;
+    a.cell_start = p->d_gcell;
+    a.pairs = pairs;
+    a.source = g.source;
+    a.vmodel = p->d_vmodel;
+    a.hmodel = p->d_gmodel;
+    a.radius = g.radius_px;
+    a.octave_window = g.octave_window;
+    a.scale_radius = (g.flags & ORB_GUIDE_SCALE_RADIUS) ? 1u : 0u;
+    a.out = p->d_gmatch;
+    hipLaunchKernelGGL(k_guide_bin, dim3(n_frames), dim3(kGuideBinThreads), 0, s, a);
+    hipLaunchKernelGGL(k_guide_search, dim3(pairs * (unsigned)((cap + kGuideSearchThreads - 1u) / kGuideSearchThreads)),
+                       dim3(kGuideSearchThreads), 0, s, a);
+    HIP_TRY(p, hipGetLastError());
+    HIP_TRY(p, hipEventRecord(p->guide_done, s));
+    p->guide_stream = s;
+    p->guide_pairs = pairs;
+    return ORB_OK;
+}
+
+int orb_match_guided_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
+    if (!p) return ORB_EINVAL;
+    if (!p->guide_pairs) return fail(p, ORB_ESTATE, "match_guided_read before match_guided");
+    if (frame >= p->guide_pairs || (!dst && n)) return fail(p, ORB_EINVAL, "match_guided_read: frame %u of %u, or dst is NULL", frame, p->guide_pairs);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(p->guide_done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    static_assert(sizeof(OrbGuideParams) == 32, "OrbGuideParams layout");
+    if (n) HIP_TRY(p, hipMemcpy(dst, p->d_gmatch + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

@@ -45,6 +45,9 @@ VERIFY_MODEL_DTYPE = np.dtype([("h", "<f4", (9,)), ("candidates", "<u4"), ("inli
                                ("status", "<u4"), ("reserved", "<u4", (3,))])
 ORB_VERIFY_OK, ORB_VERIFY_FEW, ORB_VERIFY_DEGENERATE, ORB_VERIFY_MINIMAL = 0, 1, 2, 3
 ORB_VERIFY_MAX_HYPOTHESES = 4096
+# guided matching (orb_match_guided): where a pair's model comes from, and the flag of OrbGuideParams
+ORB_GUIDE_VERIFIED, ORB_GUIDE_IDENTITY, ORB_GUIDE_HOST = 0, 1, 2
+ORB_GUIDE_SCALE_RADIUS = 1
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -63,7 +66,7 @@ EXPORTS = [
     "orb_node_read_collated", "orb_node_collate_begin", "orb_node_collate_end", "orb_node_pending",
     "orb_extract_batch_pinned", "orb_upload_sync", "orb_node_exchange_backend", "orb_node_rccl_pairs",
     "orb_write_input_image_pinned", "orb_node_set_results", "orb_node_shard_result",
-    "orb_verify_consecutive", "orb_verify_read",
+    "orb_verify_consecutive", "orb_verify_read", "orb_match_guided", "orb_match_guided_read",
 ]
 
 
@@ -93,6 +96,12 @@ class _VerifyParams(ctypes.Structure):
     """OrbVerifyParams (32 bytes; zero fields = the defaults)"""
     _fields_ = [("hypotheses", ctypes.c_uint32), ("max_distance", ctypes.c_uint32), ("ratio", ctypes.c_float),
                 ("inlier_px", ctypes.c_float), ("seed", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class _GuideParams(ctypes.Structure):
+    """OrbGuideParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("source", ctypes.c_uint32), ("radius_px", ctypes.c_float), ("octave_window", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
 
 
 class _Options(ctypes.Structure):
@@ -167,6 +176,8 @@ def load_library(path=None):
     L.orb_match_read.argtypes = [vp, u32, vp, ctypes.c_size_t]
     L.orb_verify_consecutive.argtypes = [vp, u32, ctypes.POINTER(_VerifyParams), vp]
     L.orb_verify_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_match_guided.argtypes = [vp, u32, ctypes.POINTER(_GuideParams), vp, vp]
+    L.orb_match_guided_read.argtypes = [vp, u32, vp, sz]
     L.orb_profile_enable.argtypes = [vp, ctypes.c_int]
     L.orb_profile_reset.argtypes = [vp]
     L.orb_profile_get.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
@@ -511,6 +522,31 @@ class OrbProgram:
         mask = np.zeros(min(n, self.config.max_features), dtype=np.uint8)
         self._check(self._lib.orb_verify_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
         return rec, mask
+
+    def match_guided(self, n_frames, source=ORB_GUIDE_VERIFIED, radius_px=0.0, octave_window=0, scale_radius=False, models=None,
+                     stream=None, flags=0, reserved=(0, 0, 0, 0)):
+        """Guided matching of the last batch (not in the reference): per pair (f, f+1),
+        f < n_frames - 1, every keypoint of f is sent through the pair's 3 x 3 model -- the last verify_consecutive's h
+        (ORB_GUIDE_VERIFIED, pairs with status OK / MINIMAL only), the unit matrix (ORB_GUIDE_IDENTITY) or models[f]
+        (ORB_GUIDE_HOST: (n_frames - 1) x 9 or x 3 x 3 float32, read during the call) -- and matched against the keypoints of f+1
+        within radius_px level-0 pixels of the prediction (0: 16; times 2^octave with scale_radius) and, with octave_window n > 0,
+        |octave difference| < n.  Asynchronous on `stream` (None: the stream of the program's last batched call, match or
+        verification, as the matcher chooses).  `flags` and `reserved` are OR'ed / passed into OrbGuideParams as they are."""
+        prm = _GuideParams(source, float(np.float32(radius_px)), octave_window, (ORB_GUIDE_SCALE_RADIUS if scale_radius else 0) | flags,
+                           (ctypes.c_uint32 * 4)(*reserved))
+        m = None
+        if models is not None:
+            m = np.ascontiguousarray(models, dtype=np.float32)
+            if source == ORB_GUIDE_HOST and m.size < (n_frames - 1) * 9:
+                raise ValueError("models: need (n_frames - 1) x 9 floats, got %d" % m.size)
+        self._check(self._lib.orb_match_guided(self._handle(), n_frames, ctypes.byref(prm), _ptr(m) if m is not None else None,
+                                               ctypes.c_void_p(stream) if stream else None))
+
+    def match_guided_read(self, frame, n):
+        """MATCH_DTYPE records of the queries of `frame` (the first min(n, max_features)) of the last match_guided -- synchronises."""
+        out = np.zeros(min(n, self.config.max_features), dtype=MATCH_DTYPE)
+        self._check(self._lib.orb_match_guided_read(self._handle(), frame, _ptr(out) if len(out) else None, len(out)))
+        return out
 
     def batch_select_output(self, slot):
         self._check(self._lib.orb_batch_select_output(self._handle(), slot))
