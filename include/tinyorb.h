@@ -437,6 +437,64 @@ int orb_match_guided(OrbProgram *p, uint32_t n_frames, const OrbGuideParams *par
  * ORB_ESTATE before any call, ORB_EINVAL for a frame outside its pairs. */
 int orb_match_guided_read(OrbProgram *p, uint32_t frame, OrbMatch *dst, size_t n);
 
+/* ---- feature tracks and keyframes (NOT in the reference; definition TK-1..TK-5 in DESIGN.md section 15) ----
+ * Over the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: query i of frame f links to target j of frame f+1 by the
+ * source's record (VERIFIED: the matcher's record where the last verification's inlier byte is 1; GUIDED / MATCHED: the last
+ * orb_match_guided's / orb_match_consecutive's record when it passes the verifier's candidate test with max_distance and ratio).
+ * Of the links to one target only the one with the smallest key (distance << 23) | i survives, giving prev / next; head_* and
+ * tail_frame follow them to the ends of the chain.  Keyframes: frame 0, then every frame f at least min_gap after the current
+ * keyframe k with max_gap reached (max_gap != 0), no track left from k to f, 1000 shared < keep_permille links_out(k), or
+ * shared < min_shared, where shared = the tracks that run from k to f. */
+typedef struct {              /* zero-initialised = the defaults */
+    uint32_t source;          /* ORB_TRACK_VERIFIED (0), ORB_TRACK_GUIDED (1), ORB_TRACK_MATCHED (2) */
+    uint32_t max_distance;    /* GUIDED / MATCHED: 0..256 (0: 64); must be 0 with VERIFIED */
+    float ratio;              /* GUIDED / MATCHED: finite, >= 0 (0: 0.8); must be 0 with VERIFIED */
+    uint32_t min_gap;         /* frames between keyframes, at least (0: 1) */
+    uint32_t max_gap;         /* 0: no bound; else >= min_gap */
+    uint32_t keep_permille;   /* 1..1000 (0: 900) */
+    uint32_t min_shared;      /* 0: no absolute floor */
+    uint32_t reserved;        /* must be 0 (ORB_EINVAL otherwise) */
+} OrbTrackParams;             /* 32 bytes */
+
+#define ORB_TRACK_VERIFIED 0u     /* the last orb_verify_consecutive's inliers (and the matcher's records it verified) */
+#define ORB_TRACK_GUIDED 1u       /* the last orb_match_guided's records */
+#define ORB_TRACK_MATCHED 2u      /* the last orb_match_consecutive's records */
+
+typedef struct {
+    uint32_t prev;            /* the keypoint of frame f-1 linked to this one, ORB_MATCH_NONE if none */
+    uint32_t next;            /* the keypoint of frame f+1 this one links to, ORB_MATCH_NONE if none */
+    uint32_t head_index;      /* first keypoint of the chain (this one if prev is NONE) */
+    uint16_t head_frame;      /* its frame */
+    uint16_t tail_frame;      /* the frame of the chain's last keypoint */
+} OrbTrack;                   /* 16 bytes; entries past a frame's stored keypoints: NONE, NONE, NONE, 0xffff, 0xffff */
+
+typedef struct {
+    uint32_t keypoints;       /* min(count, max_features) */
+    uint32_t links_in;        /* keypoints with prev != NONE */
+    uint32_t links_out;       /* keypoints with next != NONE */
+    uint32_t keyframe;        /* 1 for a keyframe */
+    uint32_t ref_keyframe;    /* the keyframe the frame was tested against (0 for frame 0) */
+    uint32_t shared;          /* tracks running from ref_keyframe to this frame */
+    uint32_t reserved[2];     /* 0 */
+} OrbTrackFrame;              /* 32 bytes */
+
+/* Chains the pairs of the last batch into tracks and picks keyframes (params NULL: the defaults).  ORB_EINVAL when n_frames is not
+ * 2..min(4096, frames of the last batch) or exceeds the source's pairs + 1, max_features > 2^23, or a parameter is out of range;
+ * ORB_ESTATE when the source's last call was not of the current batch and output set (VERIFIED: also when the matcher ran on
+ * another batch or output set than the verification).  Asynchronous on `stream` (NULL: the stream of the program's last batched
+ * call; the track call does not change it), ordered behind the source's last call and the last track call when they ran on another
+ * stream; orb_match_consecutive, orb_verify_consecutive and orb_match_guided wait for a track call on another stream.  Result
+ * buffers of its own (allocated by the first call): the matcher's, the verifier's and the guided call's are never written.
+ * Environment: TINYORB_TRACK_GLOBAL_KEYS=1 (read once per program) keeps the link keys in global memory, which changes no
+ * result. */
+int orb_track_consecutive(OrbProgram *p, uint32_t n_frames, const OrbTrackParams *params, void *stream);
+/* Copy up to n OrbTrack entries of frame `frame` of the last orb_track_consecutive call to the host (synchronises); ORB_ESTATE
+ * before any call, ORB_EINVAL for a frame outside its frames. */
+int orb_track_read(OrbProgram *p, uint32_t frame, OrbTrack *dst, size_t n);
+/* Copy the first min(n, n_frames) OrbTrackFrame records of the last orb_track_consecutive call (synchronises); ORB_ESTATE before
+ * any call. */
+int orb_track_frames(OrbProgram *p, OrbTrackFrame *dst, size_t n);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

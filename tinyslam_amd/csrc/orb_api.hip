@@ -27,6 +27,7 @@
 #include "orb_kernels_match.h"
 #include "orb_kernels_verify.h"
 #include "orb_kernels_guide.h"
+#include "orb_kernels_track.h"
 
 using namespace orb;
 
@@ -141,6 +142,21 @@ struct OrbProgram {
     hipStream_t guide_stream = nullptr;
     uint32_t guide_pairs = 0;             // pairs of the last guided call (0: none)
     int guide_cell = -1;                  // log2 of the grid's cell size (TINYORB_GUIDE_CELL); -1 until the first call
+    uint64_t guide_seq = 0;               // batch_seq of the batch the last guided call read
+    uint32_t guide_set = 0;               // output set it read
+    // orb_track_consecutive (orb_kernels_track.h): one set of buffers per program, allocated by the first call
+    uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
+    uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
+    uint32_t* d_tnext = nullptr;          // [max_batch][max_features]
+    uint4* d_tptr = nullptr;              // [2][max_batch][max_features] pointer-doubling ping-pong
+    uint4* d_track = nullptr;             // [max_batch][max_features] OrbTrack
+    uint32_t* d_tlinks = nullptr;         // [max_batch] links per pair
+    uint32_t* d_tshared = nullptr;        // [max_batch][max_batch] shared(k, f) at [f][k]
+    uint32_t* d_tframe = nullptr;         // [max_batch] OrbTrackFrame
+    hipEvent_t track_done = nullptr;
+    hipStream_t track_stream = nullptr;
+    uint32_t track_frames = 0;            // n_frames of the last track call (0: none)
+    int track_global_keys = -1;           // TINYORB_TRACK_GLOBAL_KEYS; -1 until the first call
     uint32_t* d_prov2_counts = nullptr;
     CornerData* d_prov2 = nullptr;
     float* d_prov2_scores = nullptr;
@@ -1342,6 +1358,15 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_gmodel);
     if (p->h_gmodel) (void)hipHostFree(p->h_gmodel);
     if (p->guide_done) (void)hipEventDestroy(p->guide_done);
+    (void)hipFree(p->d_tkeys);
+    (void)hipFree(p->d_tprev);
+    (void)hipFree(p->d_tnext);
+    (void)hipFree(p->d_tptr);
+    (void)hipFree(p->d_track);
+    (void)hipFree(p->d_tlinks);
+    (void)hipFree(p->d_tshared);
+    (void)hipFree(p->d_tframe);
+    if (p->track_done) (void)hipEventDestroy(p->track_done);
     if (p->single_done_ev) (void)hipEventDestroy(p->single_done_ev);
     if (p->h_count) (void)hipHostFree(p->h_count);
     if (p->d_single_done) (void)hipFree(p->d_single_done);
@@ -1991,6 +2016,8 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     if (p->match_stream && p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
     // and behind a verification on another stream, which still reads the matches this call overwrites
     if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
+    // and behind a track call on another stream, which may still read them
+    if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
     if (mfma && !i8) {
         {
             LaunchScope ls(p, s, KID_DESC_EXPAND);
@@ -2078,6 +2105,8 @@ int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyPara
     if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
     // and behind a guided match on another stream, which may still read the models this call overwrites
     if (p->guide_stream && p->guide_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->guide_done, 0));
+    // and behind a track call on another stream, which may still read the inlier bytes
+    if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
     // GV-2: coordinates centred on the level-0 image and scaled by 2 / max(W, H)
     const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
     VerifyArgs a{};
@@ -2200,6 +2229,8 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     // the models come from the last verification; the buffers are the last guided call's, which may run on another stream
     if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
     if (p->guide_stream && p->guide_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->guide_done, 0));
+    // and behind a track call on another stream, which may still read the records this call overwrites
+    if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
     const uint32_t pairs = n_frames - 1u;
     if (g.source == ORB_GUIDE_HOST) {  // through the pinned staging buffer, once the previous call's copy out of it is done
         if (p->guide_stream) HIP_TRY(p, hipEventSynchronize(p->guide_done));
@@ -2232,6 +2263,7 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     HIP_TRY(p, hipEventRecord(p->guide_done, s));
     p->guide_stream = s;
     p->guide_pairs = pairs;
+    p->guide_seq = p->batch_seq, p->guide_set = p->cur_set;
     return ORB_OK;
 }
 
@@ -2245,6 +2277,151 @@ int orb_match_guided_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n
     if (n > cap) n = cap;
     static_assert(sizeof(OrbGuideParams) == 32, "OrbGuideParams layout");
     if (n) HIP_TRY(p, hipMemcpy(dst, p->d_gmatch + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbTrackParams t{};
+    if (params) t = *params;
+    if (t.reserved) return fail(p, ORB_EINVAL, "track_consecutive: reserved word must be 0");
+    if (t.source > ORB_TRACK_MATCHED) return fail(p, ORB_EINVAL, "track_consecutive: unknown source %u", t.source);
+    if (t.source == ORB_TRACK_VERIFIED ? (t.max_distance != 0u || t.ratio != 0.0f)
+                                       : (t.max_distance > 256u || !(std::isfinite(t.ratio) && t.ratio >= 0.0f)))
+        return fail(p, ORB_EINVAL, "track_consecutive: max_distance must be 0..256 and ratio finite and >= 0 (both 0 with ORB_TRACK_VERIFIED)");
+    if (!t.min_gap) t.min_gap = 1u;
+    if (!t.keep_permille) t.keep_permille = 900u;
+    if (t.keep_permille > 1000u || (t.max_gap != 0u && t.max_gap < t.min_gap))
+        return fail(p, ORB_EINVAL, "track_consecutive: keep_permille must be 1..1000 and max_gap 0 or >= min_gap");
+    if (n_frames < 2u || n_frames > p->last_batch || n_frames > kTrackMaxFrames)
+        return fail(p, ORB_EINVAL, "track_consecutive: need 2..%u frames of the last batch", std::min(p->last_batch, kTrackMaxFrames));
+    if (p->cfg.max_features > (1u << 23)) return fail(p, ORB_EINVAL, "track_consecutive: max_features must be <= 2^23");
+    uint32_t pairs_avail = 0;
+    if (t.source == ORB_TRACK_VERIFIED) {
+        if (!p->verify_pairs || p->verify_seq != p->batch_seq || p->verify_set != p->cur_set || p->match_seq != p->verify_seq ||
+            p->match_set != p->verify_set)
+            return fail(p, ORB_ESTATE, "track_consecutive: no orb_verify_consecutive of the current batch, output set and matches");
+        pairs_avail = p->verify_pairs;
+    } else if (t.source == ORB_TRACK_GUIDED) {
+        if (!p->guide_pairs || p->guide_seq != p->batch_seq || p->guide_set != p->cur_set)
+            return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_guided of the current batch and output set");
+        pairs_avail = p->guide_pairs;
+    } else {
+        if (!p->match_seq || p->match_seq != p->batch_seq || p->match_set != p->cur_set)
+            return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_consecutive of the current batch and output set");
+        pairs_avail = p->match_frames - 1u;
+    }
+    if (n_frames - 1u > pairs_avail)
+        return fail(p, ORB_EINVAL, "track_consecutive: %u pairs, the source has %u", n_frames - 1u, pairs_avail);
+    if (t.source != ORB_TRACK_VERIFIED) {
+        if (!t.max_distance) t.max_distance = 64u;
+        if (t.ratio == 0.0f) t.ratio = 0.8f;
+    }
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    if (p->track_global_keys < 0) {
+        const char* e = getenv("TINYORB_TRACK_GLOBAL_KEYS");
+        p->track_global_keys = (e && atoi(e) != 0) ? 1 : 0;
+    }
+    if (!p->d_track) {  // all or none: a failure frees what was allocated, so the next call allocates again
+        void* buf[8] = {};
+        const size_t bytes[8] = {B * cap * sizeof(uint32_t), B * cap * sizeof(uint32_t), B * cap * sizeof(uint32_t),
+                                 2u * B * cap * sizeof(uint4), B * sizeof(uint32_t), B * B * sizeof(uint32_t),
+                                 B * sizeof(OrbTrackFrame), B * cap * sizeof(OrbTrack)};
+        for (int i = 0; i < 8; i++) {
+            const hipError_t e = hipMalloc(&buf[i], bytes[i]);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
+                return fail(p, ORB_EHIP, "track_consecutive: hipMalloc of %zu bytes failed: %s", bytes[i], hipGetErrorString(e));
+            }
+        }
+        p->d_tkeys = static_cast<uint32_t*>(buf[0]);
+        p->d_tprev = static_cast<uint32_t*>(buf[1]);
+        p->d_tnext = static_cast<uint32_t*>(buf[2]);
+        p->d_tptr = static_cast<uint4*>(buf[3]);
+        p->d_tlinks = static_cast<uint32_t*>(buf[4]);
+        p->d_tshared = static_cast<uint32_t*>(buf[5]);
+        p->d_tframe = static_cast<uint32_t*>(buf[6]);
+        p->d_track = static_cast<uint4*>(buf[7]);
+    }
+    if (!p->track_done) HIP_TRY(p, hipEventCreateWithFlags(&p->track_done, hipEventDisableTiming));
+    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
+    // the links come from the source's last call; the buffers are the last track call's, which may run on another stream
+    if (t.source != ORB_TRACK_GUIDED && p->match_stream && p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
+    if (t.source == ORB_TRACK_VERIFIED && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
+    if (t.source == ORB_TRACK_GUIDED && p->guide_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->guide_done, 0));
+    if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
+    TrackArgs a{};
+    a.counts = p->d_counts;
+    a.cap = (uint32_t)cap;
+    a.frames = n_frames;
+    a.stride = (uint32_t)B;
+    a.source = t.source;
+    a.rec = t.source == ORB_TRACK_GUIDED ? p->d_gmatch : p->d_matches;
+    a.mask = p->d_vmask;
+    a.max_distance = t.max_distance;
+    a.ratio = t.ratio;
+    a.gkeys = p->d_tkeys;
+    a.prev = p->d_tprev;
+    a.next = p->d_tnext;
+    a.links = p->d_tlinks;
+    a.ptr[0] = p->d_tptr;
+    a.ptr[1] = p->d_tptr + B * cap;
+    a.out = p->d_track;
+    a.shared = p->d_tshared;
+    a.min_gap = t.min_gap;
+    a.max_gap = t.max_gap;
+    a.keep_permille = t.keep_permille;
+    a.min_shared = t.min_shared;
+    a.frame_out = p->d_tframe;
+    const uint32_t pairs = n_frames - 1u;
+    if (!p->track_global_keys && cap <= kTrackLdsKeys)
+        hipLaunchKernelGGL(k_track_link<true>, dim3(pairs), dim3(kTrackLinkThreads), cap * sizeof(uint32_t), s, a);
+    else
+        hipLaunchKernelGGL(k_track_link<false>, dim3(pairs), dim3(kTrackLinkThreads), 0, s, a);
+    // pointer doubling: the first round covers chains of 2 links, every further one doubles that; ceil(log2(n_frames - 1)) rounds,
+    // at least one, the last of them inside k_track_hist
+    uint32_t rounds = 1u;
+    while ((1u << rounds) < pairs) rounds++;
+    a.first = 1u;
+    a.src = 1u;  // the first round writes ptr[0]
+    for (uint32_t r = 0; r + 1u < rounds; r++) {
+        hipLaunchKernelGGL(k_track_jump, dim3((unsigned)((cap + kTrackJumpThreads - 1u) / kTrackJumpThreads), n_frames),
+                           dim3(kTrackJumpThreads), 0, s, a);
+        a.first = 0u;
+        a.src ^= 1u;
+    }
+    hipLaunchKernelGGL(k_track_hist, dim3(n_frames), dim3(kTrackHistThreads), 0, s, a);
+    hipLaunchKernelGGL(k_track_key, dim3(1), dim3(kTrackKeyThreads), 0, s, a);
+    HIP_TRY(p, hipGetLastError());
+    HIP_TRY(p, hipEventRecord(p->track_done, s));
+    p->track_stream = s;
+    p->track_frames = n_frames;
+    return ORB_OK;
+}
+
+int orb_track_read(OrbProgram* p, uint32_t frame, OrbTrack* dst, size_t n) {
+    if (!p) return ORB_EINVAL;
+    if (!p->track_frames) return fail(p, ORB_ESTATE, "track_read before track_consecutive");
+    if (frame >= p->track_frames || (!dst && n)) return fail(p, ORB_EINVAL, "track_read: frame %u of %u, or dst is NULL", frame, p->track_frames);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(p->track_done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    static_assert(sizeof(OrbTrack) == 16 && sizeof(OrbTrackFrame) == 32 && sizeof(OrbTrackParams) == 32, "track layouts");
+    if (n) HIP_TRY(p, hipMemcpy(dst, p->d_track + (size_t)frame * cap, n * sizeof(OrbTrack), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_track_frames(OrbProgram* p, OrbTrackFrame* dst, size_t n) {
+    if (!p) return ORB_EINVAL;
+    if (!p->track_frames) return fail(p, ORB_ESTATE, "track_frames before track_consecutive");
+    if (!dst && n) return fail(p, ORB_EINVAL, "track_frames: dst is NULL");
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(p->track_done));
+    if (n > p->track_frames) n = p->track_frames;
+    if (n) HIP_TRY(p, hipMemcpy(dst, p->d_tframe, n * sizeof(OrbTrackFrame), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

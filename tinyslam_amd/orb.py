@@ -48,6 +48,11 @@ ORB_VERIFY_MAX_HYPOTHESES = 4096
 # guided matching (orb_match_guided): where a pair's model comes from, and the flag of OrbGuideParams
 ORB_GUIDE_VERIFIED, ORB_GUIDE_IDENTITY, ORB_GUIDE_HOST = 0, 1, 2
 ORB_GUIDE_SCALE_RADIUS = 1
+# feature tracks and keyframes (orb_track_consecutive): the link source, OrbTrack (16 B), OrbTrackFrame (32 B)
+ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
+TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
+TRACK_FRAME_DTYPE = np.dtype([("keypoints", "<u4"), ("links_in", "<u4"), ("links_out", "<u4"), ("keyframe", "<u4"),
+                              ("ref_keyframe", "<u4"), ("shared", "<u4"), ("reserved", "<u4", (2,))])
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -67,6 +72,7 @@ EXPORTS = [
     "orb_extract_batch_pinned", "orb_upload_sync", "orb_node_exchange_backend", "orb_node_rccl_pairs",
     "orb_write_input_image_pinned", "orb_node_set_results", "orb_node_shard_result",
     "orb_verify_consecutive", "orb_verify_read", "orb_match_guided", "orb_match_guided_read",
+    "orb_track_consecutive", "orb_track_read", "orb_track_frames",
 ]
 
 
@@ -102,6 +108,13 @@ class _GuideParams(ctypes.Structure):
     """OrbGuideParams (32 bytes; zero fields = the defaults)"""
     _fields_ = [("source", ctypes.c_uint32), ("radius_px", ctypes.c_float), ("octave_window", ctypes.c_uint32),
                 ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+class _TrackParams(ctypes.Structure):
+    """OrbTrackParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("source", ctypes.c_uint32), ("max_distance", ctypes.c_uint32), ("ratio", ctypes.c_float), ("min_gap", ctypes.c_uint32),
+                ("max_gap", ctypes.c_uint32), ("keep_permille", ctypes.c_uint32), ("min_shared", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 class _Options(ctypes.Structure):
@@ -178,6 +191,9 @@ def load_library(path=None):
     L.orb_verify_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_match_guided.argtypes = [vp, u32, ctypes.POINTER(_GuideParams), vp, vp]
     L.orb_match_guided_read.argtypes = [vp, u32, vp, sz]
+    L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
+    L.orb_track_read.argtypes = [vp, u32, vp, sz]
+    L.orb_track_frames.argtypes = [vp, vp, sz]
     L.orb_profile_enable.argtypes = [vp, ctypes.c_int]
     L.orb_profile_reset.argtypes = [vp]
     L.orb_profile_get.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
@@ -546,6 +562,31 @@ class OrbProgram:
         """MATCH_DTYPE records of the queries of `frame` (the first min(n, max_features)) of the last match_guided -- synchronises."""
         out = np.zeros(min(n, self.config.max_features), dtype=MATCH_DTYPE)
         self._check(self._lib.orb_match_guided_read(self._handle(), frame, _ptr(out) if len(out) else None, len(out)))
+        return out
+
+    def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
+                          min_shared=0, stream=None, reserved=0):
+        """Feature tracks and keyframes of the last batch (not in the reference): the pairs
+        (f, f + 1), f < n_frames - 1, are linked by the last verify_consecutive's inliers (ORB_TRACK_VERIFIED), the last
+        match_guided's records (ORB_TRACK_GUIDED) or the last match_consecutive's (ORB_TRACK_MATCHED) -- the latter two through
+        the verifier's candidate test with max_distance (0: 64) and ratio (0: 0.8) --, made one-to-one, chained into tracks, and
+        keyframes picked with min_gap (0: 1), max_gap (0: none), keep_permille (0: 900) and min_shared.  Asynchronous on `stream`
+        (None: the stream of the program's last batched call)."""
+        prm = _TrackParams(source, max_distance, float(np.float32(ratio)), min_gap, max_gap, keep_permille, min_shared, reserved)
+        self._check(self._lib.orb_track_consecutive(self._handle(), n_frames, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+        self._track_n = n_frames
+
+    def track_read(self, frame, n):
+        """TRACK_DTYPE entries of the keypoints of `frame` (the first min(n, max_features)) of the last track_consecutive --
+        synchronises."""
+        out = np.zeros(min(n, self.config.max_features), dtype=TRACK_DTYPE)
+        self._check(self._lib.orb_track_read(self._handle(), frame, _ptr(out) if len(out) else None, len(out)))
+        return out
+
+    def track_frames(self, n):
+        """TRACK_FRAME_DTYPE records of the first n frames of the last track_consecutive (at most its n_frames) -- synchronises."""
+        out = np.zeros(min(n, getattr(self, "_track_n", n)), dtype=TRACK_FRAME_DTYPE)
+        self._check(self._lib.orb_track_frames(self._handle(), _ptr(out) if len(out) else None, len(out)))
         return out
 
     def batch_select_output(self, slot):
