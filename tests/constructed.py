@@ -1,0 +1,437 @@
+"""Constructed records for the matcher, the verifier, guided matching and tracks (test infrastructure, not a test file).
+
+Extraction never drives these stages to the inputs their kernels were written around: ties across tile boundaries, a unique best at
+the last candidate, chains as long as the batch, many links to one target, windows that end exactly on a target.  The builders here
+make such records directly, each together with the outcome the construction implies, and `inject` writes them over the current
+output set of a program, so that match -> verify -> guided -> track run on them as on extracted records.
+
+Constructed records stay inside what extraction can produce: octave < depth, (x, y) inside that level, angle < 6284, no two records
+of one frame at one (x, y, octave).  Descriptors are arbitrary 256-bit values (uint32 (n, 8) arrays).  Random descriptors lie about
+128 +- 8 bits apart, so a planted descriptor within 40 bits of a query is that query's unique best among random ones (a random pair
+closer than 64 bits has probability below 1e-12).
+"""
+import numpy as np
+
+from tinyslam_amd.orb import CORNER_DTYPE, MATCH_DTYPE, ORB_MATCH_NONE as NONE, TRACK_DTYPE
+
+_POP8 = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint16)
+
+
+# ---- injection ---------------------------------------------------------------------------------------------------------------
+def inject(prog, counts, corners=None, descriptors=None):
+    """Overwrites the first len(counts) frames of the program's current output set: the raw counters (they may exceed the
+    capacity, as extraction's may), and, when given, frame f's records 0 .. m_f - 1 from corners[f] (CORNER_DTYPE (m_f,)) and
+    descriptors[f] (uint32 (m_f, 8)).  The program must hold a batch of at least len(counts) frames.  The stages run on the
+    program's stream, not torch's: the copies are finished before this returns."""
+    import torch
+    from tinyslam_amd import node
+    prog.batch_sync()
+    cfg = prog.config
+    B, cap = cfg.max_batch, cfg.max_features
+    dev = torch.device("cuda", cfg.device)
+    d_counts, d_corners, d_desc = prog.batch_device_buffers()
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    n = len(counts)
+    assert n <= B
+    node.as_tensor(d_counts, (B,), "<i4", dev)[:n].copy_(torch.from_numpy(counts.view(np.int32)))
+    tc = node.as_tensor(d_corners, (B, cap, 4), "<i4", dev)
+    td = node.as_tensor(d_desc, (B, cap, 8), "<i4", dev)
+    for f in range(n if corners is not None else 0):
+        c = np.ascontiguousarray(corners[f], dtype=CORNER_DTYPE)
+        assert len(c) <= cap
+        if len(c):
+            tc[f, :len(c)].copy_(torch.from_numpy(c.view(np.int32).reshape(len(c), 4)))
+    for f in range(n if descriptors is not None else 0):
+        d = np.ascontiguousarray(descriptors[f], dtype=np.uint32).reshape(-1, 8)
+        assert len(d) <= cap
+        if len(d):
+            td[f, :len(d)].copy_(torch.from_numpy(d.view(np.int32)))
+    torch.cuda.synchronize(dev)
+
+
+# ---- descriptors -------------------------------------------------------------------------------------------------------------
+def random_desc(rng, n):
+    return rng.integers(0, 1 << 32, size=(n, 8), dtype=np.uint32)
+
+
+def flip(desc, k, rng, lo=0, hi=256):
+    """Copies of `desc` ((n, 8) or (8,)) with k distinct bits in [lo, hi) flipped in each row: exactly k bits from the original."""
+    d = np.array(desc, dtype=np.uint32, ndmin=2, copy=True)
+    for r in range(len(d)):
+        bits = lo + rng.choice(hi - lo, size=k, replace=False)
+        for b in bits:
+            d[r, b >> 5] ^= np.uint32(1 << (int(b) & 31))
+    return d if np.ndim(desc) == 2 else d[0]
+
+
+def hamming(a, b):
+    """Row-wise popcount(a ^ b) of broadcastable uint32 (..., 8) arrays."""
+    x = np.bitwise_xor(np.asarray(a, dtype=np.uint32), np.asarray(b, dtype=np.uint32))
+    return _POP8[np.ascontiguousarray(x).view(np.uint8)].reshape(x.shape[:-1] + (32,)).sum(-1).astype(np.int64)
+
+
+def match_ref(qd, td, chunk=64):
+    """orb_match_consecutive's records by a dense argmin, in query chunks so that a full 16 383-candidate
+    frame fits in memory; equal to oracle/orb_numpy.match (tests/test_constructed_ref.py checks it).  Returns MATCH_DTYPE."""
+    qd, td = np.asarray(qd, np.uint32).reshape(-1, 8), np.asarray(td, np.uint32).reshape(-1, 8)
+    out = np.zeros(len(qd), MATCH_DTYPE)
+    out["index"] = NONE
+    out["distance"] = out["second"] = 0xFFFF
+    if not len(td):
+        return out
+    tb = np.ascontiguousarray(td).view(np.uint8)
+    for i0 in range(0, len(qd), chunk):
+        qb = np.ascontiguousarray(qd[i0:i0 + chunk]).view(np.uint8)
+        D = _POP8[qb[:, None, :] ^ tb[None, :, :]].sum(2, dtype=np.int64)
+        j = D.argmin(1)
+        r = np.arange(len(qb))
+        out["index"][i0:i0 + chunk] = j
+        out["distance"][i0:i0 + chunk] = D[r, j]
+        if len(td) > 1:
+            D[r, j] = 1 << 20
+            out["second"][i0:i0 + chunk] = D.min(1)
+    return out
+
+
+# ---- corners -----------------------------------------------------------------------------------------------------------------
+def corners(x, y, octave=0, angle=None, rng=None):
+    c = np.zeros(len(x), CORNER_DTYPE)
+    c["x"], c["y"], c["octave"] = x, y, octave
+    c["angle"] = angle if angle is not None else (rng.integers(0, 6284, len(x)) if rng is not None else 0)
+    return c
+
+
+def distinct_corners(rng, n, W, H, margin=0):
+    """n octave-0 records at distinct pixels of [margin, W - margin) x [margin, H - margin)."""
+    w, h = W - 2 * margin, H - 2 * margin
+    p = rng.choice(w * h, size=n, replace=False)
+    return corners(margin + p % w, margin + p // w, 0, rng=rng)
+
+
+# ---- matcher -----------------------------------------------------------------------------------------------------------------
+def planted_ties(rng, na, nb, groups, d=None):
+    """na random queries, nb random targets; groups[q] = indices planted for query q (a list of lists): every planted index holds
+    one copy of the query with d[q] bits flipped, so the query's best is min(group) at distance d[q], and with two copies or more
+    second == d[q]; with one copy the construction only bounds second (> distance + 40), and the record says 0xFFFF there.
+    Returns (qd, td, expected MATCH_DTYPE of the planted queries 0 .. len(groups) - 1)."""
+    assert len({j for js in groups for j in js}) == sum(len(js) for js in groups), "groups must not share a target"
+    qd, td = random_desc(rng, na), random_desc(rng, nb)
+    d = list(d) if d is not None else [int(v) for v in rng.integers(0, 30, len(groups))]
+    exp = np.zeros(len(groups), MATCH_DTYPE)
+    for q, js in enumerate(groups):
+        c = flip(qd[q], d[q], rng)
+        for j in js:
+            td[j] = c
+        exp[q] = (min(js), d[q], d[q] if len(js) > 1 else 0xFFFF)
+    return qd, td, exp
+
+
+def last_is_best(rng, na, nb, max_d=20):
+    """Queries that are all within max_d bits of target nb - 1 and random against the rest: every query's unique best is the last
+    candidate (the partial tile's last column).  Returns (qd, td, expected index / distance; second only bounded: > distance)."""
+    td = random_desc(rng, nb)
+    dist = rng.integers(0, max_d + 1, na)
+    qd = np.stack([flip(td[nb - 1], int(k), rng) for k in dist]) if na else np.zeros((0, 8), np.uint32)
+    exp = np.zeros(na, MATCH_DTYPE)
+    exp["index"], exp["distance"], exp["second"] = nb - 1, dist, 0xFFFF
+    return qd, td, exp
+
+
+def extremes(rng, nb):
+    """Distance 0 and 256 and the all-zero / all-one descriptors.  Targets: nb random, with target 3 all ones, target 5 all zeros.
+    Queries: 0 all zeros (best 5 at 0), 1 all ones (best 3 at 0), 2 = target 7 (best 7 at 0), 3 = the complement of target 9
+    (9 is the one target at 256: irrelevant to the best).  Returns (qd, td, expected records of queries 0..2)."""
+    td = random_desc(rng, nb)
+    td[3] = 0xFFFFFFFF
+    td[5] = 0
+    qd = np.stack([np.zeros(8, np.uint32), np.full(8, 0xFFFFFFFF, np.uint32), td[7].copy(), ~td[9]])
+    exp = np.zeros(3, MATCH_DTYPE)
+    exp["index"], exp["distance"], exp["second"] = (5, 3, 7), 0, 0xFFFF
+    return qd, td, exp
+
+
+def all_at_256(nq, nb):
+    """Every query the complement of every target: all candidates at distance 256, so index 0, distance 256, second 256 (one
+    target: second 0xFFFF)."""
+    td = np.full((nb, 8), 0xFFFFFFFF, np.uint32)
+    qd = np.zeros((nq, 8), np.uint32)
+    exp = np.zeros(nq, MATCH_DTYPE)
+    exp["index"], exp["distance"], exp["second"] = 0, 256, 256 if nb > 1 else 0xFFFF
+    return qd, td, exp
+
+
+def last_of_huge(rng, nq, nb):
+    """nb targets (up to 2^23) without a per-candidate computation: targets 0 .. nb - 2 are all ~Z except two planted ones, target
+    nb - 1 is Z; query q = Z with a[q] <= 40 bits flipped in bits 0 .. 127.  d(q, ~Z) = 256 - a[q]; target 1 = ~Z with 64 bits
+    of 128 .. 255 flipped: 192 - a[q]; target nb // 2 = Z with 60 bits of 128 .. 255 flipped: 60 + a[q].  So index nb - 1,
+    distance a[q], second 60 + a[q] (the runner-up is target nb // 2 for every query)."""
+    Z = random_desc(rng, 1)[0]
+    a = rng.integers(0, 41, nq)
+    qd = np.stack([flip(Z, int(k), rng, 0, 128) for k in a])
+    td = np.empty((nb, 8), np.uint32)
+    td[:] = ~Z
+    td[1] = flip(~Z, 64, rng, 128, 256)
+    td[nb // 2] = flip(Z, 60, rng, 128, 256)
+    td[nb - 1] = Z
+    exp = np.zeros(nq, MATCH_DTYPE)
+    exp["index"], exp["distance"], exp["second"] = nb - 1, a, 60 + a
+    return qd, td, exp
+
+
+# ---- tracks ------------------------------------------------------------------------------------------------------------------
+def chains(rng, starts, W, H, margin=0):
+    """Permutation chains.  starts: bool (n_frames, n_slots), row 0 all True: slot s gets a fresh random descriptor at every frame
+    where starts[f, s] and keeps the one before otherwise.  Each slot keeps one pixel in every frame (so every link is an inlier
+    of the identity), and each frame stores its slots in an order of its own, a random permutation.  A kept descriptor is a link
+    at distance 0 with a runner-up about 100 bits away; a fresh one leaves the query of the frame before without a candidate.
+
+    Returns dict(counts, corners (F, n), desc (F, n, 8), perm (F, n): the record index of slot s in frame f, and tracks: the
+    expected TRACK_DTYPE records of every frame (n entries) from the segments alone)."""
+    starts = np.asarray(starts, bool)
+    F, n = starts.shape
+    assert starts[0].all()
+    pos = distinct_corners(rng, n, W, H, margin)
+    perm = np.stack([rng.permutation(n) for _ in range(F)])
+    desc_slot = np.empty((F, n, 8), np.uint32)
+    for f in range(F):
+        fresh = random_desc(rng, n)
+        desc_slot[f] = np.where(starts[f][:, None], fresh, desc_slot[f - 1] if f else fresh)
+    desc = np.empty_like(desc_slot)
+    cor = np.empty((F, n), CORNER_DTYPE)
+    for f in range(F):
+        desc[f, perm[f]] = desc_slot[f]
+        cor[f, perm[f]] = pos
+    # expected tracks from the segments: head = the slot's last start <= f, tail = its next start > f, minus one
+    head = np.zeros((F, n), np.int64)
+    for f in range(F):
+        head[f] = np.where(starts[f], f, head[f - 1] if f else 0)
+    tail = np.zeros((F, n), np.int64)
+    for f in range(F - 1, -1, -1):
+        tail[f] = f if f == F - 1 else np.where(starts[f + 1], f, tail[f + 1])
+    tracks = []
+    slots = np.arange(n)
+    for f in range(F):
+        t = np.zeros(n, TRACK_DTYPE)
+        r = perm[f]
+        t["prev"][r] = np.where(starts[f], NONE, perm[f - 1] if f else 0)
+        t["next"][r] = np.where(starts[f + 1], NONE, perm[f + 1]) if f + 1 < F else NONE
+        t["head_frame"][r] = head[f]
+        t["head_index"][r] = perm[head[f], slots]
+        t["tail_frame"][r] = tail[f]
+        tracks.append(t)
+    return dict(counts=np.full(F, n, np.uint32), corners=cor, desc=desc, perm=perm, tracks=tracks)
+
+
+def exact_lengths(F, lengths, filler):
+    """starts for chains(): one slot per entry of `lengths` holding a track of exactly L links (L + 1 frames) that begins at frame
+    (37 L) mod (F - L), plus `filler` slots that run through the whole batch.  Returns (starts, [(slot, first frame, L)])."""
+    n = len(lengths) + filler
+    starts = np.zeros((F, n), bool)
+    starts[0] = True
+    spans = []
+    for s, L in enumerate(lengths):
+        a = (37 * L) % (F - L)
+        starts[a, s] = True
+        if a + L + 1 < F:
+            starts[a + L + 1, s] = True
+        spans.append((s, a, L))
+    return starts, spans
+
+
+def steady_loss(F, n):
+    """starts for chains(): slot t restarts at frame t + 1 (t < F - 1).  Then links_out(k) = n - 1 for k < F - 1, and
+    shared(k, f) = n - (f - k): the tracks that ran from k, less one per frame since."""
+    starts = np.zeros((F, n), bool)
+    starts[0] = True
+    for t in range(min(n, F - 1)):
+        starts[t + 1, t] = True
+    return starts
+
+
+def permille_for_gap(n, G):
+    """The keep_permille at which steady_loss(., n) first fires TK-5's permille clause at gap G: 1000 (n - G) < p (n - 1) but not
+    1000 (n - G + 1) < p (n - 1)."""
+    p = 1000 * (n - G) // (n - 1) + 1
+    assert 1000 * (n - G) < p * (n - 1) and not 1000 * (n - G + 1) < p * (n - 1) and 1 <= p <= 1000, (n, G, p)
+    return p
+
+
+def steady_keyframes(F, n, base, min_gap=1, max_gap=0, keep_permille=900, min_shared=0):
+    """TK-5 on a construction where shared(k, f) = n - (f - k) and links_out(k) = base for every k that can be a reference (a
+    perfect chain: n = base and no loss, written as shared = n): the decision depends on the gap alone, so the keyframes are the
+    multiples of the first gap G that fires.  Returns (keyframe, ref_keyframe, shared) over the F frames."""
+    loss = 0 if base == n else 1
+
+    def fires(g):
+        s = n - loss * g
+        return g >= min_gap and ((max_gap and g >= max_gap) or s == 0 or 1000 * s < keep_permille * base or s < min_shared)
+
+    G = next((g for g in range(1, F) if fires(g)), F)
+    key = np.zeros(F, np.uint32)
+    ref = np.zeros(F, np.uint32)
+    shared = np.zeros(F, np.uint32)
+    key[0], shared[0] = 1, n
+    for f in range(1, F):
+        ref[f] = ((f - 1) // G) * G
+        key[f] = f % G == 0
+        shared[f] = n - loss * (f - ref[f])
+    return key, ref, shared
+
+
+def contention(rng, nq, nt, groups):
+    """Many links to one target.  nt random targets, nq random queries; groups: [(j, [(i, d), ...]), ...]: query i is target j with
+    d bits flipped, so its best is j at distance d and it links under the defaults (d <= 20 < 64, second about 100).  TK-2 keeps
+    the smallest (d, i) of each group.  Returns (qd, td, {j: winning i}, every planted i)."""
+    qd, td = random_desc(rng, nq), random_desc(rng, nt)
+    win, planted = {}, []
+    for j, members in groups:
+        for i, d in members:
+            qd[i] = flip(td[j], d, rng)
+            planted.append(i)
+        win[j] = min(members, key=lambda m: (m[1], m[0]))[0]
+    return qd, td, win, planted
+
+
+# ---- verification ------------------------------------------------------------------------------------------------------------
+def correspondences(rng, M, outliers, W, H, shift=(5, -3), margin=8):
+    """M exact inliers of the translation `shift` (a homography) and `outliers` candidates whose frame-1 pixel is random.  Every
+    frame-0 record's descriptor is stored again at its partner in frame 1 (distance 0, so each one is a candidate); frame 1's
+    records are permuted.  Returns (corners (2, n), desc (2, n, 8), inlier flags of frame 0's records)."""
+    n = M + outliers
+    dx, dy = shift
+    c0 = distinct_corners(rng, n, W, H, margin)
+    p1 = np.stack([c0["x"].astype(np.int64) + dx, c0["y"].astype(np.int64) + dy], 1)
+    taken = set(map(tuple, p1[:M]))
+    for i in range(M, n):  # outliers: a random free pixel far from the translated one
+        while True:
+            x, y = int(rng.integers(0, W)), int(rng.integers(0, H))
+            if (x, y) not in taken and abs(x - p1[i, 0]) + abs(y - p1[i, 1]) > 40:
+                break
+        taken.add((x, y))
+        p1[i] = (x, y)
+    d0 = random_desc(rng, n)
+    perm = rng.permutation(n)
+    c1 = np.zeros(n, CORNER_DTYPE)
+    d1 = np.zeros((n, 8), np.uint32)
+    c1[perm] = corners(p1[:, 0], p1[:, 1], 0, rng=rng)
+    d1[perm] = d0
+    inl = np.zeros(n, bool)
+    inl[:M] = True
+    return np.stack([c0, c1]), np.stack([d0, d1]), inl
+
+
+def two_motions(rng, M, W, H):
+    """Two equal-size consistent subsets under different translations, interleaved over the whole frame (in two halves of the
+    frame a homography could bend from one shift to the other): correspondences 0 .. M - 1 move by (6, 2), M .. 2M - 1 by
+    (-2, 7); the shifts differ by 9.4 px, so no correspondence of one is within 3 px of the other's model.  Returns (corners (2, 2M),
+    desc (2, 2M, 8)); frame 1 holds the partners in frame 0's order."""
+    while True:
+        c0 = distinct_corners(rng, 2 * M, W, H, 16)
+        x1 = c0["x"].astype(np.int64) + np.where(np.arange(2 * M) < M, 6, -2)
+        y1 = c0["y"].astype(np.int64) + np.where(np.arange(2 * M) < M, 2, 7)
+        if len(set(zip(x1.tolist(), y1.tolist()))) == 2 * M:
+            break
+    d = random_desc(rng, 2 * M)
+    return np.stack([c0, corners(x1, y1, 0, rng=rng)]), np.stack([d, d])
+
+
+def jittered(rng, M, W, H, jitter=3):
+    """correspondences() without outliers whose frame-1 pixels are then moved by up to `jitter` pixels per axis: a noisy model
+    near the inlier threshold, where the refit can lose more than a sixteenth of the minimal model's inliers (GV-6's MINIMAL).
+    Returns (corners, desc), or None when the jitter made two frame-1 pixels coincide."""
+    c, d, _ = correspondences(rng, M, 0, W, H)
+    j = rng.integers(-jitter, jitter + 1, (M, 2))
+    c1 = c[1].copy()
+    c1["x"] = np.clip(c1["x"].astype(np.int64) + j[:, 0], 0, W - 1)
+    c1["y"] = np.clip(c1["y"].astype(np.int64) + j[:, 1], 0, H - 1)
+    if len(set(zip(c1["x"].tolist(), c1["y"].tolist()))) < M:
+        return None
+    return np.stack([c[0], c1]), d
+
+
+# found on the CPU (tests/test_constructed_ref.py::test_verification_constructions): jittered(default_rng(81), 40, 256, 256) at
+# 64 hypotheses, inlier_px 2 and seed 0 is reported MINIMAL by the restatement
+MINIMAL_SEED, MINIMAL_PARAMS = 81, dict(hypotheses=64, inlier_px=2.0)
+
+
+def collinear(rng, n, W, H):
+    """n correspondences on one row in both frames (a translation along it): every minimal sample is degenerate."""
+    x = 10 + 3 * np.arange(n)
+    assert x[-1] + 4 < W
+    c0 = corners(x, np.full(n, H // 2), 0, rng=rng)
+    c1 = corners(x + 4, np.full(n, H // 2), 0, rng=rng)
+    d = random_desc(rng, n)
+    return np.stack([c0, c1]), np.stack([d, d])
+
+
+# ---- guided matching ---------------------------------------------------------------------------------------------------------
+def window_edges(rng, r, octave_q=0, spacing=40, W=256, H=256):
+    """One query per direction (+x, -x, +y, -y, the corner +x -y) on a grid `spacing` apart, each with three targets of its own:
+    E on the window's edge (|x - px| = r or |y - py| = r exactly; 1 bit from the query), O one pixel beyond it (the query itself:
+    distance 0), C at the centre (10 bits).  With radius r: index E, distance 1, second 10; with r one ulp less: index C, distance 10,
+    second 0xFFFF.  octave_q = 0: integer r on integer coordinates; octave_q = 1: queries at octave 1 (level-0 centres 2 x + 0.5),
+    targets at octave 0, r = 2.5 (edge offsets 2.5 and 0.5 ... whole pixels + 1/2).  Returns (q_corners, q_desc, t_corners,
+    t_desc, [(query, E, C)])."""
+    dirs = [(1, 0), (-1, 0), (0, 1), (0, -1), (1, -1)]
+    qd = random_desc(rng, len(dirs))
+    qc, tc, td, cases = [], [], [], []
+    for q, (ux, uy) in enumerate(dirs):
+        gx, gy = spacing * (1 + q % 4), spacing * (1 + q // 4)
+        if octave_q == 0:
+            qc.append((gx, gy, 0))
+            cx, cy = gx, gy  # level-0 centre
+            e = (gx + ux * r, gy + uy * r)
+            o = (gx + ux * (r + 1) if ux else gx, gy + uy * (r + 1) if uy else gy)
+            tc += [e + (0,), o + (0,), (cx, cy, 0)]
+        else:  # query (a, b) at octave 1: centre (2a + 0.5, 2b + 0.5); targets at octave 0, integer pixels
+            a, b = gx // 2, gy // 2
+            qc.append((a, b, 1))
+            cx, cy = 2 * a + 0.5, 2 * b + 0.5
+            ex = cx + ux * r if ux else cx - 0.5
+            ey = cy + uy * r if uy else cy - 0.5
+            ox = ex + ux if ux else ex
+            oy = ey + uy if uy else ey
+            tc += [(int(ex), int(ey), 0), (int(ox), int(oy), 0), (int(cx - 0.5), int(cy + 0.5), 0)]
+        td += [flip(qd[q], 1, rng), qd[q].copy(), flip(qd[q], 10, rng)]
+        cases.append((q, 3 * q, 3 * q + 2))
+    qc, tc = np.array(qc), np.array(tc)
+    return (corners(qc[:, 0], qc[:, 1], qc[:, 2], rng=rng), qd, corners(tc[:, 0], tc[:, 1], tc[:, 2], rng=rng), np.stack(td), cases)
+
+
+def cell_ties(rng, W=256, H=256):
+    """Ties between targets in different grid cells, stored in the opposite order to their indices: for each query (radius 16)
+    two copies of the query with 2 bits flipped, the smaller index up and to the right of it in a later cell, the larger index
+    in an earlier cell (row above, or the same row to the left).  Expected: the smaller index, distance 2, second 2.  Returns
+    (q_corners, q_desc, t_corners, t_desc, expected MATCH_DTYPE)."""
+    offs = [((12, 12), (-12, -12)), ((12, 0), (-12, 0)), ((0, 12), (0, -12)), ((-12, 12), (12, -12))]
+    qd = random_desc(rng, len(offs))
+    qc, tc, td = [], [], []
+    exp = np.zeros(len(offs), MATCH_DTYPE)
+    for q, (lo, hi) in enumerate(offs):
+        gx, gy = 40 + 48 * q, 60 + 40 * (q % 2)
+        qc.append((gx, gy))
+        tc += [(gx + lo[0], gy + lo[1]), (gx + hi[0], gy + hi[1])]
+        c = flip(qd[q], 2, rng)
+        td += [c, c.copy()]
+        exp[q] = (2 * q, 2, 2)
+    qc, tc = np.array(qc), np.array(tc)
+    return corners(qc[:, 0], qc[:, 1], rng=rng), qd, corners(tc[:, 0], tc[:, 1], rng=rng), np.stack(td), exp
+
+
+def dense_cell(rng, x0, y0, extra, W=256, H=256):
+    """Every octave-0 pixel of the 8 x 8 cell at (x0, y0) (64 targets, random descriptors) followed by `extra` random targets
+    elsewhere; one query per target of the cell, each the target with 3 bits flipped.  Returns (q_corners, q_desc, t_corners,
+    t_desc): with a radius of 16 query k's best is target k (inside the cell) at distance 3, wherever the capacity cuts the rest."""
+    xs, ys = np.meshgrid(np.arange(x0, x0 + 8), np.arange(y0, y0 + 8))
+    cell = set(zip(xs.ravel().tolist(), ys.ravel().tolist()))
+    others = []
+    while len(others) < extra:
+        x, y = int(rng.integers(0, W)), int(rng.integers(0, H))
+        if (x, y) not in cell and (x, y) not in others:
+            others.append((x, y))
+    tx = np.r_[xs.ravel(), [p[0] for p in others]].astype(np.int64)
+    ty = np.r_[ys.ravel(), [p[1] for p in others]].astype(np.int64)
+    td = random_desc(rng, len(tx))
+    qd = flip(td[:64], 3, rng)
+    qc = corners(np.clip(xs.ravel() + 1, 0, W - 1), ys.ravel(), rng=rng)  # the queries one pixel to the right (distinct within frame 0)
+    return qc, qd, corners(tx, ty, rng=rng), td
