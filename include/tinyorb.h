@@ -400,6 +400,27 @@ int orb_verify_consecutive(OrbProgram *p, uint32_t n_frames, const OrbVerifyPara
  * for every other query. */
 int orb_verify_read(OrbProgram *p, uint32_t pair, OrbPairModel *model, uint8_t *inlier, size_t n);
 
+/* ---- epipolar verification of the matches (NOT in the reference; definition EP-1..EP-6 in DESIGN.md section 16) ----
+ * The homography above is the right model for a planar scene or a camera that only rotates; a camera that translates through
+ * a scene with depth needs the epipolar constraint x2^T F x1 = 0.  Same candidates (GV-1) and coordinates (GV-2) as
+ * orb_verify_consecutive; a RANSAC over minimal 8-point fundamental matrices (null vector by elimination with complete
+ * pivoting) picks the model with the most inliers (Sampson distance below inlier_px, tested without a division or a square
+ * root), a least-squares refit over its inliers replaces it unless it loses 1/16 of them or more, and every candidate gets an
+ * inlier byte.  OrbVerifyParams and its defaults as above; the record is an OrbPairModel whose h holds F (row-major, level-0
+ * keypoint coordinates, x2^T F x1 = 0 for x1 of frame f and x2 of frame f+1), divided by its first entry of largest magnitude
+ * (that entry is 1; all 0 for FEW / DEGENERATE).  F is NOT projected to rank 2 (that needs an SVD).  The status codes keep
+ * their meaning, except that ORB_VERIFY_FEW means fewer than 8 candidates.  Integer and binary32 arithmetic only, in a fixed
+ * order: a CPU restatement gives the same bits.
+ *
+ * State, arguments and streams as orb_verify_consecutive: ORB_ESTATE without an orb_match_consecutive of the current batch and
+ * output set; ORB_EINVAL for n_frames or a parameter out of range; asynchronous on `stream` (NULL: as orb_verify_consecutive),
+ * ordered behind the matcher's last call and the last epipolar call on another stream; orb_match_consecutive waits for an
+ * epipolar call on another stream.  Result buffers of its own (allocated by the first call): it never writes
+ * orb_verify_consecutive's results, and orb_match_guided and orb_track_consecutive keep reading those. */
+int orb_verify_epipolar(OrbProgram *p, uint32_t n_frames, const OrbVerifyParams *params, void *stream);
+/* As orb_verify_read, for the last orb_verify_epipolar call (ORB_ESTATE before the first). */
+int orb_verify_epipolar_read(OrbProgram *p, uint32_t pair, OrbPairModel *model, uint8_t *inlier, size_t n);
+
 /* ---- guided matching, "search by projection" (NOT in the reference; definition GM-1..GM-6 in DESIGN.md section 14) ----
  * For every consecutive pair (f, f+1) of the last batch: each stored keypoint i of frame f is sent through a row-major 3 x 3
  * model M (level-0 coordinates of orb_corner_level0_xy, binary32, no fused operations, in the order

@@ -1,0 +1,290 @@
+"""CPU restatement of the epipolar verifier, EP-1..EP-6 of DESIGN.md section 16, in NumPy (test infrastructure, not a test file).
+
+Every intermediate is np.float32 and every binary32 operation is the one the kernels in tinyslam_amd/csrc/orb_kernels_epipolar.h
+perform, in the same order: the records and inlier bytes of orb_verify_epipolar must equal what this module returns, bit for bit.
+Hypotheses are vectorised (one row per hypothesis); the complete-pivoting elimination of EP-3 runs on all of them at once, each
+with its own pivots, and the solve of EP-5 is verify_ref's GV-6 solver.
+"""
+import numpy as np
+
+import verify_ref as vr
+from tinyslam_amd.orb import ORB_MATCH_NONE as _NONE, VERIFY_MODEL_DTYPE
+
+F = np.float32
+VERIFY_OK, VERIFY_FEW, VERIFY_DEGENERATE, VERIFY_MINIMAL = vr.VERIFY_OK, vr.VERIFY_FEW, vr.VERIFY_DEGENERATE, vr.VERIFY_MINIMAL
+MAX_HYPOTHESES = vr.MAX_HYPOTHESES
+SEED_SALT = 0x45504931   # EP-2: the draw stream's seed is lowbias32(seed ^ SEED_SALT)
+DRAWS = 32               # EP-2: draws per hypothesis
+PIVOT_RATIO = F(2.0 ** -20)  # EP-3: degenerate when |last pivot| <= PIVOT_RATIO * |first pivot|
+_IU, _JU = np.triu_indices(8)
+
+defaults = vr.defaults
+
+
+def sample(seed, pair, M, hyps):
+    """EP-2: (hyps, 8) candidate indices in draw order and a validity flag per hypothesis."""
+    mix = vr.lowbias32(vr.lowbias32(np.uint32((seed ^ SEED_SALT) & 0xFFFFFFFF)) ^ np.uint32(pair))
+    h = np.arange(hyps, dtype=np.uint32)
+    J = np.zeros((hyps, 8), dtype=np.int64)
+    n = np.zeros(hyps, dtype=np.int64)
+    rows = np.arange(hyps)
+    for d in range(DRAWS):
+        r = vr.lowbias32(mix ^ ((h << np.uint32(5)) | np.uint32(d)))
+        j = ((r.astype(np.uint64) * np.uint64(M)) >> np.uint64(32)).astype(np.int64)
+        dup = ((np.arange(8)[None, :] < n[:, None]) & (J == j[:, None])).any(1)
+        take = (n < 8) & ~dup
+        J[rows[take], n[take]] = j[take]
+        n += take
+    return J, n == 8
+
+
+def design_rows(rec):
+    """EP-3 / EP-5: the row [u2 u, u2 v, u2, v2 u, v2 v, v2, u, v, 1] of every candidate, (M, 9)."""
+    u, v, u2, v2 = rec[..., 0], rec[..., 1], rec[..., 2], rec[..., 3]
+    return np.stack([u2 * u, u2 * v, u2, v2 * u, v2 * v, v2, u, v, np.ones_like(u)], -1).astype(F)
+
+
+def null_vectors(A):
+    """EP-3 on (n, 8, 9) matrices: complete pivoting (the first maximal |a| of the remaining block in row-major order; the row and
+    the column are swapped into place), elimination `f = a[q][r] / a[r][r]`, `a[q][c] = a[q][c] - f a[r][c]` for c > r, the one
+    unpivoted column set to 1, back substitution `s = s - a[r][q] x[q]` over ascending q starting from s = 0, `x[r] = s / a[r][r]`,
+    the columns put back, and the result divided by its first entry of largest magnitude.  Returns (F (n, 9), m (n,), ok (n,))."""
+    A = np.array(A, dtype=F, copy=True)
+    n = len(A)
+    rows = np.arange(n)
+    perm = np.tile(np.arange(9), (n, 1))
+    ok = np.ones(n, dtype=bool)
+    p0 = np.zeros(n, dtype=F)
+    with np.errstate(all="ignore"):
+        for r in range(8):
+            sub = np.abs(A[:, r:, r:]).reshape(n, -1)
+            k = np.argmax(sub, 1)
+            pi, pj = r + k // (9 - r), r + k % (9 - r)
+            pmax = sub[rows, k]
+            ok &= pmax != F(0)
+            if r == 0:
+                p0 = pmax
+            ri, rr = A[rows, pi].copy(), A[:, r].copy()  # row swap
+            A[:, r], A[rows, pi] = ri, rr
+            ci, cr = A[rows, :, pj].copy(), A[:, :, r].copy()  # column swap, every row
+            A[:, :, r], A[rows, :, pj] = ci, cr
+            qi, qr = perm[rows, pj].copy(), perm[:, r].copy()
+            perm[:, r], perm[rows, pj] = qi, qr
+            for q in range(r + 1, 8):
+                f = A[:, q, r] / A[:, r, r]
+                A[:, q, r + 1:] = A[:, q, r + 1:] - f[:, None] * A[:, r, r + 1:]
+        ok &= ~(np.abs(A[:, 7, 7]) <= PIVOT_RATIO * p0)
+        x = np.zeros((n, 9), dtype=F)
+        x[:, 8] = F(1)
+        for r in range(7, -1, -1):
+            s = np.zeros(n, dtype=F)
+            for q in range(r + 1, 9):
+                s = s - A[:, r, q] * x[:, q]
+            x[:, r] = s / A[:, r, r]
+        ok &= np.isfinite(x).all(1)
+        Fm = np.zeros((n, 9), dtype=F)
+        Fm[rows[:, None], perm] = x
+        m = np.argmax(np.abs(Fm), 1)
+        Fm = Fm / Fm[rows, m][:, None]
+    Fm[~ok] = F(0)
+    return Fm, m, ok
+
+
+def inliers(Fs, rec, t2):
+    """EP-4: (n_models, M) inlier flags of models Fs (n_models, 9), Sampson's test without a division."""
+    Fs = np.atleast_2d(Fs)
+    u, v, u2, v2 = (rec[None, :, i] for i in range(4))
+    f = [Fs[:, e:e + 1] for e in range(9)]
+    a0 = (f[0] * u + f[1] * v) + f[2]
+    a1 = (f[3] * u + f[4] * v) + f[5]
+    a2 = (f[6] * u + f[7] * v) + f[8]
+    d0 = (f[0] * u2 + f[3] * v2) + f[6]
+    d1 = (f[1] * u2 + f[4] * v2) + f[7]
+    r = (u2 * a0 + v2 * a1) + a2
+    return r * r < t2 * ((a0 * a0 + a1 * a1) + (d0 * d0 + d1 * d1))
+
+
+def normal_sums(rec, inl, m):
+    """EP-5: with entry m fixed at 1, the unknowns are the other 8 entries in ascending order: b = the row without entry m,
+    c = -(row[m]); the 36 upper-triangle sums b_i b_j and the 8 right sides b_i c, in GV-6's order and tree."""
+    A = design_rows(rec)
+    keep = [e for e in range(9) if e != m]
+    b = A[:, keep]
+    c = -A[:, m]
+    T = np.concatenate([b[:, _IU] * b[:, _JU], b * c[:, None]], 1)
+    T[~inl] = F(0)
+    P = np.zeros((256, 44), dtype=F)
+    for j0 in range(0, len(rec), 256):
+        blk = T[j0:j0 + 256]
+        P[:len(blk)] = P[:len(blk)] + blk
+    s = 128
+    while s >= 1:
+        P[:s] = P[:s] + P[s:2 * s]
+        s //= 2
+    return P[0]
+
+
+def refit(rec, inl, m):
+    """EP-5: the least-squares F with F[m] = 1 (None when GV-6's solver fails)."""
+    x = vr.solve(normal_sums(rec, inl, m))
+    if x is None:
+        return None
+    Fr = np.zeros(9, dtype=F)
+    Fr[[e for e in range(9) if e != m]] = x[:8]
+    Fr[m] = F(1)
+    return Fr
+
+
+def to_pixels(Fn, cx, cy, k):
+    """EP-6: T^T (F T), every entry (a0 b0 + a1 b1) + a2 b2, divided by its first entry of largest magnitude."""
+    T = np.array([[k, 0, -(cx * k), 0, k, -(cy * k), 0, 0, 1]], dtype=F)
+    Tt = np.array([[k, 0, 0, 0, k, 0, -(cx * k), -(cy * k), 1]], dtype=F)
+    P = vr.mat3(Tt, vr.mat3(Fn[None], T))[0]
+    m = int(np.argmax(np.abs(P)))
+    with np.errstate(all="ignore"):
+        return P / P[m]
+
+
+def verify_points(x0, y0, x1, y1, W, H, pair=0, **params):
+    """EP-1..EP-6 on candidate correspondences (level-0 pixel coordinates, float32, in candidate order).
+    Returns (record of VERIFY_MODEL_DTYPE, per-candidate inlier flags)."""
+    p = defaults(**params)
+    cx, cy, k = vr.normalise(W, H)
+    t = p["inlier_px"] * k
+    t2 = t * t
+    x0, y0, x1, y1 = (np.asarray(a, dtype=F) for a in (x0, y0, x1, y1))
+    rec = np.stack([(x0 - cx) * k, (y0 - cy) * k, (x1 - cx) * k, (y1 - cy) * k], 1).astype(F)
+    M = len(rec)
+    out = np.zeros((), dtype=VERIFY_MODEL_DTYPE)
+    out["candidates"] = M
+    out["hypothesis"] = _NONE
+    mask = np.zeros(M, dtype=bool)
+    if M < 8:
+        out["status"] = VERIFY_FEW
+        return out, mask
+    hyps = p["hypotheses"]
+    J, ok = sample(p["seed"], pair, M, hyps)
+    Fs, ms, okm = null_vectors(design_rows(rec[J]))
+    ok = ok & okm
+    Fs[~ok] = F(0)
+    if not ok.any():
+        out["status"] = VERIFY_DEGENERATE
+        return out, mask
+    counts = np.zeros(hyps, dtype=np.int64)
+    for h0 in range(0, hyps, 256):  # chunks of hypotheses bound the memory
+        counts[h0:h0 + 256] = inliers(Fs[h0:h0 + 256], rec, t2).sum(1)
+    keys = np.where(ok, ((counts + 1) << 12) | (MAX_HYPOTHESES - 1 - np.arange(hyps)), 0)
+    h = int(np.argmax(keys))
+    Fm, m = Fs[h], int(ms[h])
+    inl_m = inliers(Fm, rec, t2)[0]
+    n_min = int(inl_m.sum())
+    assert n_min == counts[h]
+    Fr = refit(rec, inl_m, m)
+    keep = False
+    if Fr is not None:
+        inl_r = inliers(Fr, rec, t2)[0]
+        keep = 16 * int(inl_r.sum()) >= 15 * n_min
+    Fk, mask = (Fr, inl_r) if keep else (Fm, inl_m)
+    out["h"] = to_pixels(Fk, cx, cy, k)
+    out["inliers"] = int(mask.sum())
+    out["hypothesis"] = h
+    out["status"] = VERIFY_OK if keep else VERIFY_MINIMAL
+    return out, mask
+
+
+def scene_motion(name):
+    """The constructed camera motions of DESIGN.md section 16 (R, t; x2 = R x1 + t in metres): 'sideways' (R = I: the normalised
+    F33 is 0), 'yaw' (1 degree of yaw, sideways), 'forward' (3 degrees of yaw, 1 of pitch, mostly forward)."""
+    def rot(ax, deg):
+        a = np.radians(deg)
+        c, s = np.cos(a), np.sin(a)
+        return np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]) if ax == "y" else np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+    return {"sideways": (np.eye(3), np.array([0.25, 0.0, 0.0])),
+            "yaw": (rot("y", 1.0), np.array([0.25, 0.0, 0.0])),
+            "forward": (rot("y", 3.0) @ rot("x", 1.0), np.array([0.05, 0.02, 0.3]))}[name]
+
+
+def sampson_px(Fm, x0, y0, x1, y1):
+    """Sampson distance in pixels of correspondences under a float64 pixel F."""
+    a = np.stack([x0, y0, np.ones_like(x0)]).astype(np.float64)
+    b = np.stack([x1, y1, np.ones_like(x1)]).astype(np.float64)
+    Fa, Fb = Fm @ a, Fm.T @ b
+    r = (b * Fa).sum(0)
+    return np.abs(r) / np.sqrt(Fa[0] ** 2 + Fa[1] ** 2 + Fb[0] ** 2 + Fb[1] ** 2)
+
+
+def scene(rng, motion, W=640, H=480, focal=500.0, n=600, outlier_share=0.3, zmin=2.0, zmax=12.0, count=None):
+    """A constructed two-view scene: n points at random pixels of frame 0 with inverse-uniform depths in [zmin, zmax], seen again
+    after `motion` (scene_motion) by a pinhole camera (focal length `focal`, principal point at the image centre); the points
+    that stay inside frame 1 become octave-0 records at the floor of their projections (pixel-edge coordinates, so the record's
+    level-0 coordinate is the projection rounded to the nearest pixel centre), one per pixel.  Then outlier_share of the
+    correspondences are outliers at random free pixels of both frames (outlier_share 1: outliers only, n of them).  With `count`,
+    a random subset of that many correspondences is kept.  Each frame-0 record's descriptor is stored again at its
+    partner (tests/constructed.py's builders: the brute-force best of every query is its partner, at distance 0); both frames are
+    stored in random orders.
+
+    Returns dict(corners (2 CORNER_DTYPE arrays), desc (2 (n, 8)), F: the true F in level-0 coordinates (float64, 3 x 3),
+    correct: per frame-0 record, a planted correspondence or an outlier within 2 px Sampson distance of F, planted: the same
+    without those outliers)."""
+    import constructed as C
+    R, t = scene_motion(motion) if isinstance(motion, str) else motion
+    Ke = np.array([[focal, 0, W / 2], [0, focal, H / 2], [0, 0, 1.0]])  # pixel-edge coordinates
+    Kc = np.array([[focal, 0, (W - 1) / 2], [0, focal, (H - 1) / 2], [0, 0, 1.0]])  # level-0 (pixel-centre) coordinates
+    x, y = rng.uniform(0, W, n), rng.uniform(0, H, n)
+    z = 1.0 / rng.uniform(1.0 / zmax, 1.0 / zmin, n)
+    P = np.linalg.inv(Ke) @ np.stack([x, y, np.ones(n)]) * z
+    Q = R @ P + t[:, None]
+    q = Ke @ Q
+    x2, y2 = q[0] / q[2], q[1] / q[2]
+    ok = (Q[2] > 0) & (x2 >= 0) & (x2 < W) & (y2 >= 0) & (y2 < H)
+    p0 = np.stack([np.floor(x[ok]), np.floor(y[ok])], 1).astype(np.int64)
+    p1 = np.stack([np.floor(x2[ok]), np.floor(y2[ok])], 1).astype(np.int64)
+    seen0, seen1, keep = set(), set(), []
+    for i in range(len(p0)):  # one record per pixel in each frame
+        a, b = tuple(p0[i]), tuple(p1[i])
+        if a not in seen0 and b not in seen1:
+            seen0.add(a)
+            seen1.add(b)
+            keep.append(i)
+    p0, p1 = p0[keep], p1[keep]
+    if outlier_share >= 1.0:
+        p0, p1, seen0, seen1 = p0[:0], p1[:0], set(), set()
+    n_in = len(p0)
+    n_out = n if outlier_share >= 1.0 else int(round(outlier_share / (1.0 - outlier_share) * n_in))
+    o0, o1 = [], []
+    for seen, out in ((seen0, o0), (seen1, o1)):
+        while len(out) < n_out:
+            c = (int(rng.integers(0, W)), int(rng.integers(0, H)))
+            if c not in seen:
+                seen.add(c)
+                out.append(c)
+    p0 = np.concatenate([p0, np.array(o0, np.int64).reshape(-1, 2)])
+    p1 = np.concatenate([p1, np.array(o1, np.int64).reshape(-1, 2)])
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    Ft = np.linalg.inv(Kc).T @ tx @ R @ np.linalg.inv(Kc)
+    planted = np.arange(len(p0)) < n_in
+    correct = planted | (sampson_px(Ft, p0[:, 0], p0[:, 1], p1[:, 0], p1[:, 1]) < 2.0)
+    if count is not None:
+        sub = np.sort(rng.choice(len(p0), size=count, replace=False))
+        p0, p1, planted, correct = p0[sub], p1[sub], planted[sub], correct[sub]
+    order0, order1 = rng.permutation(len(p0)), rng.permutation(len(p0))  # record r of frame 0 is correspondence order0[r]
+    d = C.random_desc(rng, len(p0))
+    c0 = C.corners(p0[order0, 0], p0[order0, 1], 0, rng=rng)
+    c1 = np.zeros(len(p0), c0.dtype)
+    d1 = np.zeros_like(d)
+    c1[order1] = C.corners(p1[:, 0], p1[:, 1], 0, rng=rng)
+    d1[order1] = d
+    return dict(corners=[c0, c1], desc=[d[order0], d1], F=Ft, correct=correct[order0], planted=planted[order0])
+
+
+def verify_pair(q_corners, t_corners, matches, W, H, pair, cap=None, **params):
+    """EP-1..EP-6 for one pair from the stored records of frames f and f + 1 and the matches of frame f's stored queries.
+    Returns (record, inlier bytes of the queries: cap of them when cap is given, else len(matches))."""
+    p = defaults(**params)
+    sel = vr.candidates(matches, len(t_corners), p["max_distance"], p["ratio"])
+    x0, y0 = vr.level0(q_corners[sel])
+    x1, y1 = vr.level0(t_corners[matches["index"][sel].astype(np.int64)])
+    rec, inl = verify_points(x0, y0, x1, y1, W, H, pair=pair, **params)
+    mask = np.zeros(len(matches) if cap is None else cap, dtype=np.uint8)
+    mask[sel[inl]] = 1
+    return rec, mask

@@ -26,6 +26,7 @@
 #include "orb_kernels_collate.h"
 #include "orb_kernels_match.h"
 #include "orb_kernels_verify.h"
+#include "orb_kernels_epipolar.h"
 #include "orb_kernels_guide.h"
 #include "orb_kernels_track.h"
 
@@ -131,6 +132,16 @@ struct OrbProgram {
     uint32_t verify_pairs = 0;            // pairs of the last verify call (0: none)
     uint64_t verify_seq = 0;              // batch_seq of the batch the last verify call read (its match's)
     uint32_t verify_set = 0;              // output set it read
+    // orb_verify_epipolar (orb_kernels_epipolar.h): buffers of its own, laid out like the verifier's, allocated by the first call
+    float4* d_erec = nullptr;             // [max_batch][max_features] candidates (u, v, u2, v2)
+    uint32_t* d_ecand = nullptr;          // [max_batch][max_features] candidate of each query
+    uint32_t* d_en = nullptr;             // [max_batch] candidates per pair
+    unsigned long long* d_ekeys = nullptr;  // [max_batch][kVerifyMaxHyp]
+    uint32_t* d_emodel = nullptr;         // [max_batch] OrbPairModel
+    uint8_t* d_emask = nullptr;           // [max_batch][max_features] inlier bytes
+    hipEvent_t epi_done = nullptr;
+    hipStream_t epi_stream = nullptr;
+    uint32_t epi_pairs = 0;               // pairs of the last epipolar call (0: none)
     // orb_match_guided (orb_kernels_guide.h): one set of buffers per program, allocated by the first call
     uint4* d_gsrec = nullptr;             // [max_batch][max_features] records in cell order (x0, y0, index, octave)
     uint4* d_gsdesc = nullptr;            // [max_batch][max_features][2] descriptors in cell order
@@ -1351,6 +1362,13 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_vmodel);
     (void)hipFree(p->d_vmask);
     if (p->verify_done) (void)hipEventDestroy(p->verify_done);
+    (void)hipFree(p->d_erec);
+    (void)hipFree(p->d_ecand);
+    (void)hipFree(p->d_en);
+    (void)hipFree(p->d_ekeys);
+    (void)hipFree(p->d_emodel);
+    (void)hipFree(p->d_emask);
+    if (p->epi_done) (void)hipEventDestroy(p->epi_done);
     (void)hipFree(p->d_gsrec);
     (void)hipFree(p->d_gsdesc);
     (void)hipFree(p->d_gcell);
@@ -2016,6 +2034,8 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     if (p->match_stream && p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
     // and behind a verification on another stream, which still reads the matches this call overwrites
     if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
+    // and behind an epipolar verification on another stream, which reads them too
+    if (p->epi_stream && p->epi_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->epi_done, 0));
     // and behind a track call on another stream, which may still read them
     if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
     if (mfma && !i8) {
@@ -2163,6 +2183,99 @@ int orb_verify_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* 
     static_assert(sizeof(OrbPairModel) == kVerifyModelWords * sizeof(uint32_t) && sizeof(OrbVerifyParams) == 32, "verify layouts");
     if (model) HIP_TRY(p, hipMemcpy(model, p->d_vmodel + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
     if (n) HIP_TRY(p, hipMemcpy(inlier, p->d_vmask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_verify_epipolar(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbVerifyParams v{};
+    if (params) v = *params;
+    if (v.reserved[0] || v.reserved[1] || v.reserved[2]) return fail(p, ORB_EINVAL, "verify_epipolar: reserved words must be 0");
+    if (v.hypotheses > kVerifyMaxHyp || v.max_distance > 256u)
+        return fail(p, ORB_EINVAL, "verify_epipolar: hypotheses must be 0..%u and max_distance 0..256", kVerifyMaxHyp);
+    if (!(std::isfinite(v.ratio) && v.ratio >= 0.0f) || !(std::isfinite(v.inlier_px) && v.inlier_px >= 0.0f))
+        return fail(p, ORB_EINVAL, "verify_epipolar: ratio and inlier_px must be finite and >= 0");
+    if (!p->match_seq || p->match_seq != p->batch_seq)
+        return fail(p, ORB_ESTATE, "verify_epipolar: no orb_match_consecutive since the last batch");
+    if (p->match_set != p->cur_set)
+        return fail(p, ORB_ESTATE, "verify_epipolar: the output set changed since orb_match_consecutive");
+    if (n_frames < 2u || n_frames > p->match_frames)
+        return fail(p, ORB_EINVAL, "verify_epipolar: need 2..%u frames (the matched ones)", p->match_frames);
+    if (!v.hypotheses) v.hypotheses = 512u;
+    if (!v.max_distance) v.max_distance = 64u;
+    if (v.ratio == 0.0f) v.ratio = 0.8f;
+    if (v.inlier_px == 0.0f) v.inlier_px = 3.0f;
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    if (!p->d_erec) {  // all six or none: a failure frees what was allocated, so the next call allocates again
+        void* buf[6] = {};
+        const size_t bytes[6] = {B * cap * sizeof(float4), B * cap * sizeof(uint32_t), B * sizeof(uint32_t),
+                                 B * kVerifyMaxHyp * sizeof(unsigned long long), B * sizeof(OrbPairModel), B * cap};
+        for (int i = 0; i < 6; i++) {
+            const hipError_t e = hipMalloc(&buf[i], bytes[i]);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
+                return fail(p, ORB_EHIP, "verify_epipolar: hipMalloc of %zu bytes failed: %s", bytes[i], hipGetErrorString(e));
+            }
+        }
+        p->d_ecand = static_cast<uint32_t*>(buf[1]);
+        p->d_en = static_cast<uint32_t*>(buf[2]);
+        p->d_ekeys = static_cast<unsigned long long*>(buf[3]);
+        p->d_emodel = static_cast<uint32_t*>(buf[4]);
+        p->d_emask = static_cast<uint8_t*>(buf[5]);
+        p->d_erec = static_cast<float4*>(buf[0]);
+    }
+    if (!p->epi_done) HIP_TRY(p, hipEventCreateWithFlags(&p->epi_done, hipEventDisableTiming));
+    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
+    // the matches come from the matcher's stream; the buffers are the last epipolar call's, which may run on another one
+    if (p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
+    if (p->epi_stream && p->epi_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->epi_done, 0));
+    // EP-1: GV-1 and GV-2, the verifier's gather into this call's own buffers
+    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    VerifyArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.matches = p->d_matches;
+    a.cap = (uint32_t)cap;
+    a.hyps = v.hypotheses;
+    a.max_distance = v.max_distance;
+    a.ratio = v.ratio;
+    a.cx = 0.5f * (float)(W - 1u);
+    a.cy = 0.5f * (float)(H - 1u);
+    a.k = 2.0f / (float)(W > H ? W : H);
+    const float t = v.inlier_px * a.k;
+    a.t2 = t * t;
+    a.seed_mix = lowbias32(v.seed ^ kEpiSeedSalt);  // EP-2: a draw stream of its own
+    a.rec = p->d_erec;
+    a.cand_of = p->d_ecand;
+    a.n_cand = p->d_en;
+    a.keys = p->d_ekeys;
+    a.model = p->d_emodel;
+    a.mask = p->d_emask;
+    const uint32_t pairs = n_frames - 1u;
+    hipLaunchKernelGGL(k_verify_gather, dim3(pairs), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_epi_score, dim3(pairs, (v.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_epi_refine, dim3(pairs), dim3(256), 0, s, a);
+    HIP_TRY(p, hipGetLastError());
+    HIP_TRY(p, hipEventRecord(p->epi_done, s));
+    p->epi_stream = s;
+    p->epi_pairs = pairs;
+    p->last_stream = s;
+    return ORB_OK;
+}
+
+int orb_verify_epipolar_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
+    if (!p) return ORB_EINVAL;
+    if (!p->epi_pairs) return fail(p, ORB_ESTATE, "verify_epipolar_read before verify_epipolar");
+    if (pair >= p->epi_pairs || (!inlier && n))
+        return fail(p, ORB_EINVAL, "verify_epipolar_read: pair %u of %u, or inlier is NULL", pair, p->epi_pairs);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(p->epi_done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    if (model) HIP_TRY(p, hipMemcpy(model, p->d_emodel + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(inlier, p->d_emask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

@@ -72,7 +72,7 @@ EXPORTS = [
     "orb_extract_batch_pinned", "orb_upload_sync", "orb_node_exchange_backend", "orb_node_rccl_pairs",
     "orb_write_input_image_pinned", "orb_node_set_results", "orb_node_shard_result",
     "orb_verify_consecutive", "orb_verify_read", "orb_match_guided", "orb_match_guided_read",
-    "orb_track_consecutive", "orb_track_read", "orb_track_frames",
+    "orb_track_consecutive", "orb_track_read", "orb_track_frames", "orb_verify_epipolar", "orb_verify_epipolar_read",
 ]
 
 
@@ -189,6 +189,8 @@ def load_library(path=None):
     L.orb_match_read.argtypes = [vp, u32, vp, ctypes.c_size_t]
     L.orb_verify_consecutive.argtypes = [vp, u32, ctypes.POINTER(_VerifyParams), vp]
     L.orb_verify_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_verify_epipolar.argtypes = [vp, u32, ctypes.POINTER(_VerifyParams), vp]
+    L.orb_verify_epipolar_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_match_guided.argtypes = [vp, u32, ctypes.POINTER(_GuideParams), vp, vp]
     L.orb_match_guided_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
@@ -537,6 +539,24 @@ class OrbProgram:
         rec = np.zeros((), dtype=VERIFY_MODEL_DTYPE)
         mask = np.zeros(min(n, self.config.max_features), dtype=np.uint8)
         self._check(self._lib.orb_verify_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
+        return rec, mask
+
+    def verify_epipolar(self, n_frames, hypotheses=0, max_distance=0, ratio=0.0, inlier_px=0.0, seed=0, stream=None, reserved=(0, 0, 0)):
+        """Epipolar verification of the last match_consecutive (not in the reference): the
+        candidates of verify_consecutive, a RANSAC fit of a fundamental matrix over `hypotheses` minimal eight-point samples (0: 512),
+        a least-squares refit over the winner's inliers (Sampson distance below inlier_px level-0 pixels, 0: 3.0) and an inlier byte
+        per query.  Results of its own: verify_consecutive's stay as they are.  Asynchronous on `stream` as verify_consecutive."""
+        prm = _VerifyParams(hypotheses, max_distance, float(np.float32(ratio)), float(np.float32(inlier_px)), seed & 0xFFFFFFFF,
+                            (ctypes.c_uint32 * 3)(*reserved))
+        self._check(self._lib.orb_verify_epipolar(self._handle(), n_frames, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def verify_epipolar_read(self, pair, n):
+        """(record of VERIFY_MODEL_DTYPE, uint8[min(n, max_features)] inlier bytes of pair's queries) of the last verify_epipolar --
+        synchronises.  The record's h is F (row-major, x2^T F x1 = 0 for level-0 keypoint coordinates x1 of frame `pair` and x2 of
+        frame `pair` + 1), divided by its first entry of largest magnitude."""
+        rec = np.zeros((), dtype=VERIFY_MODEL_DTYPE)
+        mask = np.zeros(min(n, self.config.max_features), dtype=np.uint8)
+        self._check(self._lib.orb_verify_epipolar_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
         return rec, mask
 
     def match_guided(self, n_frames, source=ORB_GUIDE_VERIFIED, radius_px=0.0, octave_window=0, scale_radius=False, models=None,
