@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <string>
 #include <algorithm>
 #include <vector>
@@ -58,6 +59,22 @@ struct ProfSpan {
 };
 
 }  // namespace
+
+// Device state of one verifier: the buffers of VerifyArgs (allocated by the verifier's first call, all or none), the event behind
+// its last call and what that call covered
+struct VerifierState {
+    float4* rec = nullptr;              // [max_batch][max_features] candidates (u, v, u2, v2)
+    uint32_t* cand = nullptr;           // [max_batch][max_features] candidate of each query
+    uint32_t* n = nullptr;              // [max_batch] candidates per pair
+    unsigned long long* keys = nullptr; // [max_batch][kVerifyMaxHyp]
+    uint32_t* model = nullptr;          // [max_batch] OrbPairModel
+    uint8_t* mask = nullptr;            // [max_batch][max_features] inlier bytes
+    hipEvent_t done = nullptr;
+    hipStream_t stream = nullptr;
+    uint32_t pairs = 0;                 // pairs of the last call (0: none)
+    uint64_t seq = 0;                   // orb_verify_consecutive only: batch_seq of the batch the last call read (its match's)
+    uint32_t set = 0;                   // orb_verify_consecutive only: output set it read
+};
 
 struct OrbProgram {
     OrbConfig cfg{};
@@ -120,28 +137,8 @@ struct OrbProgram {
     uint64_t match_seq = 0;    // batch_seq at the last orb_match_consecutive (0: none)
     uint32_t match_set = 0;    // output set it read
     uint32_t match_frames = 0; // frames it matched
-    // orb_verify_consecutive (orb_kernels_verify.h): one set of buffers per program, allocated by the first call
-    float4* d_vrec = nullptr;             // [max_batch][max_features] candidates (u, v, u2, v2)
-    uint32_t* d_vcand = nullptr;          // [max_batch][max_features] candidate of each query
-    uint32_t* d_vn = nullptr;             // [max_batch] candidates per pair
-    unsigned long long* d_vkeys = nullptr;  // [max_batch][kVerifyMaxHyp]
-    uint32_t* d_vmodel = nullptr;         // [max_batch] OrbPairModel
-    uint8_t* d_vmask = nullptr;           // [max_batch][max_features] inlier bytes
-    hipEvent_t verify_done = nullptr;
-    hipStream_t verify_stream = nullptr;
-    uint32_t verify_pairs = 0;            // pairs of the last verify call (0: none)
-    uint64_t verify_seq = 0;              // batch_seq of the batch the last verify call read (its match's)
-    uint32_t verify_set = 0;              // output set it read
-    // orb_verify_epipolar (orb_kernels_epipolar.h): buffers of its own, laid out like the verifier's, allocated by the first call
-    float4* d_erec = nullptr;             // [max_batch][max_features] candidates (u, v, u2, v2)
-    uint32_t* d_ecand = nullptr;          // [max_batch][max_features] candidate of each query
-    uint32_t* d_en = nullptr;             // [max_batch] candidates per pair
-    unsigned long long* d_ekeys = nullptr;  // [max_batch][kVerifyMaxHyp]
-    uint32_t* d_emodel = nullptr;         // [max_batch] OrbPairModel
-    uint8_t* d_emask = nullptr;           // [max_batch][max_features] inlier bytes
-    hipEvent_t epi_done = nullptr;
-    hipStream_t epi_stream = nullptr;
-    uint32_t epi_pairs = 0;               // pairs of the last epipolar call (0: none)
+    // orb_verify_consecutive (orb_kernels_verify.h) and orb_verify_epipolar (orb_kernels_epipolar.h): a set of buffers each
+    VerifierState verify, epi;
     // orb_match_guided (orb_kernels_guide.h): one set of buffers per program, allocated by the first call
     uint4* d_gsrec = nullptr;             // [max_batch][max_features] records in cell order (x0, y0, index, octave)
     uint4* d_gsdesc = nullptr;            // [max_batch][max_features][2] descriptors in cell order
@@ -264,6 +261,27 @@ int fail(OrbProgram* p, int code, const char* fmt, ...) {
         hipError_t e_ = (expr);                                                                           \
         if (e_ != hipSuccess) return fail((p), ORB_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// Makes stream s wait behind a stage (its event `done`) that last ran on another stream; nothing to do when the stage has not run
+// (stage_stream is null) or ran on s itself.
+hipError_t wait_behind(hipStream_t s, hipStream_t stage_stream, hipEvent_t done) {
+    return stage_stream && stage_stream != s ? hipStreamWaitEvent(s, done, 0) : hipSuccess;
+}
+
+// hipMalloc of n buffers, all or none: a failure frees the earlier ones and leaves every buf[i] null, so the caller records nothing and
+// its next call allocates again.
+int alloc_all_or_none(OrbProgram* p, const char* who, int n, const size_t* bytes, void** buf) {
+    for (int i = 0; i < n; i++) {
+        const hipError_t e = hipMalloc(&buf[i], bytes[i]);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
+            for (int j = 0; j < n; j++) buf[j] = nullptr;
+            return fail(p, ORB_EHIP, "%s: hipMalloc of %zu bytes failed: %s", who, bytes[i], hipGetErrorString(e));
+        }
+    }
+    return ORB_OK;
+}
 
 // Bracket one kernel launch with events when profiling is on.
 struct LaunchScope {
@@ -1355,20 +1373,10 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_stamps);
     (void)hipFree(p->d_desc8);
     if (p->match_done) (void)hipEventDestroy(p->match_done);
-    (void)hipFree(p->d_vrec);
-    (void)hipFree(p->d_vcand);
-    (void)hipFree(p->d_vn);
-    (void)hipFree(p->d_vkeys);
-    (void)hipFree(p->d_vmodel);
-    (void)hipFree(p->d_vmask);
-    if (p->verify_done) (void)hipEventDestroy(p->verify_done);
-    (void)hipFree(p->d_erec);
-    (void)hipFree(p->d_ecand);
-    (void)hipFree(p->d_en);
-    (void)hipFree(p->d_ekeys);
-    (void)hipFree(p->d_emodel);
-    (void)hipFree(p->d_emask);
-    if (p->epi_done) (void)hipEventDestroy(p->epi_done);
+    for (VerifierState* st : {&p->verify, &p->epi}) {
+        for (void* b : {(void*)st->rec, (void*)st->cand, (void*)st->n, (void*)st->keys, (void*)st->model, (void*)st->mask}) (void)hipFree(b);
+        if (st->done) (void)hipEventDestroy(st->done);
+    }
     (void)hipFree(p->d_gsrec);
     (void)hipFree(p->d_gsdesc);
     (void)hipFree(p->d_gcell);
@@ -2031,13 +2039,13 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     const dim3 grid_e((unsigned)((cap + 31u) / 32u), n_frames), grid_m(n_frames - 1u, (unsigned)((cap + kMatchQueriesPerWg - 1u) / kMatchQueriesPerWg));
     // one result buffer and one expanded-descriptor buffer per program: a match on another stream than the last one waits for it
     if (!p->match_done) HIP_TRY(p, hipEventCreateWithFlags(&p->match_done, hipEventDisableTiming));
-    if (p->match_stream && p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
+    HIP_TRY(p, wait_behind(s, p->match_stream, p->match_done));
     // and behind a verification on another stream, which still reads the matches this call overwrites
-    if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
+    HIP_TRY(p, wait_behind(s, p->verify.stream, p->verify.done));
     // and behind an epipolar verification on another stream, which reads them too
-    if (p->epi_stream && p->epi_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->epi_done, 0));
+    HIP_TRY(p, wait_behind(s, p->epi.stream, p->epi.done));
     // and behind a track call on another stream, which may still read them
-    if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
+    HIP_TRY(p, wait_behind(s, p->track_stream, p->track_done));
     if (mfma && !i8) {
         {
             LaunchScope ls(p, s, KID_DESC_EXPAND);
@@ -2078,55 +2086,66 @@ int orb_match_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
     return ORB_OK;
 }
 
-int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
-    if (!p) return ORB_EINVAL;
+}  // extern "C"
+
+namespace {
+
+// What orb_verify_consecutive and orb_verify_epipolar differ in
+struct VerifierKind {
+    const char* name;             // in messages
+    const char* read_name;
+    uint32_t seed_salt;           // the draw stream's seed is lowbias32(seed ^ seed_salt)
+    void (*score)(VerifyArgs);
+    void (*refine)(VerifyArgs);
+    bool has_readers;             // guided and track calls read its results (on any stream): a call waits behind them
+    bool profiled;                // launches under LaunchScope (KID_VERIFY_*)
+};
+const VerifierKind kHomography = {"verify_consecutive", "verify_read", 0u, k_verify_score, k_verify_refine, true, true};
+const VerifierKind kEpipolar = {"verify_epipolar", "verify_epipolar_read", kEpiSeedSalt, k_epi_score, k_epi_refine, false, false};
+
+int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
     OrbVerifyParams v{};
     if (params) v = *params;
-    if (v.reserved[0] || v.reserved[1] || v.reserved[2]) return fail(p, ORB_EINVAL, "verify_consecutive: reserved words must be 0");
+    if (v.reserved[0] || v.reserved[1] || v.reserved[2]) return fail(p, ORB_EINVAL, "%s: reserved words must be 0", kind.name);
     if (v.hypotheses > kVerifyMaxHyp || v.max_distance > 256u)
-        return fail(p, ORB_EINVAL, "verify_consecutive: hypotheses must be 0..%u and max_distance 0..256", kVerifyMaxHyp);
+        return fail(p, ORB_EINVAL, "%s: hypotheses must be 0..%u and max_distance 0..256", kind.name, kVerifyMaxHyp);
     if (!(std::isfinite(v.ratio) && v.ratio >= 0.0f) || !(std::isfinite(v.inlier_px) && v.inlier_px >= 0.0f))
-        return fail(p, ORB_EINVAL, "verify_consecutive: ratio and inlier_px must be finite and >= 0");
+        return fail(p, ORB_EINVAL, "%s: ratio and inlier_px must be finite and >= 0", kind.name);
     if (!p->match_seq || p->match_seq != p->batch_seq)
-        return fail(p, ORB_ESTATE, "verify_consecutive: no orb_match_consecutive since the last batch");
+        return fail(p, ORB_ESTATE, "%s: no orb_match_consecutive since the last batch", kind.name);
     if (p->match_set != p->cur_set)
-        return fail(p, ORB_ESTATE, "verify_consecutive: the output set changed since orb_match_consecutive");
+        return fail(p, ORB_ESTATE, "%s: the output set changed since orb_match_consecutive", kind.name);
     if (n_frames < 2u || n_frames > p->match_frames)
-        return fail(p, ORB_EINVAL, "verify_consecutive: need 2..%u frames (the matched ones)", p->match_frames);
+        return fail(p, ORB_EINVAL, "%s: need 2..%u frames (the matched ones)", kind.name, p->match_frames);
     if (!v.hypotheses) v.hypotheses = 512u;
     if (!v.max_distance) v.max_distance = 64u;
     if (v.ratio == 0.0f) v.ratio = 0.8f;
     if (v.inlier_px == 0.0f) v.inlier_px = 3.0f;
     HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features, B = p->max_batch;
-    if (!p->d_vrec) {  // all six or none: a failure frees what was allocated, so the next call allocates again
+    if (!st.rec) {  // all six or none: a failure frees what was allocated, so the next call allocates again
         void* buf[6] = {};
         const size_t bytes[6] = {B * cap * sizeof(float4), B * cap * sizeof(uint32_t), B * sizeof(uint32_t),
                                  B * kVerifyMaxHyp * sizeof(unsigned long long), B * sizeof(OrbPairModel), B * cap};
-        for (int i = 0; i < 6; i++) {
-            const hipError_t e = hipMalloc(&buf[i], bytes[i]);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
-                return fail(p, ORB_EHIP, "verify_consecutive: hipMalloc of %zu bytes failed: %s", bytes[i], hipGetErrorString(e));
-            }
-        }
-        p->d_vcand = static_cast<uint32_t*>(buf[1]);
-        p->d_vn = static_cast<uint32_t*>(buf[2]);
-        p->d_vkeys = static_cast<unsigned long long*>(buf[3]);
-        p->d_vmodel = static_cast<uint32_t*>(buf[4]);
-        p->d_vmask = static_cast<uint8_t*>(buf[5]);
-        p->d_vrec = static_cast<float4*>(buf[0]);
+        if (int rc = alloc_all_or_none(p, kind.name, 6, bytes, buf)) return rc;
+        st.rec = static_cast<float4*>(buf[0]);
+        st.cand = static_cast<uint32_t*>(buf[1]);
+        st.n = static_cast<uint32_t*>(buf[2]);
+        st.keys = static_cast<unsigned long long*>(buf[3]);
+        st.model = static_cast<uint32_t*>(buf[4]);
+        st.mask = static_cast<uint8_t*>(buf[5]);
     }
-    if (!p->verify_done) HIP_TRY(p, hipEventCreateWithFlags(&p->verify_done, hipEventDisableTiming));
+    if (!st.done) HIP_TRY(p, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
     hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
-    // the matches come from the matcher's stream; the buffers are the last verification's, which may run on another one
-    if (p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
-    if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
-    // and behind a guided match on another stream, which may still read the models this call overwrites
-    if (p->guide_stream && p->guide_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->guide_done, 0));
-    // and behind a track call on another stream, which may still read the inlier bytes
-    if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
+    // the matches come from the matcher's stream; the buffers are this verifier's last call's, which may run on another one
+    HIP_TRY(p, wait_behind(s, p->match_stream, p->match_done));
+    HIP_TRY(p, wait_behind(s, st.stream, st.done));
+    if (kind.has_readers) {
+        // and behind a guided match on another stream, which may still read the models this call overwrites
+        HIP_TRY(p, wait_behind(s, p->guide_stream, p->guide_done));
+        // and behind a track call on another stream, which may still read the inlier bytes
+        HIP_TRY(p, wait_behind(s, p->track_stream, p->track_done));
+    }
     // GV-2: coordinates centred on the level-0 image and scaled by 2 / max(W, H)
     const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
     VerifyArgs a{};
@@ -2142,141 +2161,66 @@ int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyPara
     a.k = 2.0f / (float)(W > H ? W : H);
     const float t = v.inlier_px * a.k;
     a.t2 = t * t;
-    a.seed_mix = lowbias32(v.seed);
-    a.rec = p->d_vrec;
-    a.cand_of = p->d_vcand;
-    a.n_cand = p->d_vn;
-    a.keys = p->d_vkeys;
-    a.model = p->d_vmodel;
-    a.mask = p->d_vmask;
+    a.seed_mix = lowbias32(v.seed ^ kind.seed_salt);
+    a.rec = st.rec;
+    a.cand_of = st.cand;
+    a.n_cand = st.n;
+    a.keys = st.keys;
+    a.model = st.model;
+    a.mask = st.mask;
     const uint32_t pairs = n_frames - 1u;
-    {
-        LaunchScope ls(p, s, KID_VERIFY_GATHER);
-        hipLaunchKernelGGL(k_verify_gather, dim3(pairs), dim3(256), 0, s, a);
-    }
-    {
-        LaunchScope ls(p, s, KID_VERIFY_SCORE);
-        hipLaunchKernelGGL(k_verify_score, dim3(pairs, (v.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a);
-    }
-    {
-        LaunchScope ls(p, s, KID_VERIFY_REFINE);
-        hipLaunchKernelGGL(k_verify_refine, dim3(pairs), dim3(256), 0, s, a);
-    }
+    const auto launch = [&](int kid, void (*kernel)(VerifyArgs), dim3 grid) {
+        std::optional<LaunchScope> ls;
+        if (kind.profiled) ls.emplace(p, s, kid);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a);
+    };
+    launch(KID_VERIFY_GATHER, k_verify_gather, dim3(pairs));  // EP-1: GV-1 and GV-2 serve both verifiers
+    launch(KID_VERIFY_SCORE, kind.score, dim3(pairs, (v.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg));
+    launch(KID_VERIFY_REFINE, kind.refine, dim3(pairs));
     HIP_TRY(p, hipGetLastError());
-    HIP_TRY(p, hipEventRecord(p->verify_done, s));
-    p->verify_stream = s;
-    p->verify_pairs = pairs;
-    p->verify_seq = p->match_seq;
-    p->verify_set = p->match_set;
+    HIP_TRY(p, hipEventRecord(st.done, s));
+    st.stream = s;
+    st.pairs = pairs;
     p->last_stream = s;
+    return ORB_OK;
+}
+
+int read_verifier(OrbProgram* p, const VerifierKind& kind, const VerifierState& st, uint32_t pair, OrbPairModel* model, uint8_t* inlier,
+                     size_t n) {
+    if (!st.pairs) return fail(p, ORB_ESTATE, "%s before %s", kind.read_name, kind.name);
+    if (pair >= st.pairs || (!inlier && n)) return fail(p, ORB_EINVAL, "%s: pair %u of %u, or inlier is NULL", kind.read_name, pair, st.pairs);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(st.done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    static_assert(sizeof(OrbPairModel) == kVerifyModelWords * sizeof(uint32_t) && sizeof(OrbVerifyParams) == 32, "verify layouts");
+    if (model) HIP_TRY(p, hipMemcpy(model, st.model + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(inlier, st.mask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    if (int rc = run_verifier(p, kHomography, p->verify, n_frames, params, stream)) return rc;
+    p->verify.seq = p->match_seq;  // what guided and track calls check before they read the models and the inlier bytes
+    p->verify.set = p->match_set;
     return ORB_OK;
 }
 
 int orb_verify_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
-    if (!p) return ORB_EINVAL;
-    if (!p->verify_pairs) return fail(p, ORB_ESTATE, "verify_read before verify_consecutive");
-    if (pair >= p->verify_pairs || (!inlier && n)) return fail(p, ORB_EINVAL, "verify_read: pair %u of %u, or inlier is NULL", pair, p->verify_pairs);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(p->verify_done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    static_assert(sizeof(OrbPairModel) == kVerifyModelWords * sizeof(uint32_t) && sizeof(OrbVerifyParams) == 32, "verify layouts");
-    if (model) HIP_TRY(p, hipMemcpy(model, p->d_vmodel + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(p, hipMemcpy(inlier, p->d_vmask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_verifier(p, kHomography, p->verify, pair, model, inlier, n) : ORB_EINVAL;
 }
 
 int orb_verify_epipolar(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
-    if (!p) return ORB_EINVAL;
-    OrbVerifyParams v{};
-    if (params) v = *params;
-    if (v.reserved[0] || v.reserved[1] || v.reserved[2]) return fail(p, ORB_EINVAL, "verify_epipolar: reserved words must be 0");
-    if (v.hypotheses > kVerifyMaxHyp || v.max_distance > 256u)
-        return fail(p, ORB_EINVAL, "verify_epipolar: hypotheses must be 0..%u and max_distance 0..256", kVerifyMaxHyp);
-    if (!(std::isfinite(v.ratio) && v.ratio >= 0.0f) || !(std::isfinite(v.inlier_px) && v.inlier_px >= 0.0f))
-        return fail(p, ORB_EINVAL, "verify_epipolar: ratio and inlier_px must be finite and >= 0");
-    if (!p->match_seq || p->match_seq != p->batch_seq)
-        return fail(p, ORB_ESTATE, "verify_epipolar: no orb_match_consecutive since the last batch");
-    if (p->match_set != p->cur_set)
-        return fail(p, ORB_ESTATE, "verify_epipolar: the output set changed since orb_match_consecutive");
-    if (n_frames < 2u || n_frames > p->match_frames)
-        return fail(p, ORB_EINVAL, "verify_epipolar: need 2..%u frames (the matched ones)", p->match_frames);
-    if (!v.hypotheses) v.hypotheses = 512u;
-    if (!v.max_distance) v.max_distance = 64u;
-    if (v.ratio == 0.0f) v.ratio = 0.8f;
-    if (v.inlier_px == 0.0f) v.inlier_px = 3.0f;
-    HIP_TRY(p, hipSetDevice(p->device));
-    const size_t cap = p->cfg.max_features, B = p->max_batch;
-    if (!p->d_erec) {  // all six or none: a failure frees what was allocated, so the next call allocates again
-        void* buf[6] = {};
-        const size_t bytes[6] = {B * cap * sizeof(float4), B * cap * sizeof(uint32_t), B * sizeof(uint32_t),
-                                 B * kVerifyMaxHyp * sizeof(unsigned long long), B * sizeof(OrbPairModel), B * cap};
-        for (int i = 0; i < 6; i++) {
-            const hipError_t e = hipMalloc(&buf[i], bytes[i]);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
-                return fail(p, ORB_EHIP, "verify_epipolar: hipMalloc of %zu bytes failed: %s", bytes[i], hipGetErrorString(e));
-            }
-        }
-        p->d_ecand = static_cast<uint32_t*>(buf[1]);
-        p->d_en = static_cast<uint32_t*>(buf[2]);
-        p->d_ekeys = static_cast<unsigned long long*>(buf[3]);
-        p->d_emodel = static_cast<uint32_t*>(buf[4]);
-        p->d_emask = static_cast<uint8_t*>(buf[5]);
-        p->d_erec = static_cast<float4*>(buf[0]);
-    }
-    if (!p->epi_done) HIP_TRY(p, hipEventCreateWithFlags(&p->epi_done, hipEventDisableTiming));
-    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
-    // the matches come from the matcher's stream; the buffers are the last epipolar call's, which may run on another one
-    if (p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
-    if (p->epi_stream && p->epi_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->epi_done, 0));
-    // EP-1: GV-1 and GV-2, the verifier's gather into this call's own buffers
-    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
-    VerifyArgs a{};
-    a.counts = p->d_counts;
-    a.corners = p->d_corners;
-    a.matches = p->d_matches;
-    a.cap = (uint32_t)cap;
-    a.hyps = v.hypotheses;
-    a.max_distance = v.max_distance;
-    a.ratio = v.ratio;
-    a.cx = 0.5f * (float)(W - 1u);
-    a.cy = 0.5f * (float)(H - 1u);
-    a.k = 2.0f / (float)(W > H ? W : H);
-    const float t = v.inlier_px * a.k;
-    a.t2 = t * t;
-    a.seed_mix = lowbias32(v.seed ^ kEpiSeedSalt);  // EP-2: a draw stream of its own
-    a.rec = p->d_erec;
-    a.cand_of = p->d_ecand;
-    a.n_cand = p->d_en;
-    a.keys = p->d_ekeys;
-    a.model = p->d_emodel;
-    a.mask = p->d_emask;
-    const uint32_t pairs = n_frames - 1u;
-    hipLaunchKernelGGL(k_verify_gather, dim3(pairs), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_epi_score, dim3(pairs, (v.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_epi_refine, dim3(pairs), dim3(256), 0, s, a);
-    HIP_TRY(p, hipGetLastError());
-    HIP_TRY(p, hipEventRecord(p->epi_done, s));
-    p->epi_stream = s;
-    p->epi_pairs = pairs;
-    p->last_stream = s;
-    return ORB_OK;
+    return p ? run_verifier(p, kEpipolar, p->epi, n_frames, params, stream) : ORB_EINVAL;
 }
 
 int orb_verify_epipolar_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
-    if (!p) return ORB_EINVAL;
-    if (!p->epi_pairs) return fail(p, ORB_ESTATE, "verify_epipolar_read before verify_epipolar");
-    if (pair >= p->epi_pairs || (!inlier && n))
-        return fail(p, ORB_EINVAL, "verify_epipolar_read: pair %u of %u, or inlier is NULL", pair, p->epi_pairs);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(p->epi_done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    if (model) HIP_TRY(p, hipMemcpy(model, p->d_emodel + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(p, hipMemcpy(inlier, p->d_emask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_verifier(p, kEpipolar, p->epi, pair, model, inlier, n) : ORB_EINVAL;
 }
 
 int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {
@@ -2293,10 +2237,10 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     if ((g.source == ORB_GUIDE_HOST) != (models_host != nullptr))
         return fail(p, ORB_EINVAL, "match_guided: models_host is required with ORB_GUIDE_HOST and only then");
     if (g.source == ORB_GUIDE_VERIFIED) {
-        if (!p->verify_pairs || p->verify_seq != p->batch_seq || p->verify_set != p->cur_set)
+        if (!p->verify.pairs || p->verify.seq != p->batch_seq || p->verify.set != p->cur_set)
             return fail(p, ORB_ESTATE, "match_guided: no orb_verify_consecutive of the current batch and output set");
-        if (n_frames - 1u > p->verify_pairs)
-            return fail(p, ORB_EINVAL, "match_guided: %u pairs, the last verification has %u", n_frames - 1u, p->verify_pairs);
+        if (n_frames - 1u > p->verify.pairs)
+            return fail(p, ORB_EINVAL, "match_guided: %u pairs, the last verification has %u", n_frames - 1u, p->verify.pairs);
     }
     if (g.radius_px == 0.0f) g.radius_px = 16.0f;
     HIP_TRY(p, hipSetDevice(p->device));
@@ -2315,14 +2259,7 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
         void* buf[5] = {};
         const size_t bytes[5] = {B * cap * sizeof(uint4), B * cap * 2u * sizeof(uint4), B * (kGuideMaxCells + 1u) * sizeof(uint32_t),
                                  B * cap * sizeof(MatchRecord), B * 9u * sizeof(float)};
-        for (int i = 0; i < 5; i++) {
-            const hipError_t e = hipMalloc(&buf[i], bytes[i]);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
-                return fail(p, ORB_EHIP, "match_guided: hipMalloc of %zu bytes failed: %s", bytes[i], hipGetErrorString(e));
-            }
-        }
+        if (int rc = alloc_all_or_none(p, "match_guided", 5, bytes, buf)) return rc;
         void* h = nullptr;
         const hipError_t e = hipHostMalloc(&h, B * 9u * sizeof(float), hipHostMallocDefault);
         if (e != hipSuccess) {
@@ -2340,10 +2277,10 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     if (!p->guide_done) HIP_TRY(p, hipEventCreateWithFlags(&p->guide_done, hipEventDisableTiming));
     hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
     // the models come from the last verification; the buffers are the last guided call's, which may run on another stream
-    if (p->verify_stream && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
-    if (p->guide_stream && p->guide_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->guide_done, 0));
+    HIP_TRY(p, wait_behind(s, p->verify.stream, p->verify.done));
+    HIP_TRY(p, wait_behind(s, p->guide_stream, p->guide_done));
     // and behind a track call on another stream, which may still read the records this call overwrites
-    if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
+    HIP_TRY(p, wait_behind(s, p->track_stream, p->track_done));
     const uint32_t pairs = n_frames - 1u;
     if (g.source == ORB_GUIDE_HOST) {  // through the pinned staging buffer, once the previous call's copy out of it is done
         if (p->guide_stream) HIP_TRY(p, hipEventSynchronize(p->guide_done));
@@ -2363,7 +2300,7 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     a.cell_start = p->d_gcell;
     a.pairs = pairs;
     a.source = g.source;
-    a.vmodel = p->d_vmodel;
+    a.vmodel = p->verify.model;
     a.hmodel = p->d_gmodel;
     a.radius = g.radius_px;
     a.octave_window = g.octave_window;
@@ -2411,10 +2348,10 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
     if (p->cfg.max_features > (1u << 23)) return fail(p, ORB_EINVAL, "track_consecutive: max_features must be <= 2^23");
     uint32_t pairs_avail = 0;
     if (t.source == ORB_TRACK_VERIFIED) {
-        if (!p->verify_pairs || p->verify_seq != p->batch_seq || p->verify_set != p->cur_set || p->match_seq != p->verify_seq ||
-            p->match_set != p->verify_set)
+        if (!p->verify.pairs || p->verify.seq != p->batch_seq || p->verify.set != p->cur_set || p->match_seq != p->verify.seq ||
+            p->match_set != p->verify.set)
             return fail(p, ORB_ESTATE, "track_consecutive: no orb_verify_consecutive of the current batch, output set and matches");
-        pairs_avail = p->verify_pairs;
+        pairs_avail = p->verify.pairs;
     } else if (t.source == ORB_TRACK_GUIDED) {
         if (!p->guide_pairs || p->guide_seq != p->batch_seq || p->guide_set != p->cur_set)
             return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_guided of the current batch and output set");
@@ -2441,14 +2378,7 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
         const size_t bytes[8] = {B * cap * sizeof(uint32_t), B * cap * sizeof(uint32_t), B * cap * sizeof(uint32_t),
                                  2u * B * cap * sizeof(uint4), B * sizeof(uint32_t), B * B * sizeof(uint32_t),
                                  B * sizeof(OrbTrackFrame), B * cap * sizeof(OrbTrack)};
-        for (int i = 0; i < 8; i++) {
-            const hipError_t e = hipMalloc(&buf[i], bytes[i]);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
-                return fail(p, ORB_EHIP, "track_consecutive: hipMalloc of %zu bytes failed: %s", bytes[i], hipGetErrorString(e));
-            }
-        }
+        if (int rc = alloc_all_or_none(p, "track_consecutive", 8, bytes, buf)) return rc;
         p->d_tkeys = static_cast<uint32_t*>(buf[0]);
         p->d_tprev = static_cast<uint32_t*>(buf[1]);
         p->d_tnext = static_cast<uint32_t*>(buf[2]);
@@ -2461,10 +2391,10 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
     if (!p->track_done) HIP_TRY(p, hipEventCreateWithFlags(&p->track_done, hipEventDisableTiming));
     hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
     // the links come from the source's last call; the buffers are the last track call's, which may run on another stream
-    if (t.source != ORB_TRACK_GUIDED && p->match_stream && p->match_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->match_done, 0));
-    if (t.source == ORB_TRACK_VERIFIED && p->verify_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->verify_done, 0));
-    if (t.source == ORB_TRACK_GUIDED && p->guide_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->guide_done, 0));
-    if (p->track_stream && p->track_stream != s) HIP_TRY(p, hipStreamWaitEvent(s, p->track_done, 0));
+    if (t.source != ORB_TRACK_GUIDED) HIP_TRY(p, wait_behind(s, p->match_stream, p->match_done));
+    if (t.source == ORB_TRACK_VERIFIED) HIP_TRY(p, wait_behind(s, p->verify.stream, p->verify.done));
+    if (t.source == ORB_TRACK_GUIDED) HIP_TRY(p, wait_behind(s, p->guide_stream, p->guide_done));
+    HIP_TRY(p, wait_behind(s, p->track_stream, p->track_done));
     TrackArgs a{};
     a.counts = p->d_counts;
     a.cap = (uint32_t)cap;
@@ -2472,7 +2402,7 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
     a.stride = (uint32_t)B;
     a.source = t.source;
     a.rec = t.source == ORB_TRACK_GUIDED ? p->d_gmatch : p->d_matches;
-    a.mask = p->d_vmask;
+    a.mask = p->verify.mask;
     a.max_distance = t.max_distance;
     a.ratio = t.ratio;
     a.gkeys = p->d_tkeys;

@@ -1,17 +1,21 @@
 // orb_kernels_epipolar.h -- epipolar verification of the Hamming matches between consecutive frames (not in the reference; the
 // definition is the build's own, EP-1..EP-6 in DESIGN.md section 16): a RANSAC fit of a fundamental matrix per pair from minimal
 // eight-point samples, a least-squares refit over the winner's inliers, an inlier byte per query.  The candidates and their
-// normalised coordinates are the homography verifier's (GV-1, GV-2: k_verify_gather, run into this call's own buffers), and the
-// sums, the tree and the solve of the refit are GV-6's.  Every binary32 operation below is written out in the order the definition
-// gives (-ffp-contract=off, correctly rounded division), so the CPU restatement (tests/epipolar_ref.py) reproduces every bit.
-// F is not projected to rank 2 (that needs an SVD).
+// normalised coordinates are the homography verifier's (GV-1, GV-2: k_verify_gather, run into this call's own buffers).  Every
+// binary32 operation below is written out in the order the definition gives (-ffp-contract=off, correctly rounded division), so the
+// CPU restatement (tests/epipolar_ref.py) reproduces every bit.  F is not projected to rank 2 (that needs an SVD).
+//
+// This header holds what is the fundamental matrix's own: the sampling, the minimal solver, the inlier test, an inlier's share of the
+// refit's sums, and EpipolarModel, which hands them to the skeleton both verifiers share (orb_kernels_verify.h: verify_score_tail,
+// verify_refine_body).
 //
 //   k_epi_score    grid (pair, 64-hypothesis block), 256 threads: wave 0 builds hypothesis 64 * block + l on lane l (EP-2, EP-3),
 //                  eliminating with complete pivoting in a padded LDS row of its own (pivots found at run time would send a
-//                  private array to scratch); the 64 models go through LDS to all four waves, the candidates pass through LDS in
-//                  tiles of 256 and are read as broadcasts, each wave takes every fourth one; one packed key per hypothesis (EP-4)
-//   k_epi_refine   one workgroup per pair: the best key, the winner rebuilt on one lane, the 44 normal-equation sums in GV-6's
-//                  order and tree, GV-6's solve on one lane, the refit scored, the record (EP-6) and the inlier bytes written
+//                  private array to scratch); the 64 models go through LDS to all four waves; then the shared tail: the candidates
+//                  in tiles of 256 read as broadcasts, each wave every fourth one, one packed key per hypothesis (EP-4)
+//   k_epi_refine   the shared refine body: the best key, the winner rebuilt on one lane (EpipolarModel::winner), the 44
+//                  normal-equation sums in GV-6's order and tree, GV-6's solve on one lane, the refit scored, the record (EP-6)
+//                  and the inlier bytes written
 #pragma once
 #include "orb_kernels_verify.h"
 
@@ -152,52 +156,6 @@ __device__ __forceinline__ bool epi_inlier(const float F[9], const float4& c, fl
     return r * r < t2 * ((a0 * a0 + a1 * a1) + (d0 * d0 + d1 * d1));
 }
 
-// grid (pairs, ceil(hyps / 64)), block 256; VerifyArgs.seed_mix = lowbias32(seed ^ kEpiSeedSalt)
-__global__ __launch_bounds__(256) void k_epi_score(VerifyArgs a) {
-    __shared__ float mat[kVerifyHypPerWg * kEpiRow];
-    __shared__ float models[9][kVerifyHypPerWg];
-    __shared__ float4 tile[256];
-    __shared__ uint32_t cnt[4][kVerifyHypPerWg];
-    __shared__ uint32_t valid_mask[2];
-    const uint32_t pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t M = a.n_cand[pair];
-    if (M < 8u) return;  // uniform: k_epi_refine reads no key of such a pair
-    const float4* const rec = a.rec + (size_t)pair * a.cap;
-    const uint32_t h = blockIdx.y * kVerifyHypPerWg + lane;
-    if (wave == 0u) {
-        float F[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        uint32_t mi = 0;
-        bool valid = h < a.hyps && epi_model(rec, M, lowbias32(a.seed_mix ^ pair), h, mat + lane * kEpiRow, F, mi);
-#pragma unroll
-        for (int e = 0; e < 9; e++) models[e][lane] = valid ? F[e] : 0.0f;  // an invalid hypothesis: F = 0, never an inlier
-        const unsigned long long vb = __ballot(valid);
-        if (lane == 0u) {
-            valid_mask[0] = (uint32_t)vb;
-            valid_mask[1] = (uint32_t)(vb >> 32);
-        }
-    }
-    __syncthreads();
-    float F[9];
-#pragma unroll
-    for (int e = 0; e < 9; e++) F[e] = models[e][lane];
-    uint32_t n = 0;
-    for (uint32_t c0 = 0; c0 < M; c0 += 256u) {
-        const uint32_t tn = min(M - c0, 256u);
-        if (tid < tn) tile[tid] = rec[c0 + tid];
-        __syncthreads();
-#pragma unroll 4
-        for (uint32_t q = wave; q < tn; q += 4u) n += epi_inlier(F, tile[q], a.t2) ? 1u : 0u;
-        __syncthreads();
-    }
-    cnt[wave][lane] = n;
-    __syncthreads();
-    if (wave == 0u && h < a.hyps) {
-        const bool valid = (valid_mask[lane >> 5] >> (lane & 31u)) & 1u;
-        const uint32_t total = (cnt[0][lane] + cnt[1][lane]) + (cnt[2][lane] + cnt[3][lane]);
-        a.keys[(size_t)pair * kVerifyMaxHyp + h] = valid ? (((unsigned long long)(total + 1u) << 12) | (kVerifyMaxHyp - 1u - h)) : 0ull;
-    }
-}
-
 // EP-5: an inlier's row without entry m (b, 8 entries) and c = -(row[m]), added to the 44 sums in GV-6's order
 __device__ __forceinline__ void epi_accumulate(float acc[kVerifySums], const float4& c, uint32_t m) {
     float r[9];
@@ -218,152 +176,87 @@ __device__ __forceinline__ void epi_accumulate(float acc[kVerifySums], const flo
     for (int i = 0; i < 8; i++) acc[36 + i] = acc[36 + i] + b[i] * cm;
 }
 
-// grid (pairs), block 256
-__global__ __launch_bounds__(256) void k_epi_refine(VerifyArgs a) {
-    __shared__ float part[kVerifySums][256];  // [sum][thread]: conflict-free columns
-    __shared__ float aug[8][9];
-    __shared__ float sol[9];
-    __shared__ float rowbuf[kEpiRow];
-    __shared__ float fmin[9];
-    __shared__ uint32_t s_m;
-    __shared__ unsigned long long wkey[4];
-    __shared__ uint32_t s_ok, s_count;
+// What the shared skeleton (orb_kernels_verify.h) needs to know about the fundamental matrix.  `m` is the entry of largest
+// magnitude of the minimal model, which the refit fixes to 1 (EP-5).
+struct EpipolarModel {
+    static constexpr uint32_t kSample = 8u;  // candidates of a minimal sample; a pair with fewer is ORB_VERIFY_FEW
+    // the winner rebuilt on one lane through an LDS row (valid: it scored a key), then handed to every thread
+    static __device__ __forceinline__ void winner(const float4* __restrict__ rec, uint32_t M, uint32_t pair_mix, uint32_t h, bool has_min,
+                                                  float Fm[9], uint32_t& m) {
+        __shared__ float rowbuf[kEpiRow];
+        __shared__ float fmin[9];
+        __shared__ uint32_t s_m;
+        if (has_min && threadIdx.x == 0u) {
+            float F[9];
+            uint32_t mi = 0;
+            (void)epi_model(rec, M, pair_mix, h, rowbuf, F, mi);
+#pragma unroll
+            for (int e = 0; e < 9; e++) fmin[e] = F[e];
+            s_m = mi;
+        }
+        __syncthreads();
+        if (has_min) {
+#pragma unroll
+            for (int e = 0; e < 9; e++) Fm[e] = fmin[e];
+            m = s_m;
+        }
+    }
+    static __device__ __forceinline__ bool inlier(const float F[9], const float4& c, float t2) { return epi_inlier(F, c, t2); }
+    static __device__ __forceinline__ void accumulate(float acc[kVerifySums], const float4& c, uint32_t m) { epi_accumulate(acc, c, m); }
+    // EP-5: F[m] = 1, the other entries the solution in ascending order
+    static __device__ __forceinline__ void from_solution(const float* sol, uint32_t m, float F[9]) {
+#pragma unroll
+        for (int e = 0; e < 9; e++) F[e] = (uint32_t)e == m ? 1.0f : sol[(uint32_t)e > m ? e - 1 : e];
+    }
+    // EP-6: the model in level-0 pixels, T^T * (F * T) divided by its first entry of largest magnitude
+    static __device__ __forceinline__ void to_pixels(const float Fk[9], const VerifyArgs& a, float P[9]) {
+        const float T[9] = {a.k, 0.0f, -(a.cx * a.k), 0.0f, a.k, -(a.cy * a.k), 0.0f, 0.0f, 1.0f};
+        const float Tt[9] = {a.k, 0.0f, 0.0f, 0.0f, a.k, 0.0f, -(a.cx * a.k), -(a.cy * a.k), 1.0f};
+        float G[9], Q[9];
+        verify_mat3(Fk, T, G);
+        verify_mat3(Tt, G, Q);
+        float bestq = fabsf(Q[0]), qm = Q[0];
+#pragma unroll
+        for (int e = 1; e < 9; e++) {
+            const bool gt = fabsf(Q[e]) > bestq;
+            bestq = gt ? fabsf(Q[e]) : bestq;
+            qm = gt ? Q[e] : qm;
+        }
+#pragma unroll
+        for (int e = 0; e < 9; e++) P[e] = Q[e] / qm;
+    }
+};
+
+// grid (pairs, ceil(hyps / 64)), block 256; VerifyArgs.seed_mix = lowbias32(seed ^ kEpiSeedSalt)
+__global__ __launch_bounds__(256) void k_epi_score(VerifyArgs a) {
+    __shared__ float mat[kVerifyHypPerWg * kEpiRow];
+    __shared__ float models[9][kVerifyHypPerWg];
+    __shared__ uint32_t valid_mask[2];
     const uint32_t pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t M = a.n_cand[pair];
+    if (M < EpipolarModel::kSample) return;  // uniform: k_epi_refine reads no key of such a pair
     const float4* const rec = a.rec + (size_t)pair * a.cap;
-    unsigned long long best = 0ull;
-    if (M >= 8u)
-        for (uint32_t h = tid; h < a.hyps; h += 256u) best = max(best, a.keys[(size_t)pair * kVerifyMaxHyp + h]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) best = max(best, (unsigned long long)__shfl_xor(best, off));
-    if (lane == 0u) wkey[wave] = best;
-    if (tid == 0u) s_count = 0u;
-    __syncthreads();
-    best = max(max(wkey[0], wkey[1]), max(wkey[2], wkey[3]));
-    const bool has_min = best != 0ull;  // uniform
-    const uint32_t h = has_min ? (kVerifyMaxHyp - 1u) - (uint32_t)(best & (kVerifyMaxHyp - 1u)) : kVerifyNone;
-    const uint32_t n_min = has_min ? (uint32_t)(best >> 12) - 1u : 0u;
-    if (has_min && tid == 0u) {  // the winner rebuilt (valid: it scored a key)
-        float F[9];
+    const uint32_t h = blockIdx.y * kVerifyHypPerWg + lane;
+    if (wave == 0u) {
+        float F[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         uint32_t mi = 0;
-        (void)epi_model(rec, M, lowbias32(a.seed_mix ^ pair), h, rowbuf, F, mi);
+        bool valid = h < a.hyps && epi_model(rec, M, lowbias32(a.seed_mix ^ pair), h, mat + lane * kEpiRow, F, mi);
 #pragma unroll
-        for (int e = 0; e < 9; e++) fmin[e] = F[e];
-        s_m = mi;
+        for (int e = 0; e < 9; e++) models[e][lane] = valid ? F[e] : 0.0f;  // an invalid hypothesis: F = 0, never an inlier
+        const unsigned long long vb = __ballot(valid);
+        if (lane == 0u) {
+            valid_mask[0] = (uint32_t)vb;
+            valid_mask[1] = (uint32_t)(vb >> 32);
+        }
     }
     __syncthreads();
-    float Fm[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    uint32_t m = 0;
-    if (has_min) {
+    float F[9];
 #pragma unroll
-        for (int e = 0; e < 9; e++) Fm[e] = fmin[e];
-        m = s_m;
-    }
-    bool keep = false;
-    float Fr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (has_min) {
-        float acc[kVerifySums];
-#pragma unroll
-        for (uint32_t e = 0; e < kVerifySums; e++) acc[e] = 0.0f;
-        for (uint32_t j = tid; j < M; j += 256u) {  // candidate j into partial sum j mod 256, ascending j
-            const float4 c = rec[j];
-            if (epi_inlier(Fm, c, a.t2)) epi_accumulate(acc, c, m);
-        }
-#pragma unroll
-        for (uint32_t e = 0; e < kVerifySums; e++) part[e][tid] = acc[e];
-        __syncthreads();
-        for (uint32_t s = 128u; s >= 1u; s >>= 1) {  // pairwise tree, strides 128 .. 1
-            if (tid < s)
-                for (uint32_t e = 0; e < kVerifySums; e++) part[e][tid] = part[e][tid] + part[e][tid + s];
-            __syncthreads();
-        }
-        if (tid == 0u) {  // GV-6's solver: elimination with partial pivoting (first maximal |pivot|), then back substitution
-            for (int i = 0, e = 0; i < 8; i++)
-                for (int j = i; j < 8; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
-            for (int i = 0; i < 8; i++) aug[i][8] = part[36 + i][0];
-            uint32_t ok = 1u;
-            for (int c = 0; c < 8 && ok; c++) {
-                int piv = c;
-                float pmax = fabsf(aug[c][c]);
-                for (int r = c + 1; r < 8; r++)
-                    if (fabsf(aug[r][c]) > pmax) pmax = fabsf(aug[r][c]), piv = r;
-                if (pmax == 0.0f) {
-                    ok = 0u;
-                    break;
-                }
-                if (piv != c)
-                    for (int q = 0; q < 9; q++) {
-                        const float tmp = aug[c][q];
-                        aug[c][q] = aug[piv][q];
-                        aug[piv][q] = tmp;
-                    }
-                for (int r = c + 1; r < 8; r++) {
-                    const float f = aug[r][c] / aug[c][c];
-                    for (int q = c + 1; q < 9; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
-                }
-            }
-            if (ok)
-                for (int r = 7; r >= 0; r--) {
-                    float s = aug[r][8];
-                    for (int q = r + 1; q < 8; q++) s = s - aug[r][q] * sol[q];
-                    sol[r] = s / aug[r][r];
-                    if (!isfinite(sol[r])) ok = 0u;
-                }
-            s_ok = ok;
-        }
-        __syncthreads();
-        if (s_ok) {  // F[m] = 1, the other entries the solution in ascending order
-#pragma unroll
-            for (int e = 0; e < 9; e++) Fr[e] = (uint32_t)e == m ? 1.0f : sol[(uint32_t)e > m ? e - 1 : e];
-            uint32_t n = 0;
-            for (uint32_t j = tid; j < M; j += 256u) n += epi_inlier(Fr, rec[j], a.t2) ? 1u : 0u;
-            atomicAdd(&s_count, n);
-        }
-        __syncthreads();
-        keep = s_ok && 16u * s_count >= 15u * n_min;  // GV-6's rule: the refit may lose a few marginal inliers, not 1/16 of them
-    }
-    float Fk[9];
-#pragma unroll
-    for (int e = 0; e < 9; e++) Fk[e] = keep ? Fr[e] : Fm[e];
-    // inlier bytes of every query slot of the pair: one write each
-    const uint32_t nq = min(a.counts[pair], a.cap);
-    const uint32_t* const cand_of = a.cand_of + (size_t)pair * a.cap;
-    uint8_t* const mask = a.mask + (size_t)pair * a.cap;
-    for (uint32_t i = tid; i < a.cap; i += 256u) {
-        uint8_t b = 0;
-        if (has_min && i < nq) {
-            const uint32_t j = cand_of[i];
-            if (j != kVerifyNone) b = epi_inlier(Fk, rec[j], a.t2) ? 1 : 0;
-        }
-        mask[i] = b;
-    }
-    if (tid == 0u) {  // EP-6: the record, the model in level-0 pixels T^T * (F * T) divided by its first entry of largest magnitude
-        uint32_t* const out = a.model + (size_t)pair * kVerifyModelWords;
-        float P[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (has_min) {
-            const float T[9] = {a.k, 0.0f, -(a.cx * a.k), 0.0f, a.k, -(a.cy * a.k), 0.0f, 0.0f, 1.0f};
-            const float Tt[9] = {a.k, 0.0f, 0.0f, 0.0f, a.k, 0.0f, -(a.cx * a.k), -(a.cy * a.k), 1.0f};
-            float G[9], Q[9];
-            verify_mat3(Fk, T, G);
-            verify_mat3(Tt, G, Q);
-            float bestq = fabsf(Q[0]), qm = Q[0];
-#pragma unroll
-            for (int e = 1; e < 9; e++) {
-                const bool gt = fabsf(Q[e]) > bestq;
-                bestq = gt ? fabsf(Q[e]) : bestq;
-                qm = gt ? Q[e] : qm;
-            }
-#pragma unroll
-            for (int e = 0; e < 9; e++) P[e] = Q[e] / qm;
-        }
-#pragma unroll
-        for (int e = 0; e < 9; e++) out[e] = __float_as_uint(P[e]);
-        out[9] = M;
-        out[10] = has_min ? (keep ? s_count : n_min) : 0u;
-        out[11] = h;
-        out[12] = M < 8u ? (uint32_t)ORB_VERIFY_FEW : !has_min ? (uint32_t)ORB_VERIFY_DEGENERATE : keep ? (uint32_t)ORB_VERIFY_OK : (uint32_t)ORB_VERIFY_MINIMAL;
-        out[13] = out[14] = out[15] = 0u;
-    }
+    for (int e = 0; e < 9; e++) F[e] = models[e][lane];
+    verify_score_tail<EpipolarModel>(a, rec, M, h, F, (valid_mask[lane >> 5] >> (lane & 31u)) & 1u);
 }
+
+// grid (pairs), block 256
+__global__ __launch_bounds__(256) void k_epi_refine(VerifyArgs a) { verify_refine_body<EpipolarModel>(a); }
 
 }  // namespace orb

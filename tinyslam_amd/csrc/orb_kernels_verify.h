@@ -13,6 +13,12 @@
 //   k_verify_refine   one workgroup per pair: the best key, the winner rebuilt, the normal equations summed in the order of
 //                     GV-6 (thread t owns partial sum t), solved on one lane, the refit scored, the record (GV-7) and the
 //                     inlier bytes written
+//
+// The score kernel behind its prologue and the whole refine kernel are a skeleton shared with the epipolar verifier
+// (orb_kernels_epipolar.h): verify_score_tail, verify_solve and verify_refine_body below, templates over a model type --
+// HomographyModel here, EpipolarModel there -- that supplies the minimal sample size, the winner's rebuild, the inlier test, an
+// inlier's share of the 44 sums, the solution as nine entries and the model in pixels.  A change to the solver or to the keep
+// rule is made once.
 #pragma once
 #include "../../include/tinyorb.h"
 #include "orb_kernels_staged.h"
@@ -181,37 +187,6 @@ __global__ __launch_bounds__(256) void k_verify_gather(VerifyArgs a) {
     if (tid == 0u) a.n_cand[pair] = base;
 }
 
-// grid (pairs, ceil(hyps / 64)), block 256
-__global__ __launch_bounds__(256) void k_verify_score(VerifyArgs a) {
-    __shared__ float4 tile[256];
-    __shared__ uint32_t cnt[4][kVerifyHypPerWg];
-    const uint32_t pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t M = a.n_cand[pair];
-    if (M < 4u) return;  // uniform: k_verify_refine reads no key of such a pair
-    const float4* const rec = a.rec + (size_t)pair * a.cap;
-    const uint32_t h = blockIdx.y * kVerifyHypPerWg + lane;
-    float H[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // an invalid hypothesis: w' = 0, never an inlier
-    const bool valid = h < a.hyps && verify_model(rec, M, lowbias32(a.seed_mix ^ pair), h, H);
-    if (!valid)
-#pragma unroll
-        for (int e = 0; e < 9; e++) H[e] = 0.f;
-    uint32_t n = 0;
-    for (uint32_t c0 = 0; c0 < M; c0 += 256u) {
-        const uint32_t tn = min(M - c0, 256u);
-        if (tid < tn) tile[tid] = rec[c0 + tid];
-        __syncthreads();
-#pragma unroll 4
-        for (uint32_t q = wave; q < tn; q += 4u) n += verify_inlier(H, tile[q], a.t2) ? 1u : 0u;
-        __syncthreads();
-    }
-    cnt[wave][lane] = n;
-    __syncthreads();
-    if (wave == 0u && h < a.hyps) {
-        const uint32_t total = (cnt[0][lane] + cnt[1][lane]) + (cnt[2][lane] + cnt[3][lane]);
-        a.keys[(size_t)pair * kVerifyMaxHyp + h] = valid ? (((unsigned long long)(total + 1u) << 12) | (kVerifyMaxHyp - 1u - h)) : 0ull;
-    }
-}
-
 // GV-6: the two rows of an inlier's equations (h33 = 1) added to the 44 sums
 __device__ inline void verify_accumulate(float acc[kVerifySums], const float4& c) {
     const float r1[8] = {c.x, c.y, 1.0f, 0.0f, 0.0f, 0.0f, -(c.x * c.z), -(c.y * c.z)};
@@ -225,18 +200,116 @@ __device__ inline void verify_accumulate(float acc[kVerifySums], const float4& c
     for (int i = 0; i < 8; i++) acc[36 + i] = acc[36 + i] + (r1[i] * c.z + r2[i] * c.w);
 }
 
-// grid (pairs), block 256
-__global__ __launch_bounds__(256) void k_verify_refine(VerifyArgs a) {
+// What the skeleton below needs to know about the homography (the fundamental matrix's counterpart is EpipolarModel in
+// orb_kernels_epipolar.h).  `m` is the entry a model fixes to 1 in its refit: always h33 here, so it is not used.
+struct HomographyModel {
+    static constexpr uint32_t kSample = 4u;  // candidates of a minimal sample; a pair with fewer is ORB_VERIFY_FEW
+    // the winner rebuilt in registers, on every thread (valid: it scored a key)
+    static __device__ __forceinline__ void winner(const float4* __restrict__ rec, uint32_t M, uint32_t pair_mix, uint32_t h, bool has_min,
+                                                  float Hm[9], uint32_t&) {
+        if (has_min) (void)verify_model(rec, M, pair_mix, h, Hm);
+    }
+    static __device__ __forceinline__ bool inlier(const float H[9], const float4& c, float t2) { return verify_inlier(H, c, t2); }
+    static __device__ __forceinline__ void accumulate(float acc[kVerifySums], const float4& c, uint32_t) { verify_accumulate(acc, c); }
+    // GV-6: the solution with h33 = 1 appended
+    static __device__ __forceinline__ void from_solution(const float* sol, uint32_t, float H[9]) {
+#pragma unroll
+        for (int e = 0; e < 8; e++) H[e] = sol[e];
+        H[8] = 1.0f;
+    }
+    // GV-7: the model in level-0 pixels, T^-1 * H * T divided by its [2][2] entry
+    static __device__ __forceinline__ void to_pixels(const float Hk[9], const VerifyArgs& a, float P[9]) {
+        const float T[9] = {a.k, 0.0f, -(a.cx * a.k), 0.0f, a.k, -(a.cy * a.k), 0.0f, 0.0f, 1.0f};
+        const float ik = 1.0f / a.k;
+        const float Ti[9] = {ik, 0.0f, a.cx, 0.0f, ik, a.cy, 0.0f, 0.0f, 1.0f};
+        float G[9], Q[9];
+        verify_mat3(Hk, T, G);
+        verify_mat3(Ti, G, Q);
+#pragma unroll
+        for (int e = 0; e < 9; e++) P[e] = Q[e] / Q[8];
+    }
+};
+
+// The skeleton both verifiers share: everything of their score and refine kernels that does not depend on the model.
+
+// The score kernels behind their prologue (lane l of every wave holds model F of hypothesis h = 64 * block + l, all zeros when it
+// is not `valid`): the candidates through LDS in tiles of 256, read as broadcasts, wave w takes every fourth one from w; the four
+// waves' counts added as (0 + 1) + (2 + 3); the packed key (GV-5), written by wave 0
+template <class Model>
+__device__ __forceinline__ void verify_score_tail(const VerifyArgs& a, const float4* __restrict__ rec, uint32_t M, uint32_t h, const float F[9],
+                                                  bool valid) {
+    __shared__ float4 tile[256];
+    __shared__ uint32_t cnt[4][kVerifyHypPerWg];
+    const uint32_t pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t n = 0;
+    for (uint32_t c0 = 0; c0 < M; c0 += 256u) {
+        const uint32_t tn = min(M - c0, 256u);
+        if (tid < tn) tile[tid] = rec[c0 + tid];
+        __syncthreads();
+#pragma unroll 4
+        for (uint32_t q = wave; q < tn; q += 4u) n += Model::inlier(F, tile[q], a.t2) ? 1u : 0u;
+        __syncthreads();
+    }
+    cnt[wave][lane] = n;
+    __syncthreads();
+    if (wave == 0u && h < a.hyps) {
+        const uint32_t total = (cnt[0][lane] + cnt[1][lane]) + (cnt[2][lane] + cnt[3][lane]);
+        a.keys[(size_t)pair * kVerifyMaxHyp + h] = valid ? (((unsigned long long)(total + 1u) << 12) | (kVerifyMaxHyp - 1u - h)) : 0ull;
+    }
+}
+
+// GV-6's solver on one lane: the 44 sums (column 0 of `part`) spread into the symmetric 8 x 9 system `aug`, Gaussian elimination
+// with partial pivoting (first maximal |pivot|), back substitution into sol[0..7].  0: a zero pivot or a non-finite entry.
+__device__ __forceinline__ uint32_t verify_solve(const float (*part)[256], float (*aug)[9], float* sol) {
+    for (int i = 0, e = 0; i < 8; i++)
+        for (int j = i; j < 8; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
+    for (int i = 0; i < 8; i++) aug[i][8] = part[36 + i][0];
+    uint32_t ok = 1u;
+    for (int c = 0; c < 8 && ok; c++) {
+        int piv = c;
+        float pmax = fabsf(aug[c][c]);
+        for (int r = c + 1; r < 8; r++)
+            if (fabsf(aug[r][c]) > pmax) pmax = fabsf(aug[r][c]), piv = r;
+        if (pmax == 0.0f) {
+            ok = 0u;
+            break;
+        }
+        if (piv != c)
+            for (int q = 0; q < 9; q++) {
+                const float tmp = aug[c][q];
+                aug[c][q] = aug[piv][q];
+                aug[piv][q] = tmp;
+            }
+        for (int r = c + 1; r < 8; r++) {
+            const float f = aug[r][c] / aug[c][c];
+            for (int q = c + 1; q < 9; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
+        }
+    }
+    if (ok)
+        for (int r = 7; r >= 0; r--) {
+            float s = aug[r][8];
+            for (int q = r + 1; q < 8; q++) s = s - aug[r][q] * sol[q];
+            sol[r] = s / aug[r][r];
+            if (!isfinite(sol[r])) ok = 0u;
+        }
+    return ok;
+}
+
+// The refine kernels, one workgroup of 256 per pair: the best key and what it encodes, the winner rebuilt (Model::winner), the
+// normal equations of its inliers summed in GV-6's order (thread t owns partial sum t, then the tree), solved on one lane, the
+// refit scored and kept or not, the inlier bytes and the record (GV-7 / EP-6)
+template <class Model>
+__device__ __forceinline__ void verify_refine_body(const VerifyArgs& a) {
     __shared__ float part[kVerifySums][256];  // [sum][thread]: conflict-free columns
     __shared__ float aug[8][9];
-    __shared__ float sol[9];
+    __shared__ float sol[8];
     __shared__ unsigned long long wkey[4];
     __shared__ uint32_t s_ok, s_count;
     const uint32_t pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t M = a.n_cand[pair];
     const float4* const rec = a.rec + (size_t)pair * a.cap;
     unsigned long long best = 0ull;
-    if (M >= 4u)
+    if (M >= Model::kSample)
         for (uint32_t h = tid; h < a.hyps; h += 256u) best = max(best, a.keys[(size_t)pair * kVerifyMaxHyp + h]);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) best = max(best, (unsigned long long)__shfl_xor(best, off));
@@ -247,17 +320,18 @@ __global__ __launch_bounds__(256) void k_verify_refine(VerifyArgs a) {
     const bool has_min = best != 0ull;  // uniform
     const uint32_t h = has_min ? (kVerifyMaxHyp - 1u) - (uint32_t)(best & (kVerifyMaxHyp - 1u)) : kVerifyNone;
     const uint32_t n_min = has_min ? (uint32_t)(best >> 12) - 1u : 0u;
-    float Hm[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (has_min) (void)verify_model(rec, M, lowbias32(a.seed_mix ^ pair), h, Hm);  // valid: it scored a key
+    float Fm[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    uint32_t m = 0;
+    Model::winner(rec, M, lowbias32(a.seed_mix ^ pair), h, has_min, Fm, m);
     bool keep = false;
-    float Hr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float Fr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (has_min) {
         float acc[kVerifySums];
 #pragma unroll
         for (uint32_t e = 0; e < kVerifySums; e++) acc[e] = 0.0f;
         for (uint32_t j = tid; j < M; j += 256u) {  // candidate j into partial sum j mod 256, ascending j
             const float4 c = rec[j];
-            if (verify_inlier(Hm, c, a.t2)) verify_accumulate(acc, c);
+            if (Model::inlier(Fm, c, a.t2)) Model::accumulate(acc, c, m);
         }
 #pragma unroll
         for (uint32_t e = 0; e < kVerifySums; e++) part[e][tid] = acc[e];
@@ -267,55 +341,20 @@ __global__ __launch_bounds__(256) void k_verify_refine(VerifyArgs a) {
                 for (uint32_t e = 0; e < kVerifySums; e++) part[e][tid] = part[e][tid] + part[e][tid + s];
             __syncthreads();
         }
-        if (tid == 0u) {  // Gaussian elimination with partial pivoting (first maximal |pivot|), then back substitution
-            for (int i = 0, e = 0; i < 8; i++)
-                for (int j = i; j < 8; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
-            for (int i = 0; i < 8; i++) aug[i][8] = part[36 + i][0];
-            uint32_t ok = 1u;
-            for (int c = 0; c < 8 && ok; c++) {
-                int piv = c;
-                float pmax = fabsf(aug[c][c]);
-                for (int r = c + 1; r < 8; r++)
-                    if (fabsf(aug[r][c]) > pmax) pmax = fabsf(aug[r][c]), piv = r;
-                if (pmax == 0.0f) {
-                    ok = 0u;
-                    break;
-                }
-                if (piv != c)
-                    for (int q = 0; q < 9; q++) {
-                        const float tmp = aug[c][q];
-                        aug[c][q] = aug[piv][q];
-                        aug[piv][q] = tmp;
-                    }
-                for (int r = c + 1; r < 8; r++) {
-                    const float f = aug[r][c] / aug[c][c];
-                    for (int q = c + 1; q < 9; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
-                }
-            }
-            if (ok)
-                for (int r = 7; r >= 0; r--) {
-                    float s = aug[r][8];
-                    for (int q = r + 1; q < 8; q++) s = s - aug[r][q] * sol[q];
-                    sol[r] = s / aug[r][r];
-                    if (!isfinite(sol[r])) ok = 0u;
-                }
-            sol[8] = 1.0f;
-            s_ok = ok;
-        }
+        if (tid == 0u) s_ok = verify_solve(part, aug, sol);
         __syncthreads();
         if (s_ok) {
-#pragma unroll
-            for (int e = 0; e < 9; e++) Hr[e] = sol[e];
+            Model::from_solution(sol, m, Fr);
             uint32_t n = 0;
-            for (uint32_t j = tid; j < M; j += 256u) n += verify_inlier(Hr, rec[j], a.t2) ? 1u : 0u;
+            for (uint32_t j = tid; j < M; j += 256u) n += Model::inlier(Fr, rec[j], a.t2) ? 1u : 0u;
             atomicAdd(&s_count, n);
         }
         __syncthreads();
         keep = s_ok && 16u * s_count >= 15u * n_min;  // GV-6: the refit may lose a few marginal inliers, not 1/16 of them
     }
-    float Hk[9];
+    float Fk[9];
 #pragma unroll
-    for (int e = 0; e < 9; e++) Hk[e] = keep ? Hr[e] : Hm[e];
+    for (int e = 0; e < 9; e++) Fk[e] = keep ? Fr[e] : Fm[e];
     // inlier bytes of every query slot of the pair: one write each
     const uint32_t nq = min(a.counts[pair], a.cap);
     const uint32_t* const cand_of = a.cand_of + (size_t)pair * a.cap;
@@ -324,31 +363,40 @@ __global__ __launch_bounds__(256) void k_verify_refine(VerifyArgs a) {
         uint8_t b = 0;
         if (has_min && i < nq) {
             const uint32_t j = cand_of[i];
-            if (j != kVerifyNone) b = verify_inlier(Hk, rec[j], a.t2) ? 1 : 0;
+            if (j != kVerifyNone) b = Model::inlier(Fk, rec[j], a.t2) ? 1 : 0;
         }
         mask[i] = b;
     }
-    if (tid == 0u) {  // GV-7: the record, the model in level-0 pixels T^-1 * H * T divided by its [2][2] entry
+    if (tid == 0u) {  // the record, the model in level-0 pixels
         uint32_t* const out = a.model + (size_t)pair * kVerifyModelWords;
         float P[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (has_min) {
-            const float T[9] = {a.k, 0.0f, -(a.cx * a.k), 0.0f, a.k, -(a.cy * a.k), 0.0f, 0.0f, 1.0f};
-            const float ik = 1.0f / a.k;
-            const float Ti[9] = {ik, 0.0f, a.cx, 0.0f, ik, a.cy, 0.0f, 0.0f, 1.0f};
-            float G[9], Q[9];
-            verify_mat3(Hk, T, G);
-            verify_mat3(Ti, G, Q);
-#pragma unroll
-            for (int e = 0; e < 9; e++) P[e] = Q[e] / Q[8];
-        }
+        if (has_min) Model::to_pixels(Fk, a, P);
 #pragma unroll
         for (int e = 0; e < 9; e++) out[e] = __float_as_uint(P[e]);
         out[9] = M;
         out[10] = has_min ? (keep ? s_count : n_min) : 0u;
         out[11] = h;
-        out[12] = M < 4u ? (uint32_t)ORB_VERIFY_FEW : !has_min ? (uint32_t)ORB_VERIFY_DEGENERATE : keep ? (uint32_t)ORB_VERIFY_OK : (uint32_t)ORB_VERIFY_MINIMAL;
+        out[12] = M < Model::kSample ? (uint32_t)ORB_VERIFY_FEW : !has_min ? (uint32_t)ORB_VERIFY_DEGENERATE : keep ? (uint32_t)ORB_VERIFY_OK : (uint32_t)ORB_VERIFY_MINIMAL;
         out[13] = out[14] = out[15] = 0u;
     }
 }
+
+// grid (pairs, ceil(hyps / 64)), block 256
+__global__ __launch_bounds__(256) void k_verify_score(VerifyArgs a) {
+    const uint32_t pair = blockIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t M = a.n_cand[pair];
+    if (M < HomographyModel::kSample) return;  // uniform: k_verify_refine reads no key of such a pair
+    const float4* const rec = a.rec + (size_t)pair * a.cap;
+    const uint32_t h = blockIdx.y * kVerifyHypPerWg + lane;
+    float H[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // an invalid hypothesis: w' = 0, never an inlier
+    const bool valid = h < a.hyps && verify_model(rec, M, lowbias32(a.seed_mix ^ pair), h, H);
+    if (!valid)
+#pragma unroll
+        for (int e = 0; e < 9; e++) H[e] = 0.f;
+    verify_score_tail<HomographyModel>(a, rec, M, h, H, valid);
+}
+
+// grid (pairs), block 256
+__global__ __launch_bounds__(256) void k_verify_refine(VerifyArgs a) { verify_refine_body<HomographyModel>(a); }
 
 }  // namespace orb
