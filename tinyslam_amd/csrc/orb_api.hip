@@ -182,6 +182,7 @@ struct OrbProgram {
     struct {
         bool single_memcpy = false, single_split = false, single_serial = false, single_sync = false, single_block = false;
         bool no_swizzle = false, quiet = false;
+        bool front_generic = false, front_trace = false;  // TINYORB_FRONT_GENERIC: no instance of k_front with a compile-time geometry; TINYORB_FRONT_TRACE: say which
         int phase_mask = -1, brief_i_mask = -1, lds_pad = 0;
     } env;
     // device-visible addresses of the pinned single-frame staging arrays (resolved once)
@@ -587,6 +588,49 @@ int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_
     return ORB_OK;
 }
 
+// The geometry of level `lvl` of the plain fused pipeline for a batch of n frames; gw, gh: the octave's FAST dispatch domain (orb.rs:501-519).
+FrontGeom fused_level_geometry(const OrbProgram* p, uint32_t lvl, uint32_t gw, uint32_t gh, uint32_t n) {
+    const Pyramid& pyr = p->pyr;
+    FrontGeom g = front_geometry(pyr, lvl, gw ? gw : 8u, gh, n, p->band_rows_lvl[lvl], p->tile_w_lvl[lvl], p->ln_threads[lvl]);
+    if (gw == 0) g.gh = 0;  // no FAST dispatch at this octave (orb.rs:511-515 with width 0)
+    g.slot_base = p->bands.slot_base[lvl];
+    g.n_slots = p->bands.n_slots;
+    g.seg_cap = p->bands.seg_cap;
+    g.n_classes = p->seg_classes;
+    g.stamps = p->d_stamps;
+    if (p->env.phase_mask >= 0) g.phase_mask = (uint32_t)p->env.phase_mask;
+    if (p->env.no_swizzle) g.xcd_swizzle = 0u;
+    g.oob = p->oob;
+    g.wq = p->wq;
+    g.fp = p->opt.fp_contract;
+    g.store_grey = (lvl == 0 && pyr.depth > 1 && !(pyr.w[0] == 2u * pyr.w[1] && pyr.h[0] == 2u * pyr.h[1])) ? 1u : 0u;
+    return g;
+}
+
+// Which instance of k_front a prepared launch takes: one with a compile-time geometry (orb_kernels_front.h) when the launch is of that
+// instance's kind -- level, input, alignment, band height, threads, arithmetic form -- AND every field the geometry replaces holds the
+// compiled-in value, compared one by one (the frame size alone does not decide: TINYORB_BAND_ROWS, a program of one frame, a batch that
+// is not a multiple of 8, an out-of-level policy, another depth all change the geometry); the generic instance otherwise, and always
+// under TINYORB_FRONT_GENERIC=1.  `why`: what ruled the specialised instance out.
+FrontGeoId front_pick_geo(const OrbProgram* p, const FrontLaunch& L, const char** why = nullptr) {
+    const char* reason = nullptr;
+    FrontGeoId id = kFrontGeoGeneric;
+    const bool l0 = L.g.lvl == 0u;
+    if (p->env.front_generic) reason = "TINYORB_FRONT_GENERIC";
+    else if (L.g.lvl > 1u) reason = "lvl";
+    else if (L.input_y8) reason = "input_y8";
+    else if (L.general) reason = "general";
+    else if (L.oob) reason = "oob";
+    else if (L.from_plane) reason = "from_plane";
+    else if (front_form(p->opt.fp_contract, l0) != 0u) reason = "fp_contract";
+    else if (L.band_rows != (l0 ? FrontGeo720pL0::rows : FrontGeo720pL1::rows)) reason = "band_rows";
+    else if (!l0 && L.ln_threads != (uint32_t)kFrontThreadsLNBig) reason = "ln_threads";
+    else reason = l0 ? front_geo_mismatch<FrontGeo720pL0>(L.g, L.pyr) : front_geo_mismatch<FrontGeo720pL1>(L.g, L.pyr);
+    if (!reason) id = l0 ? kFrontGeo720pL0 : kFrontGeo720pL1;
+    if (why) *why = reason;
+    return id;
+}
+
 // The fused pipeline for frames [f0, f0 + n) of the batch on stream s: one k_front launch per level + BRIEF
 // (with_brief = false: the caller launches its own BRIEF kernel -- the single-frame path's k_brief_one).
 // first_level > 0 (single-frame call): the levels below it have been launched already (k_front_pair).
@@ -619,20 +663,8 @@ int run_fused_range(OrbProgram* p, const uint8_t* frames_all, uint32_t f0, uint3
             dim3 grid((pyr.w[lvl] + 63u) / 64u, (pyr.h[lvl] + 4u * kMipRows - 1u) / (4u * kMipRows), n);
             hipLaunchKernelGGL(k_mip, grid, dim3(64, 4), 0, sm, d_gray, pyr, lvl, (float)pyr.w[lvl - 1] / (float)pyr.w[lvl], (float)pyr.h[lvl - 1] / (float)pyr.h[lvl], p->wq);
         }
-        FrontGeom g = front_geometry(pyr, lvl, gw ? gw : 8u, gh, n, p->band_rows_lvl[lvl], p->tile_w_lvl[lvl], p->ln_threads[lvl]);
+        const FrontGeom g = fused_level_geometry(p, lvl, gw, gh, n);
         hipStream_t s_lvl = s;
-        if (gw == 0) g.gh = 0;  // no FAST dispatch at this octave (orb.rs:511-515 with width 0)
-        g.slot_base = p->bands.slot_base[lvl];
-        g.n_slots = p->bands.n_slots;
-        g.seg_cap = p->bands.seg_cap;
-        g.n_classes = p->seg_classes;
-        g.stamps = p->d_stamps;
-        if (p->env.phase_mask >= 0) g.phase_mask = (uint32_t)p->env.phase_mask;
-        if (p->env.no_swizzle) g.xcd_swizzle = 0u;
-        g.oob = p->oob;
-        g.wq = p->wq;
-        g.fp = p->opt.fp_contract;
-        g.store_grey = (lvl == 0 && D > 1 && !(pyr.w[0] == 2u * pyr.w[1] && pyr.h[0] == 2u * pyr.h[1])) ? 1u : 0u;
         if (g.n_bands * (g.tiled ? g.n_ct : 1u) != p->bands.slot_base[lvl + 1] - p->bands.slot_base[lvl])
             return fail(p, ORB_EINVAL, "internal: band count mismatch at level %u", lvl);
         if (!g.tiled && sizeof(BlurCol) * (size_t)g.n_var > 8u * (size_t)g.ts)  // the column table borrows the queues' storage
@@ -647,6 +679,7 @@ int run_fused_range(OrbProgram* p, const uint8_t* frames_all, uint32_t f0, uint3
                       p->band_rows_lvl[lvl], p->ln_threads[lvl], p->input_y8,
                       // rows not aligned to a quad, or the level-0 plane is needed (level 1 not an exact half): the general variant
                       lvl == 0 && ((pyr.w[0] & 3u) || g.store_grey), p->oob != kOobZero, false};
+        L.geo = front_pick_geo(p, L);
         {
             LaunchScope ls(p, s_lvl, lvl == 0 ? KID_FUSED_L0 : KID_FUSED_LN);
             const hipError_t e = kFrontLaunch[front_form(p->opt.fp_contract, lvl == 0 && !p->input_y8)](L);
@@ -946,6 +979,8 @@ int orb_program_create(const OrbConfig* config, const OrbOptions* options, OrbPr
         }
         p->env.no_swizzle = on("TINYORB_NO_SWIZZLE");
         p->env.quiet = getenv("TINYORB_QUIET") != nullptr;
+        p->env.front_generic = on("TINYORB_FRONT_GENERIC");
+        p->env.front_trace = on("TINYORB_FRONT_TRACE");
         p->env.phase_mask = num("TINYORB_PHASE_MASK", -1);
         p->env.brief_i_mask = num("TINYORB_BRIEF_I_MASK", -1);
         p->env.lds_pad = num("TINYORB_LDS_PAD", 0);
@@ -1106,6 +1141,23 @@ int orb_program_create(const OrbConfig* config, const OrbOptions* options, OrbPr
                 p->use_brief_t = brieft_geometry(p, rg, 2u, &p->brieft);
                 p->seg_classes = p->use_brief_t ? 2u : 1u;
                 for (auto set_max_lds : kFrontSetMaxLds) CREATE_TRY(set_max_lds((int)p->max_lds));  // every instance of k_front / k_front_pair
+                if (p->env.front_trace) {  // which instance of k_front a full batch (max_batch frames) takes at each level
+                    uint32_t width = W, height = H;
+                    for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) {
+                        const uint32_t gw = ((width + 7u) / 8u) * 8u, gh = ((height + 7u) / 8u) * 8u;
+                        width /= 2u;
+                        height /= 2u;
+                        const FrontGeom g = fused_level_geometry(p, lvl, gw, gh, p->max_batch);
+                        FrontLaunch L{};
+                        L.pyr = p->pyr, L.g = g, L.band_rows = p->band_rows_lvl[lvl], L.ln_threads = p->ln_threads[lvl], L.input_y8 = p->input_y8;
+                        L.general = lvl == 0 && ((p->pyr.w[0] & 3u) || g.store_grey), L.oob = p->oob != kOobZero;
+                        const char* why = nullptr;
+                        const FrontGeoId id = front_pick_geo(p, L, &why);
+                        fprintf(stderr, "tinyorb: k_front level %u (%ux%u, %u-row bands, batch %u) takes the %s instance%s%s\n", lvl, p->pyr.w[lvl], p->pyr.h[lvl],
+                                p->band_rows_lvl[lvl], p->max_batch, id == kFrontGeoGeneric ? "generic" : (id == kFrontGeo720pL0 ? "specialised 720p-L0" : "specialised 720p-L1"),
+                                why ? ": " : "", why ? why : "");
+                    }
+                }
             }
         }
     }

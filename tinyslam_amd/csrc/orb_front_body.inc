@@ -3,6 +3,10 @@
 // kernel that merely calls the device function compiles to a k_front<false> that is 5 % slower: hipcc schedules the
 // inlined copy differently.)  Expects, in scope: the template parameters L0, Y8, RB, UA, TILED, SRC, OOBK, FPF, the constant NTO,
 // block_id, and the kernel's arguments frames, frame_bytes, gray, blur, blur_rowc, pyr, geo, thr, seg_counts, segments.
+// In k_front<..., GEO> with a geometry, `pyr` and `geo` are copies of the arguments whose shape fields are GEO's constants
+// (front_pyr_apply / front_geo_apply, orb_kernels_front.h): LS, TS, w, h, gw, Q, the band and slot counts, ovf_words and the swizzle
+// below are then literals, and the reciprocals, blur_tap() denominators, pitch products and trip counts built on them fold.  The
+// body itself knows nothing of it: one text serves both.
     constexpr int NT = NTO ? NTO : (L0 ? kFrontThreadsL0 : kFrontThreadsLN), R = RB, TC = kFrontTmpRows;
     constexpr int LUM = FPF & 3;             // the luminance's form (lum_form())
     constexpr bool BLC = (FPF & 4) != 0;     // the blur taps as fused multiply-adds

@@ -33,9 +33,30 @@ constexpr bool kRest = (FP & 3) == 0;    // this unit also holds the kernels tha
     else FRONT_GO(PRE, 8, POST);
 #define COMMA ,
 
+// The instances with a compile-time geometry (orb_kernels_front.h): the default form's unit holds them, no other.
+#if TINYORB_FRONT_FP == 0
+#define FRONT_GEO_L0 true, false, 16, false, false, false, false, 0, FP, FrontGeo720pL0
+#define FRONT_GEO_L1 false, false, 32, false, false, false, false, kFrontThreadsLNBig, FPB, FrontGeo720pL1
+#endif
+
 hipError_t ORB_CAT(front_launch_fp, TINYORB_FRONT_FP)(const FrontLaunch& L) {
     const dim3 grid(L.grid);
     const bool tiled = L.g.tiled != 0u;
+    if (L.geo != kFrontGeoGeneric) {  // orb_api.hip has compared every field the geometry replaces (front_pick_geo)
+#if TINYORB_FRONT_FP == 0
+        if (L.geo == kFrontGeo720pL0) {
+            const dim3 block(kFrontThreadsL0);
+            FRONT_GO(FRONT_GEO_L0);
+            return hipGetLastError();
+        }
+        if (L.geo == kFrontGeo720pL1) {
+            const dim3 block(kFrontThreadsLNBig);
+            FRONT_GO(FRONT_GEO_L1);
+            return hipGetLastError();
+        }
+#endif
+        return hipErrorInvalidValue;  // no such instance in this unit
+    }
     if (L.g.lvl == 0u && !L.input_y8 && !L.from_plane) {  // level 0 from RGBA: the luminance's form is this unit's
         const dim3 block(kFrontThreadsL0);
         if (tiled && L.general) { FRONT_BY_ROWS_TILED(true COMMA false, true COMMA true COMMA false COMMA false COMMA 0 COMMA FP) }
@@ -94,6 +115,10 @@ hipError_t ORB_CAT(front_set_max_lds_fp, TINYORB_FRONT_FP)(int max_lds) {
         reinterpret_cast<const void*>(&k_front_pair<8, 8, false, FP>)};
     for (const void* f : rgba)
         if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) return e;
+#if TINYORB_FRONT_FP == 0
+    for (const void* f : {FN(FRONT_GEO_L0), FN(FRONT_GEO_L1)})
+        if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds)) return e;
+#endif
     if constexpr (kRest) {
         const void* const rest[] = {
             FN4(true COMMA true, false COMMA false COMMA false COMMA false COMMA 0 COMMA FPB), FN4(true COMMA true, true COMMA false COMMA false COMMA false COMMA 0 COMMA FPB),

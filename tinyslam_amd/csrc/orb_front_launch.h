@@ -10,6 +10,9 @@
 
 namespace orb {
 
+// FrontLaunch::geo -- which instance a launch takes: the generic one, or one with a compile-time geometry (orb_kernels_front.h)
+enum FrontGeoId : uint32_t { kFrontGeoGeneric = 0, kFrontGeo720pL0 = 1, kFrontGeo720pL1 = 2 };
+
 struct FrontLaunch {
     const uint8_t* frames;
     size_t frame_bytes;
@@ -31,6 +34,7 @@ struct FrontLaunch {
     bool oob;             // an out-of-level policy other than "zero" (levels >= 1: the OOBK instances)
     bool from_plane;      // take the level >= 1 kernel (rows from the stored grey plane) whatever g.lvl says: the arc / NMS extension's blur-only
                           // launches read level 0's plane, which k_front_i has written (512 threads, 16-row bands)
+    FrontGeoId geo = kFrontGeoGeneric;  // an instance with a compile-time geometry: only in the unit of form 0, and only after front_geo_mismatch()
 };
 
 struct FrontPairLaunch {  // k_front_pair: levels 0 and 1 of one frame in one launch (8-row bands)

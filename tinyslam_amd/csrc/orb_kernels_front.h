@@ -101,6 +101,81 @@ struct __attribute__((aligned(8))) BlurCol {
 };
 static_assert(sizeof(BlurCol) == 24, "BlurCol layout");
 
+// ---- compile-time geometry (k_front's last template parameter) ----
+// Every workgroup of a level recomputes what depends on the level's shape alone -- item-index reciprocals, the BlurCol table's divisions
+// by the width, products by the LDS pitches, trip counts, the block swizzle's division -- from run-time FrontGeom / Pyramid fields.  An
+// instance with a geometry other than FrontGeoNone takes those fields from the instruction stream instead: front_geo_apply() /
+// front_pyr_apply() overwrite them with the geometry's constants on the kernel's own copies of its arguments, and everything
+// downstream folds.  The host takes such an instance only for a launch whose every replaced field equals the constant
+// (front_geo_mismatch(), field by field); any other launch takes the generic instance.  What changes per frame or per program without
+// changing the shape stays an argument: the pointers, frame_bytes, thr, seg_cap, stamps.
+// The fields of FrontGeom a geometry replaces (all uint32_t; wq, a float, rides along).  Not among them: n_frames, fp, oob and the
+// column-tile fields, which the full-width kernels never read.
+#define ORB_FRONT_GEO_FIELDS(X) \
+    X(lvl) X(rows) X(tiled) X(gw) X(gh) X(n_bands) X(ls) X(ts) X(write_mip) X(store_grey) X(xcd_swizzle) X(phase_mask) X(slot_base) \
+    X(n_slots) X(n_classes) X(blur_p) X(blur_q) X(n_var) X(ovf_words)
+struct FrontGeoNone {
+    static constexpr bool on = false;
+};
+// The packed pyramid of a 1280x720 frame at depth 2 (layout_pyramid), shared by its two levels' geometries.
+struct FrontPyr720pD2 {
+    static constexpr uint32_t depth = 2, w0 = 1280, h0 = 720, w1 = 640, h1 = 360, off0 = 0, off1 = 1280 * 720, stride = 1280 * 720 + 640 * 360,
+                              row_off0 = 0, row_off1 = 720, row_stride = 1080;
+};
+// Level 0 of 1280x720 from RGBA in a batch whose frame count is a multiple of 8: 16-row bands, two corner lists per band.
+struct FrontGeo720pL0 : FrontPyr720pD2 {
+    static constexpr bool on = true;
+    static constexpr uint32_t lvl = 0, rows = 16, tiled = 0, gw = 1280, gh = 720, n_bands = 45, ls = kLdsPad + 1288, ts = 1280, write_mip = 1,
+                              store_grey = 0, xcd_swizzle = 1, phase_mask = 15, slot_base = 0, n_slots = 45 + 12, n_classes = 2, blur_p = 563,
+                              blur_q = 1125, n_var = 1280 - 1125, ovf_words = 16 * 80 / 32;
+    static constexpr float wq = 0.0f;
+};
+// Level 1 of the same program: 640x360 from the stored mip, 32-row bands on kFrontThreadsLNBig threads.
+struct FrontGeo720pL1 : FrontPyr720pD2 {
+    static constexpr bool on = true;
+    static constexpr uint32_t lvl = 1, rows = 32, tiled = 0, gw = 640, gh = 360, n_bands = 12, ls = kLdsPad + 648, ts = 640, write_mip = 0,
+                              store_grey = 0, xcd_swizzle = 1, phase_mask = 15, slot_base = 45, n_slots = 45 + 12, n_classes = 2, blur_p = 282,
+                              blur_q = 563, n_var = 640 - 563, ovf_words = 32 * 40 / 32;
+    static constexpr float wq = 0.0f;
+};
+template <class GEO>
+__host__ __device__ __forceinline__ FrontGeom front_geo_apply(FrontGeom g) {
+    if constexpr (GEO::on) {
+#define X(f) g.f = GEO::f;
+        ORB_FRONT_GEO_FIELDS(X)
+#undef X
+        g.wq = GEO::wq;
+    }
+    return g;
+}
+template <class GEO>
+__host__ __device__ __forceinline__ Pyramid front_pyr_apply(Pyramid p) {
+    if constexpr (GEO::on) {
+        p.depth = GEO::depth;
+        p.w[0] = GEO::w0, p.h[0] = GEO::h0, p.off[0] = GEO::off0, p.row_off[0] = GEO::row_off0;
+        p.w[1] = GEO::w1, p.h[1] = GEO::h1, p.off[1] = GEO::off1, p.row_off[1] = GEO::row_off1;
+        p.stride = GEO::stride, p.row_stride = GEO::row_stride;
+    }
+    return p;
+}
+// Host: the first field of a launch that differs from what GEO compiles in, by name; null when all agree.
+template <class GEO>
+inline const char* front_geo_mismatch(const FrontGeom& g, const Pyramid& p) {
+#define X(f) \
+    if (g.f != GEO::f) return #f;
+    ORB_FRONT_GEO_FIELDS(X)
+#undef X
+    if (g.wq != GEO::wq) return "wq";
+    if (p.depth != GEO::depth) return "depth";
+    if (p.w[0] != GEO::w0 || p.w[1] != GEO::w1) return "w";
+    if (p.h[0] != GEO::h0 || p.h[1] != GEO::h1) return "h";
+    if (p.off[0] != GEO::off0 || p.off[1] != GEO::off1) return "off";
+    if (p.row_off[0] != GEO::row_off0 || p.row_off[1] != GEO::row_off1) return "row_off";
+    if (p.stride != GEO::stride) return "stride";
+    if (p.row_stride != GEO::row_stride) return "row_stride";
+    return nullptr;
+}
+
 __host__ __device__ inline uint32_t front_lds_bytes(const FrontGeom& g) {
     // grey rows + queues B/C (the blur column table lives there first: 24 B x n_var <= 8 B x ts, checked on the host)
     // + queue A + 5 counters + blur row constants (2 x rows float4)
@@ -380,14 +455,21 @@ __device__ __forceinline__ void front_body(const uint32_t block_id, const uint8_
 }
 
 // NTK: threads of the workgroup when not the level's default (levels >= 1: kFrontThreadsLNBig)
-template <bool L0, bool Y8 = false, int RB = kFrontRows, bool UA = false, bool TILED = false, bool SRC = false, bool OOBK = false, int NTK = 0, int FPF = 0>
+// GEO: the level's shape as compile-time constants (FrontGeo720pL0, ...; see ORB_FRONT_GEO_FIELDS), or FrontGeoNone: everything from the
+//     arguments.  The body reads `pyr` and `geo` as before; with a geometry they are copies whose shape fields are constants.
+template <bool L0, bool Y8 = false, int RB = kFrontRows, bool UA = false, bool TILED = false, bool SRC = false, bool OOBK = false, int NTK = 0, int FPF = 0,
+          class GEO = FrontGeoNone>
 __global__ __launch_bounds__(NTK ? NTK : (L0 ? kFrontThreadsL0 : kFrontThreadsLN), (L0 || NTK == kFrontThreadsLNBig) ? 8 : 4) void k_front(const uint8_t* __restrict__ frames, size_t frame_bytes,
                                                          uint16_t* __restrict__ gray, uint16_t* __restrict__ blur,
-                                                         uint16_t* __restrict__ blur_rowc, Pyramid pyr,
-                                                         FrontGeom geo, float thr, uint32_t* __restrict__ seg_counts,
+                                                         uint16_t* __restrict__ blur_rowc, Pyramid pyr_arg,
+                                                         FrontGeom geo_arg, float thr, uint32_t* __restrict__ seg_counts,
                                                          CornerData* __restrict__ segments) {
+    static_assert(!GEO::on || (!Y8 && !UA && !TILED && !SRC && !OOBK), "geometries exist for the aligned full-width kernels only");
+    if constexpr (GEO::on) static_assert((int)GEO::rows == RB && (GEO::lvl == 0u) == L0, "the geometry is of another instance");
     constexpr int NTO = NTK;
     const uint32_t block_id = blockIdx.x;
+    const Pyramid pyr = front_pyr_apply<GEO>(pyr_arg);
+    const FrontGeom geo = front_geo_apply<GEO>(geo_arg);
 #include "orb_front_body.inc"
 }
 

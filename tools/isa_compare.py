@@ -1,11 +1,15 @@
 """Compares the gfx950 machine code of two builds of libtinyorb.so kernel by kernel.
 
-    python tools/isa_compare.py OLD/libtinyorb.so NEW/libtinyorb.so
+    python tools/isa_compare.py OLD/libtinyorb.so NEW/libtinyorb.so [--ignore-template-arg=MANGLED]
 
 Every clang offload bundle in the library's .hip_fatbin section (one per translation unit) is opened, its gfx950 code object
 disassembled with llvm-objdump, and each function's instructions (encodings included, addresses and the s_nop padding after
 its end dropped) compared.  Prints one line per function present in both (identical / DIFFERENT) and the functions only one
-build has; exits 1 if any function present in both differs.  Cross-compiled builds suffice: no GPU is needed."""
+build has; exits 1 if any function present in both differs.  Cross-compiled builds suffice: no GPU is needed.
+
+--ignore-template-arg=MANGLED (e.g. NS_12FrontGeoNoneE): a build that gave a kernel template one more, defaulted parameter names every
+instance differently; the fragment is dropped from the function names, the substitution indices it shifts (S3_ -> S4_) are levelled and the
+symbol a branch target is printed against is left out, so that the instances pair up and only their instructions are compared."""
 import os
 import re
 import struct
@@ -39,9 +43,10 @@ def code_objects(blob, arch="gfx950"):
     return out
 
 
-def functions(lib):
+def functions(lib, ignore=None):
     """{function name: list of instruction lines without addresses} over every gfx950 code object of the library."""
     funcs = {}
+    level = (lambda n: re.sub(r"S\d*_", "S_", n.replace(ignore, ""))) if ignore else (lambda n: n)
     for co in code_objects(fatbin(lib)):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(co)
@@ -51,13 +56,15 @@ def functions(lib):
         for line in text.splitlines():
             m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
             if m:
-                name = m.group(1)
+                name = level(m.group(1))
                 funcs.setdefault(name, [])
                 continue
             if name and line.strip():
                 # "\ts_load_dword s4, s[0:1], 0x10   // 000000001A00: C0020100 00000010" -> instruction + encoding
                 ins, _, tail = line.partition("//")
                 enc = tail.split(":", 1)[1].strip() if ":" in tail else ""
+                if ignore:
+                    enc = re.sub(r"\s*<.*>$", "", enc)  # "BF850609 <function+0x1848>": the encoding holds the offset
                 funcs[name].append(ins.strip() + " | " + enc)
     for ins in funcs.values():  # the alignment padding after a function's end (its length depends on what follows it)
         while ins and ins[-1].startswith("s_nop 0 |"):
@@ -66,7 +73,8 @@ def functions(lib):
 
 
 def main():
-    old, new = functions(sys.argv[1]), functions(sys.argv[2])
+    ignore = next((a.split("=", 1)[1] for a in sys.argv[3:] if a.startswith("--ignore-template-arg=")), None)
+    old, new = functions(sys.argv[1], ignore), functions(sys.argv[2], ignore)
     bad = 0
     for name in sorted(set(old) & set(new)):
         same = old[name] == new[name]
