@@ -218,10 +218,17 @@ def test_state_and_ordering(tinyorb, oracle):
         for src in (V, G, M):
             prog.track_consecutive(5 if src != V else 4, source=src)
             single[src] = ([prog.track_read(f, cap).tobytes() for f in range(4)], prog.track_frames(5).tobytes())
+
+        def epipolar():
+            return [tuple(r.tobytes() for r in prog.verify_epipolar_read(f, cap)) for f in range(3)]
+
+        prog.verify_epipolar(4)
+        single_epi = epipolar()
         s1, s2 = torch.cuda.Stream(device=0), torch.cuda.Stream(device=0)
         for rep in range(2):
             a, b = (s1, s2) if rep == 0 else (s2, s1)
             prog.match_consecutive(5, stream=a.cuda_stream)
+            prog.verify_epipolar(4, stream=b.cuda_stream)  # waits for the match on a, whose results it reads
             prog.track_consecutive(5, source=M, stream=b.cuda_stream)
             prog.verify_consecutive(4, stream=a.cuda_stream)
             prog.track_consecutive(4, source=V, stream=b.cuda_stream)
@@ -230,6 +237,7 @@ def test_state_and_ordering(tinyorb, oracle):
             got_g = ([prog.track_read(f, cap).tobytes() for f in range(4)], prog.track_frames(5).tobytes())
             assert got_g == single[G]
             prog.track_consecutive(4, source=V, stream=a.cuda_stream)
+            assert epipolar() == single_epi
             prog.match_consecutive(5, stream=b.cuda_stream)  # waits for the track call on a before it overwrites the matches
             assert ([prog.track_read(f, cap).tobytes() for f in range(4)], prog.track_frames(5).tobytes()) == single[V]
             prog.track_consecutive(5, source=M, stream=a.cuda_stream)

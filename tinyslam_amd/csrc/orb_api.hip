@@ -60,8 +60,28 @@ struct ProfSpan {
 
 }  // namespace
 
-// Device state of one verifier: the buffers of VerifyArgs (allocated by the verifier's first call, all or none), the event behind
-// its last call and what that call covered
+// The stages that run after extraction.  Each owns ONE set of buffers per program, shared by both output sets and by whatever stream
+// the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
+// stages whose results it reads, which the entry point names; and the stages that read what it overwrites, kReadersOf[stage].
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_COUNT };
+const uint32_t kReadersOf[ST_COUNT] = {
+    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it)
+    1u << ST_GUIDE | 1u << ST_TRACK,                  // verify: verify.model (guided, ORB_GUIDE_VERIFIED), verify.mask (track, ORB_TRACK_VERIFIED)
+    0u,                                               // epi: its results are only read back by the host
+    1u << ST_TRACK,                                   // guide: d_gmatch (track, ORB_TRACK_GUIDED)
+    0u,                                               // track: read back by the host
+};
+
+// The last call of a stage
+struct Stage {
+    hipEvent_t done = nullptr;     // behind it (created by the stage's first call)
+    hipStream_t stream = nullptr;  // the stream it ran on
+    uint64_t seq = 0;              // batch_seq of the batch it read
+    uint32_t set = 0;              // output set it read
+    uint32_t extent = 0;           // pairs (verify, epi, guide) or frames (match, track) it covered; 0: the stage has never run
+};
+
+// The buffers of VerifyArgs, one set per verifier
 struct VerifierState {
     float4* rec = nullptr;              // [max_batch][max_features] candidates (u, v, u2, v2)
     uint32_t* cand = nullptr;           // [max_batch][max_features] candidate of each query
@@ -69,11 +89,6 @@ struct VerifierState {
     unsigned long long* keys = nullptr; // [max_batch][kVerifyMaxHyp]
     uint32_t* model = nullptr;          // [max_batch] OrbPairModel
     uint8_t* mask = nullptr;            // [max_batch][max_features] inlier bytes
-    hipEvent_t done = nullptr;
-    hipStream_t stream = nullptr;
-    uint32_t pairs = 0;                 // pairs of the last call (0: none)
-    uint64_t seq = 0;                   // orb_verify_consecutive only: batch_seq of the batch the last call read (its match's)
-    uint32_t set = 0;                   // orb_verify_consecutive only: output set it read
 };
 
 struct OrbProgram {
@@ -126,33 +141,23 @@ struct OrbProgram {
     uint32_t* d_iseg_before = nullptr;
     unsigned long long* d_thr_key = nullptr;
     uint32_t ibrief_lds = 0;
-    MatchRecord* d_matches = nullptr;  // [max_batch][max_features], allocated by the first orb_match_consecutive
+    uint64_t batch_seq = 0;    // batched calls so far (every call that sets last_batch); a stage records which one it read
+    Stage stage[ST_COUNT];     // the last call of each stage after extraction
+    // orb_match_consecutive (orb_kernels_match.h)
+    MatchRecord* d_matches = nullptr;  // [max_batch][max_features]
     uint8_t* d_desc8 = nullptr;        // [max_batch][max_features][128 or 256]: the descriptors as +-1 in fp4 (k_match_fp4) or +-127 in int8 (k_match_mfma)
     int match_valu = -1;               // which matcher (0 fp4, 1 vector unit: TINYORB_MATCH_VALU=1, 2 int8: TINYORB_MATCH_I8=1); read once
-    // d_matches and d_desc8 are ONE buffer each per program, shared by both output sets and by whatever stream the caller passes: a match
-    // on another stream is ordered behind the one before (its expand kernel would overwrite rows the earlier match still reads)
-    hipEvent_t match_done = nullptr;
-    hipStream_t match_stream = nullptr;
-    uint64_t batch_seq = 0;    // batched calls so far (every call that sets last_batch); the matcher records which one it read
-    uint64_t match_seq = 0;    // batch_seq at the last orb_match_consecutive (0: none)
-    uint32_t match_set = 0;    // output set it read
-    uint32_t match_frames = 0; // frames it matched
     // orb_verify_consecutive (orb_kernels_verify.h) and orb_verify_epipolar (orb_kernels_epipolar.h): a set of buffers each
     VerifierState verify, epi;
-    // orb_match_guided (orb_kernels_guide.h): one set of buffers per program, allocated by the first call
+    // orb_match_guided (orb_kernels_guide.h)
     uint4* d_gsrec = nullptr;             // [max_batch][max_features] records in cell order (x0, y0, index, octave)
     uint4* d_gsdesc = nullptr;            // [max_batch][max_features][2] descriptors in cell order
     uint32_t* d_gcell = nullptr;          // [max_batch][kGuideMaxCells + 1] cell starts
     MatchRecord* d_gmatch = nullptr;      // [max_batch][max_features] results
     float* d_gmodel = nullptr;            // [max_batch][9] the caller's models (ORB_GUIDE_HOST)
     float* h_gmodel = nullptr;            // pinned staging of the same
-    hipEvent_t guide_done = nullptr;
-    hipStream_t guide_stream = nullptr;
-    uint32_t guide_pairs = 0;             // pairs of the last guided call (0: none)
     int guide_cell = -1;                  // log2 of the grid's cell size (TINYORB_GUIDE_CELL); -1 until the first call
-    uint64_t guide_seq = 0;               // batch_seq of the batch the last guided call read
-    uint32_t guide_set = 0;               // output set it read
-    // orb_track_consecutive (orb_kernels_track.h): one set of buffers per program, allocated by the first call
+    // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
     uint32_t* d_tnext = nullptr;          // [max_batch][max_features]
@@ -161,9 +166,6 @@ struct OrbProgram {
     uint32_t* d_tlinks = nullptr;         // [max_batch] links per pair
     uint32_t* d_tshared = nullptr;        // [max_batch][max_batch] shared(k, f) at [f][k]
     uint32_t* d_tframe = nullptr;         // [max_batch] OrbTrackFrame
-    hipEvent_t track_done = nullptr;
-    hipStream_t track_stream = nullptr;
-    uint32_t track_frames = 0;            // n_frames of the last track call (0: none)
     int track_global_keys = -1;           // TINYORB_TRACK_GLOBAL_KEYS; -1 until the first call
     uint32_t* d_prov2_counts = nullptr;
     CornerData* d_prov2 = nullptr;
@@ -263,24 +265,113 @@ int fail(OrbProgram* p, int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail((p), ORB_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// Makes stream s wait behind a stage (its event `done`) that last ran on another stream; nothing to do when the stage has not run
-// (stage_stream is null) or ran on s itself.
-hipError_t wait_behind(hipStream_t s, hipStream_t stage_stream, hipEvent_t done) {
-    return stage_stream && stage_stream != s ? hipStreamWaitEvent(s, done, 0) : hipSuccess;
+// The stream of a call that takes one: the caller's, else the last batch's, else the program's own.
+hipStream_t call_stream(const OrbProgram* p, void* stream) {
+    return stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
 }
 
-// hipMalloc of n buffers, all or none: a failure frees the earlier ones and leaves every buf[i] null, so the caller records nothing and
-// its next call allocates again.
-int alloc_all_or_none(OrbProgram* p, const char* who, int n, const size_t* bytes, void** buf) {
+struct StageBuf {
+    void** slot;   // where the stage keeps the buffer's address
+    size_t bytes;
+    bool pinned;   // host memory (hipHostMalloc); else device memory
+};
+const int kMaxStageBufs = 8;
+
+// The buffers of stage `which`, named here and nowhere else: its first call fills the slots, orb_program_destroy frees them.  Returns how many.
+int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
+    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    int n = 0;
+    const auto add = [&](auto** slot, size_t bytes, bool pinned = false) { b[n++] = {(void**)slot, bytes, pinned}; };
+    switch (which) {
+    case ST_MATCH:  // allocated by orb_match_consecutive itself (d_desc8 only for a matrix-core matcher, and softly); listed to be freed
+        add(&p->d_matches, 0);
+        add(&p->d_desc8, 0);
+        break;
+    case ST_VERIFY:
+    case ST_EPI: {
+        VerifierState& v = which == ST_VERIFY ? p->verify : p->epi;
+        add(&v.rec, B * cap * sizeof(float4));
+        add(&v.cand, B * cap * sizeof(uint32_t));
+        add(&v.n, B * sizeof(uint32_t));
+        add(&v.keys, B * kVerifyMaxHyp * sizeof(unsigned long long));
+        add(&v.model, B * sizeof(OrbPairModel));
+        add(&v.mask, B * cap);
+        break;
+    }
+    case ST_GUIDE:
+        add(&p->d_gsrec, B * cap * sizeof(uint4));
+        add(&p->d_gsdesc, B * cap * 2u * sizeof(uint4));
+        add(&p->d_gcell, B * (kGuideMaxCells + 1u) * sizeof(uint32_t));
+        add(&p->d_gmatch, B * cap * sizeof(MatchRecord));
+        add(&p->d_gmodel, B * 9u * sizeof(float));
+        add(&p->h_gmodel, B * 9u * sizeof(float), true);
+        break;
+    case ST_TRACK:
+        add(&p->d_tkeys, B * cap * sizeof(uint32_t));
+        add(&p->d_tprev, B * cap * sizeof(uint32_t));
+        add(&p->d_tnext, B * cap * sizeof(uint32_t));
+        add(&p->d_tptr, 2u * B * cap * sizeof(uint4));
+        add(&p->d_tlinks, B * sizeof(uint32_t));
+        add(&p->d_tshared, B * B * sizeof(uint32_t));
+        add(&p->d_tframe, B * sizeof(OrbTrackFrame));
+        add(&p->d_track, B * cap * sizeof(OrbTrack));
+        break;
+    }
+    return n;
+}
+
+void free_stage_buffers(OrbProgram* p, int which) {
+    StageBuf b[kMaxStageBufs];
+    const int n = stage_buffers(p, which, b);
     for (int i = 0; i < n; i++) {
-        const hipError_t e = hipMalloc(&buf[i], bytes[i]);
+        if (*b[i].slot) (void)(b[i].pinned ? hipHostFree(*b[i].slot) : hipFree(*b[i].slot));
+        *b[i].slot = nullptr;
+    }
+}
+
+// A stage's buffers on its first call, all or none: a failure frees the earlier ones and leaves every slot null, so the next call
+// allocates again.
+int alloc_all_or_none(OrbProgram* p, int which, const char* who) {
+    StageBuf b[kMaxStageBufs];
+    const int n = stage_buffers(p, which, b);
+    if (*b[0].slot) return ORB_OK;
+    for (int i = 0; i < n; i++) {
+        const hipError_t e = b[i].pinned ? hipHostMalloc(b[i].slot, b[i].bytes, hipHostMallocDefault) : hipMalloc(b[i].slot, b[i].bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            for (int j = 0; j < i; j++) (void)hipFree(buf[j]);
-            for (int j = 0; j < n; j++) buf[j] = nullptr;
-            return fail(p, ORB_EHIP, "%s: hipMalloc of %zu bytes failed: %s", who, bytes[i], hipGetErrorString(e));
+            *b[i].slot = nullptr;
+            free_stage_buffers(p, which);
+            if (b[i].pinned) return fail(p, ORB_EHIP, "%s: hipHostMalloc failed: %s", who, hipGetErrorString(e));
+            return fail(p, ORB_EHIP, "%s: hipMalloc of %zu bytes failed: %s", who, b[i].bytes, hipGetErrorString(e));
         }
     }
+    return ORB_OK;
+}
+
+// "The last call of this stage is of the current batch and output set": what a later stage asks before it reads the stage's results.
+bool stage_fresh(const OrbProgram* p, const Stage& st) { return st.extent && st.seq == p->batch_seq && st.set == p->cur_set; }
+
+// Opens a call of stage `which`: its stream, its event on first use, and the waits behind the stage itself, the stages in `reads` (bits
+// 1 << StageId) and the readers of what it overwrites -- those that have run, and on another stream.
+int stage_begin(OrbProgram* p, int which, void* stream, uint32_t reads, hipStream_t* s_out) {
+    const hipStream_t s = call_stream(p, stream);
+    Stage& self = p->stage[which];
+    if (!self.done) HIP_TRY(p, hipEventCreateWithFlags(&self.done, hipEventDisableTiming));
+    const uint32_t behind = 1u << which | reads | kReadersOf[which];
+    for (int i = 0; i < ST_COUNT; i++) {
+        const Stage& o = p->stage[i];
+        if ((behind >> i & 1u) && o.stream && o.stream != s) HIP_TRY(p, hipStreamWaitEvent(s, o.done, 0));
+    }
+    *s_out = s;
+    return ORB_OK;
+}
+
+// Closes it after the launches.  p->last_stream is the entry point's business: only the matcher and the verifiers move it.
+int stage_end(OrbProgram* p, int which, hipStream_t s, uint32_t extent) {
+    HIP_TRY(p, hipGetLastError());
+    Stage& self = p->stage[which];
+    HIP_TRY(p, hipEventRecord(self.done, s));
+    self = {self.done, s, p->batch_seq, p->cur_set, extent};
     return ORB_OK;
 }
 
@@ -1408,7 +1499,6 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_prov_counts);
     (void)hipFree(p->d_prov);
     (void)hipFree(p->d_prov_scores);
-    (void)hipFree(p->d_matches);
     (void)hipFree(p->d_xband_counts);
     (void)hipFree(p->d_iseg);
     (void)hipFree(p->d_iseg_scores);
@@ -1423,28 +1513,10 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_sin);
     if (p->d_rot) (void)hipFree(p->d_rot);
     (void)hipFree(p->d_stamps);
-    (void)hipFree(p->d_desc8);
-    if (p->match_done) (void)hipEventDestroy(p->match_done);
-    for (VerifierState* st : {&p->verify, &p->epi}) {
-        for (void* b : {(void*)st->rec, (void*)st->cand, (void*)st->n, (void*)st->keys, (void*)st->model, (void*)st->mask}) (void)hipFree(b);
-        if (st->done) (void)hipEventDestroy(st->done);
+    for (int st = 0; st < ST_COUNT; st++) {
+        free_stage_buffers(p, st);
+        if (p->stage[st].done) (void)hipEventDestroy(p->stage[st].done);
     }
-    (void)hipFree(p->d_gsrec);
-    (void)hipFree(p->d_gsdesc);
-    (void)hipFree(p->d_gcell);
-    (void)hipFree(p->d_gmatch);
-    (void)hipFree(p->d_gmodel);
-    if (p->h_gmodel) (void)hipHostFree(p->h_gmodel);
-    if (p->guide_done) (void)hipEventDestroy(p->guide_done);
-    (void)hipFree(p->d_tkeys);
-    (void)hipFree(p->d_tprev);
-    (void)hipFree(p->d_tnext);
-    (void)hipFree(p->d_tptr);
-    (void)hipFree(p->d_track);
-    (void)hipFree(p->d_tlinks);
-    (void)hipFree(p->d_tshared);
-    (void)hipFree(p->d_tframe);
-    if (p->track_done) (void)hipEventDestroy(p->track_done);
     if (p->single_done_ev) (void)hipEventDestroy(p->single_done_ev);
     if (p->h_count) (void)hipHostFree(p->h_count);
     if (p->d_single_done) (void)hipFree(p->d_single_done);
@@ -1835,7 +1907,7 @@ int orb_extract_batch_host(OrbProgram* p, const uint8_t* frames_host, uint32_t n
 int orb_batch_sync(OrbProgram* p) {
     if (!p) return ORB_EINVAL;
     HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipStreamSynchronize(p->last_stream ? p->last_stream : p->stream));
+    HIP_TRY(p, hipStreamSynchronize(call_stream(p, nullptr)));
     return ORB_OK;
 }
 
@@ -1869,8 +1941,7 @@ namespace {
 // stream is first ordered behind the batch with an event.
 int launch_compact(OrbProgram* p, uint32_t n, uint32_t* counts, uint64_t* offsets, CornerData* corners,
                    CornerDescriptor* desc, size_t capacity, void* stream, hipStream_t* used) {
-    hipStream_t batch = p->last_stream ? p->last_stream : p->stream;
-    hipStream_t s = stream ? (hipStream_t)stream : batch;
+    hipStream_t batch = call_stream(p, nullptr), s = call_stream(p, stream);
     if (s != batch) {
         if (!p->order_event) HIP_TRY(p, hipEventCreateWithFlags(&p->order_event, hipEventDisableTiming));
         HIP_TRY(p, hipEventRecord(p->order_event, batch));
@@ -2073,7 +2144,6 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
     if (!p->d_matches) HIP_TRY(p, hipMalloc(&p->d_matches, (size_t)p->max_batch * cap * sizeof(MatchRecord)));
-    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
     if (p->match_valu < 0) {  // which matcher: 0 the block-scaled fp4 form on the matrix cores (default), 1 the vector unit, 2 the int8 form
         const char* e = getenv("TINYORB_MATCH_VALU");
         const char* e8 = getenv("TINYORB_MATCH_I8");
@@ -2089,15 +2159,8 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
         mfma = false;
     }
     const dim3 grid_e((unsigned)((cap + 31u) / 32u), n_frames), grid_m(n_frames - 1u, (unsigned)((cap + kMatchQueriesPerWg - 1u) / kMatchQueriesPerWg));
-    // one result buffer and one expanded-descriptor buffer per program: a match on another stream than the last one waits for it
-    if (!p->match_done) HIP_TRY(p, hipEventCreateWithFlags(&p->match_done, hipEventDisableTiming));
-    HIP_TRY(p, wait_behind(s, p->match_stream, p->match_done));
-    // and behind a verification on another stream, which still reads the matches this call overwrites
-    HIP_TRY(p, wait_behind(s, p->verify.stream, p->verify.done));
-    // and behind an epipolar verification on another stream, which reads them too
-    HIP_TRY(p, wait_behind(s, p->epi.stream, p->epi.done));
-    // and behind a track call on another stream, which may still read them
-    HIP_TRY(p, wait_behind(s, p->track_stream, p->track_done));
+    hipStream_t s;
+    if (int rc = stage_begin(p, ST_MATCH, stream, 0u, &s)) return rc;  // reads no other stage's results
     if (mfma && !i8) {
         {
             LaunchScope ls(p, s, KID_DESC_EXPAND);
@@ -2117,20 +2180,15 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
         hipLaunchKernelGGL(k_match, dim3(n_frames - 1u, (unsigned)((cap + 64u * kMatchQ - 1u) / (64u * kMatchQ))), dim3(64), 0, s, p->d_counts,
                            p->d_desc, (uint32_t)cap, p->d_matches);
     }
-    HIP_TRY(p, hipGetLastError());
-    HIP_TRY(p, hipEventRecord(p->match_done, s));
-    p->match_stream = s;
-    p->last_stream = s;
-    p->match_seq = p->batch_seq;
-    p->match_set = p->cur_set;
-    p->match_frames = n_frames;
+    if (int rc = stage_end(p, ST_MATCH, s, n_frames)) return rc;
+    p->last_stream = s;  // the matcher and the verifiers move the batch's stream (orb_batch_sync, orb_match_read); guided and track calls do not
     return ORB_OK;
 }
 
 int orb_match_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
     if (!p || !dst) return ORB_EINVAL;
     if (!p->d_matches || frame + 1u >= p->last_batch) return fail(p, ORB_EINVAL, "match_read: no matches for frame %u", frame);
-    if (int rc = orb_batch_sync(p)) return rc;
+    if (int rc = orb_batch_sync(p)) return rc;  // the batch's stream (the matcher moved it to its own), not the matcher's event
     const size_t cap = p->cfg.max_features;
     if (n > cap) n = cap;
     static_assert(sizeof(OrbMatch) == sizeof(MatchRecord), "OrbMatch layout");
@@ -2149,11 +2207,11 @@ struct VerifierKind {
     uint32_t seed_salt;           // the draw stream's seed is lowbias32(seed ^ seed_salt)
     void (*score)(VerifyArgs);
     void (*refine)(VerifyArgs);
-    bool has_readers;             // guided and track calls read its results (on any stream): a call waits behind them
+    StageId stage;
     bool profiled;                // launches under LaunchScope (KID_VERIFY_*)
 };
-const VerifierKind kHomography = {"verify_consecutive", "verify_read", 0u, k_verify_score, k_verify_refine, true, true};
-const VerifierKind kEpipolar = {"verify_epipolar", "verify_epipolar_read", kEpiSeedSalt, k_epi_score, k_epi_refine, false, false};
+const VerifierKind kHomography = {"verify_consecutive", "verify_read", 0u, k_verify_score, k_verify_refine, ST_VERIFY, true};
+const VerifierKind kEpipolar = {"verify_epipolar", "verify_epipolar_read", kEpiSeedSalt, k_epi_score, k_epi_refine, ST_EPI, false};
 
 int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
     OrbVerifyParams v{};
@@ -2163,41 +2221,21 @@ int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uin
         return fail(p, ORB_EINVAL, "%s: hypotheses must be 0..%u and max_distance 0..256", kind.name, kVerifyMaxHyp);
     if (!(std::isfinite(v.ratio) && v.ratio >= 0.0f) || !(std::isfinite(v.inlier_px) && v.inlier_px >= 0.0f))
         return fail(p, ORB_EINVAL, "%s: ratio and inlier_px must be finite and >= 0", kind.name);
-    if (!p->match_seq || p->match_seq != p->batch_seq)
-        return fail(p, ORB_ESTATE, "%s: no orb_match_consecutive since the last batch", kind.name);
-    if (p->match_set != p->cur_set)
-        return fail(p, ORB_ESTATE, "%s: the output set changed since orb_match_consecutive", kind.name);
-    if (n_frames < 2u || n_frames > p->match_frames)
-        return fail(p, ORB_EINVAL, "%s: need 2..%u frames (the matched ones)", kind.name, p->match_frames);
+    const Stage& m = p->stage[ST_MATCH];
+    if (!stage_fresh(p, m))  // said in two ways: the batch first, then the output set
+        return fail(p, ORB_ESTATE, !m.extent || m.seq != p->batch_seq ? "%s: no orb_match_consecutive since the last batch"
+                                                                      : "%s: the output set changed since orb_match_consecutive", kind.name);
+    if (n_frames < 2u || n_frames > m.extent)
+        return fail(p, ORB_EINVAL, "%s: need 2..%u frames (the matched ones)", kind.name, m.extent);
     if (!v.hypotheses) v.hypotheses = 512u;
     if (!v.max_distance) v.max_distance = 64u;
     if (v.ratio == 0.0f) v.ratio = 0.8f;
     if (v.inlier_px == 0.0f) v.inlier_px = 3.0f;
     HIP_TRY(p, hipSetDevice(p->device));
-    const size_t cap = p->cfg.max_features, B = p->max_batch;
-    if (!st.rec) {  // all six or none: a failure frees what was allocated, so the next call allocates again
-        void* buf[6] = {};
-        const size_t bytes[6] = {B * cap * sizeof(float4), B * cap * sizeof(uint32_t), B * sizeof(uint32_t),
-                                 B * kVerifyMaxHyp * sizeof(unsigned long long), B * sizeof(OrbPairModel), B * cap};
-        if (int rc = alloc_all_or_none(p, kind.name, 6, bytes, buf)) return rc;
-        st.rec = static_cast<float4*>(buf[0]);
-        st.cand = static_cast<uint32_t*>(buf[1]);
-        st.n = static_cast<uint32_t*>(buf[2]);
-        st.keys = static_cast<unsigned long long*>(buf[3]);
-        st.model = static_cast<uint32_t*>(buf[4]);
-        st.mask = static_cast<uint8_t*>(buf[5]);
-    }
-    if (!st.done) HIP_TRY(p, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
-    // the matches come from the matcher's stream; the buffers are this verifier's last call's, which may run on another one
-    HIP_TRY(p, wait_behind(s, p->match_stream, p->match_done));
-    HIP_TRY(p, wait_behind(s, st.stream, st.done));
-    if (kind.has_readers) {
-        // and behind a guided match on another stream, which may still read the models this call overwrites
-        HIP_TRY(p, wait_behind(s, p->guide_stream, p->guide_done));
-        // and behind a track call on another stream, which may still read the inlier bytes
-        HIP_TRY(p, wait_behind(s, p->track_stream, p->track_done));
-    }
+    const size_t cap = p->cfg.max_features;
+    if (int rc = alloc_all_or_none(p, kind.stage, kind.name)) return rc;
+    hipStream_t s;
+    if (int rc = stage_begin(p, kind.stage, stream, 1u << ST_MATCH, &s)) return rc;  // the matches come from the matcher's stream
     // GV-2: coordinates centred on the level-0 image and scaled by 2 / max(W, H)
     const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
     VerifyArgs a{};
@@ -2229,20 +2267,22 @@ int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uin
     launch(KID_VERIFY_GATHER, k_verify_gather, dim3(pairs));  // EP-1: GV-1 and GV-2 serve both verifiers
     launch(KID_VERIFY_SCORE, kind.score, dim3(pairs, (v.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg));
     launch(KID_VERIFY_REFINE, kind.refine, dim3(pairs));
-    HIP_TRY(p, hipGetLastError());
-    HIP_TRY(p, hipEventRecord(st.done, s));
-    st.stream = s;
-    st.pairs = pairs;
-    p->last_stream = s;
+    // The batch and output set stage_end records are the matcher's, which this call read: stage_fresh(p, m) above says they are the
+    // same.  Guided and track calls check them before they read the homography verifier's models and inlier bytes; the epipolar
+    // verifier's are recorded too and read by nobody.
+    if (int rc = stage_end(p, kind.stage, s, pairs)) return rc;
+    p->last_stream = s;  // as the matcher does
     return ORB_OK;
 }
 
 int read_verifier(OrbProgram* p, const VerifierKind& kind, const VerifierState& st, uint32_t pair, OrbPairModel* model, uint8_t* inlier,
                      size_t n) {
-    if (!st.pairs) return fail(p, ORB_ESTATE, "%s before %s", kind.read_name, kind.name);
-    if (pair >= st.pairs || (!inlier && n)) return fail(p, ORB_EINVAL, "%s: pair %u of %u, or inlier is NULL", kind.read_name, pair, st.pairs);
+    const Stage& last = p->stage[kind.stage];
+    if (!last.extent) return fail(p, ORB_ESTATE, "%s before %s", kind.read_name, kind.name);
+    if (pair >= last.extent || (!inlier && n))
+        return fail(p, ORB_EINVAL, "%s: pair %u of %u, or inlier is NULL", kind.read_name, pair, last.extent);
     HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(st.done));
+    HIP_TRY(p, hipEventSynchronize(last.done));
     const size_t cap = p->cfg.max_features;
     if (n > cap) n = cap;
     static_assert(sizeof(OrbPairModel) == kVerifyModelWords * sizeof(uint32_t) && sizeof(OrbVerifyParams) == 32, "verify layouts");
@@ -2256,11 +2296,7 @@ int read_verifier(OrbProgram* p, const VerifierKind& kind, const VerifierState& 
 extern "C" {
 
 int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
-    if (!p) return ORB_EINVAL;
-    if (int rc = run_verifier(p, kHomography, p->verify, n_frames, params, stream)) return rc;
-    p->verify.seq = p->match_seq;  // what guided and track calls check before they read the models and the inlier bytes
-    p->verify.set = p->match_set;
-    return ORB_OK;
+    return p ? run_verifier(p, kHomography, p->verify, n_frames, params, stream) : ORB_EINVAL;
 }
 
 int orb_verify_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
@@ -2289,14 +2325,14 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     if ((g.source == ORB_GUIDE_HOST) != (models_host != nullptr))
         return fail(p, ORB_EINVAL, "match_guided: models_host is required with ORB_GUIDE_HOST and only then");
     if (g.source == ORB_GUIDE_VERIFIED) {
-        if (!p->verify.pairs || p->verify.seq != p->batch_seq || p->verify.set != p->cur_set)
-            return fail(p, ORB_ESTATE, "match_guided: no orb_verify_consecutive of the current batch and output set");
-        if (n_frames - 1u > p->verify.pairs)
-            return fail(p, ORB_EINVAL, "match_guided: %u pairs, the last verification has %u", n_frames - 1u, p->verify.pairs);
+        const Stage& v = p->stage[ST_VERIFY];
+        if (!stage_fresh(p, v)) return fail(p, ORB_ESTATE, "match_guided: no orb_verify_consecutive of the current batch and output set");
+        if (n_frames - 1u > v.extent)
+            return fail(p, ORB_EINVAL, "match_guided: %u pairs, the last verification has %u", n_frames - 1u, v.extent);
     }
     if (g.radius_px == 0.0f) g.radius_px = 16.0f;
     HIP_TRY(p, hipSetDevice(p->device));
-    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    const size_t cap = p->cfg.max_features;
     const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
     if (p->guide_cell < 0) {  // the smallest cell (8, or TINYORB_GUIDE_CELL: a power of two 1..256) that keeps the frame within kGuideMaxCells
         int sh = 3;
@@ -2307,35 +2343,13 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
         while ((size_t)((W + (1u << sh) - 1u) >> sh) * ((H + (1u << sh) - 1u) >> sh) > kGuideMaxCells) sh++;
         p->guide_cell = sh;
     }
-    if (!p->d_gsrec) {  // all or none: a failure frees what was allocated, so the next call allocates again
-        void* buf[5] = {};
-        const size_t bytes[5] = {B * cap * sizeof(uint4), B * cap * 2u * sizeof(uint4), B * (kGuideMaxCells + 1u) * sizeof(uint32_t),
-                                 B * cap * sizeof(MatchRecord), B * 9u * sizeof(float)};
-        if (int rc = alloc_all_or_none(p, "match_guided", 5, bytes, buf)) return rc;
-        void* h = nullptr;
-        const hipError_t e = hipHostMalloc(&h, B * 9u * sizeof(float), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            for (int j = 0; j < 5; j++) (void)hipFree(buf[j]);
-            return fail(p, ORB_EHIP, "match_guided: hipHostMalloc failed: %s", hipGetErrorString(e));
-        }
-        p->d_gsdesc = static_cast<uint4*>(buf[1]);
-        p->d_gcell = static_cast<uint32_t*>(buf[2]);
-        p->d_gmatch = static_cast<MatchRecord*>(buf[3]);
-        p->d_gmodel = static_cast<float*>(buf[4]);
-        p->h_gmodel = static_cast<float*>(h);
-        p->d_gsrec = static_cast<uint4*>(buf[0]);
-    }
-    if (!p->guide_done) HIP_TRY(p, hipEventCreateWithFlags(&p->guide_done, hipEventDisableTiming));
-    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
-    // the models come from the last verification; the buffers are the last guided call's, which may run on another stream
-    HIP_TRY(p, wait_behind(s, p->verify.stream, p->verify.done));
-    HIP_TRY(p, wait_behind(s, p->guide_stream, p->guide_done));
-    // and behind a track call on another stream, which may still read the records this call overwrites
-    HIP_TRY(p, wait_behind(s, p->track_stream, p->track_done));
+    if (int rc = alloc_all_or_none(p, ST_GUIDE, "match_guided")) return rc;
+    hipStream_t s;
+    // the models come from the last verification (waited for whatever the source is)
+    if (int rc = stage_begin(p, ST_GUIDE, stream, 1u << ST_VERIFY, &s)) return rc;
     const uint32_t pairs = n_frames - 1u;
     if (g.source == ORB_GUIDE_HOST) {  // through the pinned staging buffer, once the previous call's copy out of it is done
-        if (p->guide_stream) HIP_TRY(p, hipEventSynchronize(p->guide_done));
+        if (p->stage[ST_GUIDE].stream) HIP_TRY(p, hipEventSynchronize(p->stage[ST_GUIDE].done));
         memcpy(p->h_gmodel, models_host, (size_t)pairs * 9u * sizeof(float));
         HIP_TRY(p, hipMemcpyAsync(p->d_gmodel, p->h_gmodel, (size_t)pairs * 9u * sizeof(float), hipMemcpyHostToDevice, s));
     }
@@ -2361,20 +2375,16 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     hipLaunchKernelGGL(k_guide_bin, dim3(n_frames), dim3(kGuideBinThreads), 0, s, a);
     hipLaunchKernelGGL(k_guide_search, dim3(pairs * (unsigned)((cap + kGuideSearchThreads - 1u) / kGuideSearchThreads)),
                        dim3(kGuideSearchThreads), 0, s, a);
-    HIP_TRY(p, hipGetLastError());
-    HIP_TRY(p, hipEventRecord(p->guide_done, s));
-    p->guide_stream = s;
-    p->guide_pairs = pairs;
-    p->guide_seq = p->batch_seq, p->guide_set = p->cur_set;
-    return ORB_OK;
+    return stage_end(p, ST_GUIDE, s, pairs);  // p->last_stream stays: guided results are read through the stage's event
 }
 
 int orb_match_guided_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
     if (!p) return ORB_EINVAL;
-    if (!p->guide_pairs) return fail(p, ORB_ESTATE, "match_guided_read before match_guided");
-    if (frame >= p->guide_pairs || (!dst && n)) return fail(p, ORB_EINVAL, "match_guided_read: frame %u of %u, or dst is NULL", frame, p->guide_pairs);
+    const Stage& last = p->stage[ST_GUIDE];
+    if (!last.extent) return fail(p, ORB_ESTATE, "match_guided_read before match_guided");
+    if (frame >= last.extent || (!dst && n)) return fail(p, ORB_EINVAL, "match_guided_read: frame %u of %u, or dst is NULL", frame, last.extent);
     HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(p->guide_done));
+    HIP_TRY(p, hipEventSynchronize(last.done));
     const size_t cap = p->cfg.max_features;
     if (n > cap) n = cap;
     static_assert(sizeof(OrbGuideParams) == 32, "OrbGuideParams layout");
@@ -2398,20 +2408,21 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
     if (n_frames < 2u || n_frames > p->last_batch || n_frames > kTrackMaxFrames)
         return fail(p, ORB_EINVAL, "track_consecutive: need 2..%u frames of the last batch", std::min(p->last_batch, kTrackMaxFrames));
     if (p->cfg.max_features > (1u << 23)) return fail(p, ORB_EINVAL, "track_consecutive: max_features must be <= 2^23");
-    uint32_t pairs_avail = 0;
-    if (t.source == ORB_TRACK_VERIFIED) {
-        if (!p->verify.pairs || p->verify.seq != p->batch_seq || p->verify.set != p->cur_set || p->match_seq != p->verify.seq ||
-            p->match_set != p->verify.set)
+    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_VERIFY], &gd = p->stage[ST_GUIDE];
+    uint32_t pairs_avail = 0, reads = 0;  // reads: the stages whose results the links come from
+    if (t.source == ORB_TRACK_VERIFIED) {  // the inlier bytes and the matches they mark, which must be the ones the verification read
+        if (!stage_fresh(p, v) || m.seq != v.seq || m.set != v.set)
             return fail(p, ORB_ESTATE, "track_consecutive: no orb_verify_consecutive of the current batch, output set and matches");
-        pairs_avail = p->verify.pairs;
+        pairs_avail = v.extent;
+        reads = 1u << ST_MATCH | 1u << ST_VERIFY;
     } else if (t.source == ORB_TRACK_GUIDED) {
-        if (!p->guide_pairs || p->guide_seq != p->batch_seq || p->guide_set != p->cur_set)
-            return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_guided of the current batch and output set");
-        pairs_avail = p->guide_pairs;
+        if (!stage_fresh(p, gd)) return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_guided of the current batch and output set");
+        pairs_avail = gd.extent;
+        reads = 1u << ST_GUIDE;
     } else {
-        if (!p->match_seq || p->match_seq != p->batch_seq || p->match_set != p->cur_set)
-            return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_consecutive of the current batch and output set");
-        pairs_avail = p->match_frames - 1u;
+        if (!stage_fresh(p, m)) return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_consecutive of the current batch and output set");
+        pairs_avail = m.extent - 1u;
+        reads = 1u << ST_MATCH;
     }
     if (n_frames - 1u > pairs_avail)
         return fail(p, ORB_EINVAL, "track_consecutive: %u pairs, the source has %u", n_frames - 1u, pairs_avail);
@@ -2425,28 +2436,9 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
         const char* e = getenv("TINYORB_TRACK_GLOBAL_KEYS");
         p->track_global_keys = (e && atoi(e) != 0) ? 1 : 0;
     }
-    if (!p->d_track) {  // all or none: a failure frees what was allocated, so the next call allocates again
-        void* buf[8] = {};
-        const size_t bytes[8] = {B * cap * sizeof(uint32_t), B * cap * sizeof(uint32_t), B * cap * sizeof(uint32_t),
-                                 2u * B * cap * sizeof(uint4), B * sizeof(uint32_t), B * B * sizeof(uint32_t),
-                                 B * sizeof(OrbTrackFrame), B * cap * sizeof(OrbTrack)};
-        if (int rc = alloc_all_or_none(p, "track_consecutive", 8, bytes, buf)) return rc;
-        p->d_tkeys = static_cast<uint32_t*>(buf[0]);
-        p->d_tprev = static_cast<uint32_t*>(buf[1]);
-        p->d_tnext = static_cast<uint32_t*>(buf[2]);
-        p->d_tptr = static_cast<uint4*>(buf[3]);
-        p->d_tlinks = static_cast<uint32_t*>(buf[4]);
-        p->d_tshared = static_cast<uint32_t*>(buf[5]);
-        p->d_tframe = static_cast<uint32_t*>(buf[6]);
-        p->d_track = static_cast<uint4*>(buf[7]);
-    }
-    if (!p->track_done) HIP_TRY(p, hipEventCreateWithFlags(&p->track_done, hipEventDisableTiming));
-    hipStream_t s = stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
-    // the links come from the source's last call; the buffers are the last track call's, which may run on another stream
-    if (t.source != ORB_TRACK_GUIDED) HIP_TRY(p, wait_behind(s, p->match_stream, p->match_done));
-    if (t.source == ORB_TRACK_VERIFIED) HIP_TRY(p, wait_behind(s, p->verify.stream, p->verify.done));
-    if (t.source == ORB_TRACK_GUIDED) HIP_TRY(p, wait_behind(s, p->guide_stream, p->guide_done));
-    HIP_TRY(p, wait_behind(s, p->track_stream, p->track_done));
+    if (int rc = alloc_all_or_none(p, ST_TRACK, "track_consecutive")) return rc;
+    hipStream_t s;
+    if (int rc = stage_begin(p, ST_TRACK, stream, reads, &s)) return rc;
     TrackArgs a{};
     a.counts = p->d_counts;
     a.cap = (uint32_t)cap;
@@ -2489,19 +2481,16 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
     }
     hipLaunchKernelGGL(k_track_hist, dim3(n_frames), dim3(kTrackHistThreads), 0, s, a);
     hipLaunchKernelGGL(k_track_key, dim3(1), dim3(kTrackKeyThreads), 0, s, a);
-    HIP_TRY(p, hipGetLastError());
-    HIP_TRY(p, hipEventRecord(p->track_done, s));
-    p->track_stream = s;
-    p->track_frames = n_frames;
-    return ORB_OK;
+    return stage_end(p, ST_TRACK, s, n_frames);  // p->last_stream stays, as after a guided call
 }
 
 int orb_track_read(OrbProgram* p, uint32_t frame, OrbTrack* dst, size_t n) {
     if (!p) return ORB_EINVAL;
-    if (!p->track_frames) return fail(p, ORB_ESTATE, "track_read before track_consecutive");
-    if (frame >= p->track_frames || (!dst && n)) return fail(p, ORB_EINVAL, "track_read: frame %u of %u, or dst is NULL", frame, p->track_frames);
+    const Stage& last = p->stage[ST_TRACK];
+    if (!last.extent) return fail(p, ORB_ESTATE, "track_read before track_consecutive");
+    if (frame >= last.extent || (!dst && n)) return fail(p, ORB_EINVAL, "track_read: frame %u of %u, or dst is NULL", frame, last.extent);
     HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(p->track_done));
+    HIP_TRY(p, hipEventSynchronize(last.done));
     const size_t cap = p->cfg.max_features;
     if (n > cap) n = cap;
     static_assert(sizeof(OrbTrack) == 16 && sizeof(OrbTrackFrame) == 32 && sizeof(OrbTrackParams) == 32, "track layouts");
@@ -2511,11 +2500,12 @@ int orb_track_read(OrbProgram* p, uint32_t frame, OrbTrack* dst, size_t n) {
 
 int orb_track_frames(OrbProgram* p, OrbTrackFrame* dst, size_t n) {
     if (!p) return ORB_EINVAL;
-    if (!p->track_frames) return fail(p, ORB_ESTATE, "track_frames before track_consecutive");
+    const Stage& last = p->stage[ST_TRACK];
+    if (!last.extent) return fail(p, ORB_ESTATE, "track_frames before track_consecutive");
     if (!dst && n) return fail(p, ORB_EINVAL, "track_frames: dst is NULL");
     HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(p->track_done));
-    if (n > p->track_frames) n = p->track_frames;
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    if (n > last.extent) n = last.extent;
     if (n) HIP_TRY(p, hipMemcpy(dst, p->d_tframe, n * sizeof(OrbTrackFrame), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
