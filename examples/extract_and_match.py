@@ -47,3 +47,13 @@ with orb.OrbProgram(cfg) as prog:  # == OrbProgram { config, .. }.init() in the 
               orb.ORB_VERIFY_MINIMAL: "minimal model"}[int(model["status"])]
     print("frame 0 -> 1 verified: %d candidates, %d inliers (%s), H =\n%s"
           % (int(model["candidates"]), int(model["inliers"]), status, model["h"].reshape(3, 3)))
+
+    # --- epipolar verification and the band search along its lines (DESIGN.md sections 16 and 18) --------------------------
+    prog.verify_epipolar(2)
+    fmodel, _ = prog.verify_epipolar_read(0, 0)
+    if int(fmodel["status"]) in (orb.ORB_VERIFY_OK, orb.ORB_VERIFY_MINIMAL):
+        prog.match_epipolar(2, band_px=2.0, radius_px=32.0)  # within 2 px of the epipolar line, 32 px around the keypoint itself
+        band = prog.match_epipolar_read(0, int(counts[0]))
+        print("frame 0 -> 1 along the epipolar lines: %d keypoints have a candidate" % int((band["index"] != orb.ORB_MATCH_NONE).sum()))
+    else:
+        print("frame 0 -> 1: no fundamental matrix (status %d), no band search" % int(fmodel["status"]))

@@ -458,6 +458,46 @@ int orb_match_guided(OrbProgram *p, uint32_t n_frames, const OrbGuideParams *par
  * ORB_ESTATE before any call, ORB_EINVAL for a frame outside its pairs. */
 int orb_match_guided_read(OrbProgram *p, uint32_t frame, OrbMatch *dst, size_t n);
 
+/* ---- epipolar-band guided matching, "search for triangulation" (NOT in the reference; definition EB-1..EB-6 in DESIGN.md
+ * section 18) ----
+ * For every consecutive pair (f, f+1) of the last batch: each stored keypoint i of frame f is sent to its epipolar line in
+ * frame f+1 by the pair's row-major fundamental matrix F (x2^T F x1 = 0, level-0 coordinates of orb_corner_level0_xy, binary32,
+ * no fused operations, in the order a0 = (f0 x + f1 y) + f2, a1 = (f3 x + f4 y) + f5, a2 = (f6 x + f7 y) + f8,
+ * n2 = a0 a0 + a1 a1, t = (d d) n2) and matched against the stored keypoints j of frame f+1 with r = (a0 x_j + a1 y_j) + a2,
+ * r r <= t -- within d pixels of the line, tested without a division or a square root -- and, with radius_px R > 0,
+ * fabsf(x_j - x) <= R and fabsf(y_j - y) <= R around the query's OWN position (and, with octave_window n > 0,
+ * |octave_j - octave_i| < n) only.  The record is orb_match_consecutive's restricted to that set, as orb_match_guided's is to
+ * its window; ORB_MATCH_NONE / 0xffff / 0xffff without a target or without a line (no model, a0, a1, a2 or t not finite, or
+ * n2 < 2^-64: the query is at the epipole, or F is zero).  Queries past a frame's stored keypoints get ORB_MATCH_NONE records.
+ * With ORB_BAND_HOST, a band that covers the frame (e.g. 1e6) and radius_px 0, every query that has a line gets
+ * orb_match_consecutive's record. */
+typedef struct {              /* zero-initialised = the defaults */
+    uint32_t source;          /* ORB_BAND_VERIFIED (0), ORB_BAND_HOST (1) */
+    float band_px;            /* half-width d of the band around the line, level-0 pixels, finite, >= 0 (0: 2.0) */
+    float radius_px;          /* window half-size R around the query's OWN position, finite, >= 0 (0: no window, the whole line) */
+    uint32_t octave_window;   /* as OrbGuideParams */
+    uint32_t flags;           /* ORB_BAND_SCALE */
+    uint32_t reserved[3];     /* must be 0 (ORB_EINVAL otherwise) */
+} OrbBandParams;              /* 32 bytes */
+
+#define ORB_BAND_VERIFIED 0u  /* h (= F) of the pair's record of the last orb_verify_epipolar, status OK or MINIMAL */
+#define ORB_BAND_HOST 1u      /* models_host: (n_frames - 1) x 9 floats, row-major F, read during the call */
+#define ORB_BAND_SCALE 1u     /* d and R multiplied by 2^octave_i (exact) */
+
+/* Matches the pairs (f, f+1), f in [0, n_frames - 1), of the last batch (params NULL: the defaults).  ORB_EINVAL when n_frames is
+ * not 2..frames of the last batch, max_features > 2^23, models_host is NULL with ORB_BAND_HOST or not NULL with
+ * ORB_BAND_VERIFIED, or a parameter is out of range; with ORB_BAND_VERIFIED, ORB_ESTATE when the last orb_verify_epipolar was
+ * not of the current batch and output set, ORB_EINVAL when n_frames - 1 exceeds its pairs.  Asynchronous on `stream` (NULL: as
+ * orb_match_guided chooses; the call does not change it), ordered behind the last epipolar verification and the last call of
+ * its own when they ran on another stream; orb_verify_epipolar waits for such a call on another stream before it overwrites
+ * the models.  ONE result buffer per program (allocated by the first call), of its own: the matcher's, the verifiers', the
+ * guided call's and the track call's results are never written.  TINYORB_GUIDE_CELL sets the cell size of this call's grid
+ * too, and changes no record. */
+int orb_match_epipolar(OrbProgram *p, uint32_t n_frames, const OrbBandParams *params, const float *models_host, void *stream);
+/* Copy up to n records of the queries of frame `frame` of the last orb_match_epipolar call to the host (synchronises);
+ * ORB_ESTATE before any call, ORB_EINVAL for a frame outside its pairs. */
+int orb_match_epipolar_read(OrbProgram *p, uint32_t frame, OrbMatch *dst, size_t n);
+
 /* ---- feature tracks and keyframes (NOT in the reference; definition TK-1..TK-5 in DESIGN.md section 15) ----
  * Over the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: query i of frame f links to target j of frame f+1 by the
  * source's record (VERIFIED: the matcher's record where the last verification's inlier byte is 1; GUIDED / MATCHED: the last

@@ -29,6 +29,7 @@
 #include "orb_kernels_verify.h"
 #include "orb_kernels_epipolar.h"
 #include "orb_kernels_guide.h"
+#include "orb_kernels_band.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -63,13 +64,14 @@ struct ProfSpan {
 // The stages that run after extraction.  Each owns ONE set of buffers per program, shared by both output sets and by whatever stream
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, which the entry point names; and the stages that read what it overwrites, kReadersOf[stage].
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_COUNT };
 const uint32_t kReadersOf[ST_COUNT] = {
     1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it)
     1u << ST_GUIDE | 1u << ST_TRACK,                  // verify: verify.model (guided, ORB_GUIDE_VERIFIED), verify.mask (track, ORB_TRACK_VERIFIED)
-    0u,                                               // epi: its results are only read back by the host
+    1u << ST_BAND,                                    // epi: epi.model (band, ORB_BAND_VERIFIED)
     1u << ST_TRACK,                                   // guide: d_gmatch (track, ORB_TRACK_GUIDED)
     0u,                                               // track: read back by the host
+    0u,                                               // band: d_bmatch is read back by the host
 };
 
 // The last call of a stage
@@ -157,6 +159,13 @@ struct OrbProgram {
     float* d_gmodel = nullptr;            // [max_batch][9] the caller's models (ORB_GUIDE_HOST)
     float* h_gmodel = nullptr;            // pinned staging of the same
     int guide_cell = -1;                  // log2 of the grid's cell size (TINYORB_GUIDE_CELL); -1 until the first call
+    // orb_match_epipolar (orb_kernels_band.h): its own copies of the guided call's buffers, on the same grid (guide_cell)
+    uint4* d_bsrec = nullptr;
+    uint4* d_bsdesc = nullptr;
+    uint32_t* d_bcell = nullptr;
+    MatchRecord* d_bmatch = nullptr;      // [max_batch][max_features] results
+    float* d_bmodel = nullptr;            // [max_batch][9] the caller's fundamental matrices (ORB_BAND_HOST)
+    float* h_bmodel = nullptr;            // pinned staging of the same
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -315,6 +324,14 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         add(&p->d_tshared, B * B * sizeof(uint32_t));
         add(&p->d_tframe, B * sizeof(OrbTrackFrame));
         add(&p->d_track, B * cap * sizeof(OrbTrack));
+        break;
+    case ST_BAND:
+        add(&p->d_bsrec, B * cap * sizeof(uint4));
+        add(&p->d_bsdesc, B * cap * 2u * sizeof(uint4));
+        add(&p->d_bcell, B * (kGuideMaxCells + 1u) * sizeof(uint32_t));
+        add(&p->d_bmatch, B * cap * sizeof(MatchRecord));
+        add(&p->d_bmodel, B * 9u * sizeof(float));
+        add(&p->h_bmodel, B * 9u * sizeof(float), true);
         break;
     }
     return n;
@@ -2268,8 +2285,8 @@ int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uin
     launch(KID_VERIFY_SCORE, kind.score, dim3(pairs, (v.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg));
     launch(KID_VERIFY_REFINE, kind.refine, dim3(pairs));
     // The batch and output set stage_end records are the matcher's, which this call read: stage_fresh(p, m) above says they are the
-    // same.  Guided and track calls check them before they read the homography verifier's models and inlier bytes; the epipolar
-    // verifier's are recorded too and read by nobody.
+    // same.  Guided and track calls check them before they read the homography verifier's models and inlier bytes, the band
+    // call before it reads the epipolar verifier's models.
     if (int rc = stage_end(p, kind.stage, s, pairs)) return rc;
     p->last_stream = s;  // as the matcher does
     return ORB_OK;
@@ -2289,6 +2306,20 @@ int read_verifier(OrbProgram* p, const VerifierKind& kind, const VerifierState& 
     if (model) HIP_TRY(p, hipMemcpy(model, st.model + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
     if (n) HIP_TRY(p, hipMemcpy(inlier, st.mask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
     return ORB_OK;
+}
+
+// The grid of the guided and the band search, fixed by the program's first such call: the smallest cell (8, or TINYORB_GUIDE_CELL: a
+// power of two 1..256) that keeps the frame within kGuideMaxCells
+void guide_grid(OrbProgram* p) {
+    if (p->guide_cell >= 0) return;
+    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    int sh = 3;
+    if (const char* e = getenv("TINYORB_GUIDE_CELL")) {
+        const int c = atoi(e);
+        if (c >= 1 && c <= 256 && (c & (c - 1)) == 0) sh = __builtin_ctz((unsigned)c);
+    }
+    while ((size_t)((W + (1u << sh) - 1u) >> sh) * ((H + (1u << sh) - 1u) >> sh) > kGuideMaxCells) sh++;
+    p->guide_cell = sh;
 }
 
 }  // namespace
@@ -2334,15 +2365,7 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
     const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
-    if (p->guide_cell < 0) {  // the smallest cell (8, or TINYORB_GUIDE_CELL: a power of two 1..256) that keeps the frame within kGuideMaxCells
-        int sh = 3;
-        if (const char* e = getenv("TINYORB_GUIDE_CELL")) {
-            const int c = atoi(e);
-            if (c >= 1 && c <= 256 && (c & (c - 1)) == 0) sh = __builtin_ctz((unsigned)c);
-        }
-        while ((size_t)((W + (1u << sh) - 1u) >> sh) * ((H + (1u << sh) - 1u) >> sh) > kGuideMaxCells) sh++;
-        p->guide_cell = sh;
-    }
+    guide_grid(p);
     if (int rc = alloc_all_or_none(p, ST_GUIDE, "match_guided")) return rc;
     hipStream_t s;
     // the models come from the last verification (waited for whatever the source is)
@@ -2389,6 +2412,92 @@ int orb_match_guided_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n
     if (n > cap) n = cap;
     static_assert(sizeof(OrbGuideParams) == 32, "OrbGuideParams layout");
     if (n) HIP_TRY(p, hipMemcpy(dst, p->d_gmatch + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_match_epipolar(OrbProgram* p, uint32_t n_frames, const OrbBandParams* params, const float* models_host, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbBandParams g{};
+    if (params) g = *params;
+    if (g.reserved[0] || g.reserved[1] || g.reserved[2]) return fail(p, ORB_EINVAL, "match_epipolar: reserved words must be 0");
+    if (g.source > ORB_BAND_HOST || (g.flags & ~ORB_BAND_SCALE))
+        return fail(p, ORB_EINVAL, "match_epipolar: unknown source %u or flags 0x%x", g.source, g.flags);
+    if (!(std::isfinite(g.band_px) && g.band_px >= 0.0f) || !(std::isfinite(g.radius_px) && g.radius_px >= 0.0f))
+        return fail(p, ORB_EINVAL, "match_epipolar: band_px and radius_px must be finite and >= 0");
+    if (n_frames < 2u || n_frames > p->last_batch)
+        return fail(p, ORB_EINVAL, "match_epipolar: need 2..%u frames of the last batch", p->last_batch);
+    if (p->cfg.max_features > (1u << 23)) return fail(p, ORB_EINVAL, "match_epipolar: max_features must be <= 2^23");
+    if ((g.source == ORB_BAND_HOST) != (models_host != nullptr))
+        return fail(p, ORB_EINVAL, "match_epipolar: models_host is required with ORB_BAND_HOST and only then");
+    if (g.source == ORB_BAND_VERIFIED) {
+        const Stage& v = p->stage[ST_EPI];
+        if (!stage_fresh(p, v)) return fail(p, ORB_ESTATE, "match_epipolar: no orb_verify_epipolar of the current batch and output set");
+        if (n_frames - 1u > v.extent)
+            return fail(p, ORB_EINVAL, "match_epipolar: %u pairs, the last epipolar verification has %u", n_frames - 1u, v.extent);
+    }
+    if (g.band_px == 0.0f) g.band_px = 2.0f;
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features;
+    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    guide_grid(p);
+    if (int rc = alloc_all_or_none(p, ST_BAND, "match_epipolar")) return rc;
+    hipStream_t s;
+    // the models come from the last epipolar verification (waited for whatever the source is, as the guided call does)
+    if (int rc = stage_begin(p, ST_BAND, stream, 1u << ST_EPI, &s)) return rc;
+    const uint32_t pairs = n_frames - 1u;
+    if (g.source == ORB_BAND_HOST) {  // through the pinned staging buffer, once the previous call's copy out of it is done
+        if (p->stage[ST_BAND].stream) HIP_TRY(p, hipEventSynchronize(p->stage[ST_BAND].done));
+        memcpy(p->h_bmodel, models_host, (size_t)pairs * 9u * sizeof(float));
+        HIP_TRY(p, hipMemcpyAsync(p->d_bmodel, p->h_bmodel, (size_t)pairs * 9u * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    GuideArgs bin{};  // k_guide_bin as it is, on this stage's buffers
+    bin.counts = p->d_counts;
+    bin.corners = p->d_corners;
+    bin.desc = p->d_desc;
+    bin.cap = (uint32_t)cap;
+    bin.shift = (uint32_t)p->guide_cell;
+    bin.gw = (W + (1u << bin.shift) - 1u) >> bin.shift;
+    bin.gh = (H + (1u << bin.shift) - 1u) >> bin.shift;
+    bin.srec = p->d_bsrec;
+    bin.sdesc = p->d_bsdesc;
+    bin.cell_start = p->d_bcell;
+    BandArgs a{};
+    a.counts = p->d_counts;
+    a.cap = (uint32_t)cap;
+    a.gw = bin.gw;
+    a.gh = bin.gh;
+    a.shift = bin.shift;
+    a.fw = (float)W;
+    a.fh = (float)H;
+    a.srec = p->d_bsrec;
+    a.sdesc = p->d_bsdesc;
+    a.cell_start = p->d_bcell;
+    a.pairs = pairs;
+    a.source = g.source;
+    a.vmodel = p->epi.model;
+    a.hmodel = p->d_bmodel;
+    a.band = g.band_px;
+    a.radius = g.radius_px;
+    a.octave_window = g.octave_window;
+    a.scale = (g.flags & ORB_BAND_SCALE) ? 1u : 0u;
+    a.out = p->d_bmatch;
+    hipLaunchKernelGGL(k_guide_bin, dim3(n_frames), dim3(kGuideBinThreads), 0, s, bin);
+    hipLaunchKernelGGL(k_band_search, dim3(pairs * (unsigned)((cap + kGuideSearchThreads - 1u) / kGuideSearchThreads)),
+                       dim3(kGuideSearchThreads), 0, s, a);
+    return stage_end(p, ST_BAND, s, pairs);  // p->last_stream stays, as after a guided call
+}
+
+int orb_match_epipolar_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
+    if (!p) return ORB_EINVAL;
+    const Stage& last = p->stage[ST_BAND];
+    if (!last.extent) return fail(p, ORB_ESTATE, "match_epipolar_read before match_epipolar");
+    if (frame >= last.extent || (!dst && n)) return fail(p, ORB_EINVAL, "match_epipolar_read: frame %u of %u, or dst is NULL", frame, last.extent);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    static_assert(sizeof(OrbBandParams) == 32, "OrbBandParams layout");
+    if (n) HIP_TRY(p, hipMemcpy(dst, p->d_bmatch + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

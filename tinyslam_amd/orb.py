@@ -48,6 +48,9 @@ ORB_VERIFY_MAX_HYPOTHESES = 4096
 # guided matching (orb_match_guided): where a pair's model comes from, and the flag of OrbGuideParams
 ORB_GUIDE_VERIFIED, ORB_GUIDE_IDENTITY, ORB_GUIDE_HOST = 0, 1, 2
 ORB_GUIDE_SCALE_RADIUS = 1
+# epipolar-band guided matching (orb_match_epipolar): where a pair's F comes from, and the flag of OrbBandParams
+ORB_BAND_VERIFIED, ORB_BAND_HOST = 0, 1
+ORB_BAND_SCALE = 1
 # feature tracks and keyframes (orb_track_consecutive): the link source, OrbTrack (16 B), OrbTrackFrame (32 B)
 ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
 TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
@@ -73,6 +76,7 @@ EXPORTS = [
     "orb_write_input_image_pinned", "orb_node_set_results", "orb_node_shard_result",
     "orb_verify_consecutive", "orb_verify_read", "orb_match_guided", "orb_match_guided_read",
     "orb_track_consecutive", "orb_track_read", "orb_track_frames", "orb_verify_epipolar", "orb_verify_epipolar_read",
+    "orb_match_epipolar", "orb_match_epipolar_read",
 ]
 
 
@@ -108,6 +112,12 @@ class _GuideParams(ctypes.Structure):
     """OrbGuideParams (32 bytes; zero fields = the defaults)"""
     _fields_ = [("source", ctypes.c_uint32), ("radius_px", ctypes.c_float), ("octave_window", ctypes.c_uint32),
                 ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+class _BandParams(ctypes.Structure):
+    """OrbBandParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("source", ctypes.c_uint32), ("band_px", ctypes.c_float), ("radius_px", ctypes.c_float),
+                ("octave_window", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
 class _TrackParams(ctypes.Structure):
@@ -193,6 +203,8 @@ def load_library(path=None):
     L.orb_verify_epipolar_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_match_guided.argtypes = [vp, u32, ctypes.POINTER(_GuideParams), vp, vp]
     L.orb_match_guided_read.argtypes = [vp, u32, vp, sz]
+    L.orb_match_epipolar.argtypes = [vp, u32, ctypes.POINTER(_BandParams), vp, vp]
+    L.orb_match_epipolar_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -582,6 +594,32 @@ class OrbProgram:
         """MATCH_DTYPE records of the queries of `frame` (the first min(n, max_features)) of the last match_guided -- synchronises."""
         out = np.zeros(min(n, self.config.max_features), dtype=MATCH_DTYPE)
         self._check(self._lib.orb_match_guided_read(self._handle(), frame, _ptr(out) if len(out) else None, len(out)))
+        return out
+
+    def match_epipolar(self, n_frames, source=ORB_BAND_VERIFIED, models=None, band_px=0.0, radius_px=0.0, octave_window=0, scale=False,
+                       stream=None, flags=0, reserved=(0, 0, 0)):
+        """Epipolar-band guided matching of the last batch (not in the reference): per pair
+        (f, f+1), f < n_frames - 1, every keypoint of f is sent to its epipolar line in f+1 by the pair's fundamental matrix -- the
+        last verify_epipolar's h (ORB_BAND_VERIFIED, pairs with status OK / MINIMAL only) or models[f] (ORB_BAND_HOST:
+        (n_frames - 1) x 9 or x 3 x 3 float32, x2^T F x1 = 0, read during the call) -- and matched against the keypoints of f+1
+        within band_px level-0 pixels of that line (0: 2.0), inside a window of radius_px around the keypoint's own position
+        (0: none) and, with octave_window n > 0, |octave difference| < n; `scale` multiplies band_px and radius_px by 2^octave of
+        the query.  Asynchronous on `stream` (None: as match_guided chooses).  `flags` and `reserved` are OR'ed / passed into
+        OrbBandParams as they are."""
+        prm = _BandParams(source, float(np.float32(band_px)), float(np.float32(radius_px)), octave_window,
+                          (ORB_BAND_SCALE if scale else 0) | flags, (ctypes.c_uint32 * 3)(*reserved))
+        m = None
+        if models is not None:
+            m = np.ascontiguousarray(models, dtype=np.float32)
+            if source == ORB_BAND_HOST and m.size < (n_frames - 1) * 9:
+                raise ValueError("models: need (n_frames - 1) x 9 floats, got %d" % m.size)
+        self._check(self._lib.orb_match_epipolar(self._handle(), n_frames, ctypes.byref(prm), _ptr(m) if m is not None else None,
+                                                 ctypes.c_void_p(stream) if stream else None))
+
+    def match_epipolar_read(self, frame, n):
+        """MATCH_DTYPE records of the queries of `frame` (the first min(n, max_features)) of the last match_epipolar -- synchronises."""
+        out = np.zeros(min(n, self.config.max_features), dtype=MATCH_DTYPE)
+        self._check(self._lib.orb_match_epipolar_read(self._handle(), frame, _ptr(out) if len(out) else None, len(out)))
         return out
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
