@@ -55,5 +55,11 @@ with orb.OrbProgram(cfg) as prog:  # == OrbProgram { config, .. }.init() in the 
         prog.match_epipolar(2, band_px=2.0, radius_px=32.0)  # within 2 px of the epipolar line, 32 px around the keypoint itself
         band = prog.match_epipolar_read(0, int(counts[0]))
         print("frame 0 -> 1 along the epipolar lines: %d keypoints have a candidate" % int((band["index"] != orb.ORB_MATCH_NONE).sum()))
+        # --- how the camera moved and where the points are; the intrinsics are the caller's ------------
+        prog.pose_consecutive(2, fx=500.0, fy=500.0, cx=(W - 1) / 2, cy=(H - 1) / 2)
+        pose, points = prog.pose_read(0, int(counts[0]))
+        good = (points["flags"] & orb.ORB_POINT_GOOD) != 0
+        print("frame 0 -> 1 pose: status %d, %d of %d inliers triangulated, R =\n%s\nt = %s"
+              % (int(pose["status"]), int(good.sum()), int(pose["inliers"]), pose["r"].reshape(3, 3), pose["t"]))
     else:
-        print("frame 0 -> 1: no fundamental matrix (status %d), no band search" % int(fmodel["status"]))
+        print("frame 0 -> 1: no fundamental matrix (status %d), no band search and no pose" % int(fmodel["status"]))

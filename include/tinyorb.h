@@ -498,6 +498,61 @@ int orb_match_epipolar(OrbProgram *p, uint32_t n_frames, const OrbBandParams *pa
  * ORB_ESTATE before any call, ORB_EINVAL for a frame outside its pairs. */
 int orb_match_epipolar_read(OrbProgram *p, uint32_t frame, OrbMatch *dst, size_t n);
 
+/* ---- relative pose and triangulation of the epipolar inliers (NOT in the reference; definition RP-1..RP-7 in DESIGN.md
+ * section 19) ----
+ * For every consecutive pair (f, f+1) of the last batch: the F of the last orb_verify_epipolar (status OK or MINIMAL) and the
+ * caller's pinhole intrinsics give the essential matrix E = K^T F K, scaled to sum(E^2) = 2; the baseline direction t is the row
+ * of I - E E^T with the largest diagonal entry, divided by that entry's square root; the two rotations are Cof(E) - [t]x E and
+ * Cof(E) + [t]x E (Horn's closed form), each taken to the nearest rotation by three steps R <- (R + Cof(R) / det R) / 2.  No SVD
+ * and no iteration whose length depends on the data.  Every query i whose epipolar inlier byte is 1, with its partner
+ * j = the matcher's index, is triangulated under the four candidates (Ra, t), (Ra, -t), (Rb, t), (Rb, -t): rays
+ * d = ((u - cx) / fx, (v - cy) / fy, 1), depths z1, z2 from the 2 x 2 normal equations of z1 R d1 - z2 d2 = -t, X = z1 d1.  A
+ * point is GOOD when both depths are finite and > 0 and X reprojects within max_reproj_px of the keypoint in frame f+1; it has
+ * PARALLAX when the cosine of the angle between its rays is below max_cos_parallax.  The candidate with the most good points
+ * wins (the first of equals).  Binary32 arithmetic in a fixed order, no fused operations: a CPU restatement gives the same bits.
+ * X2 = R X1 + t takes camera f's frame to camera f+1's; the scale of t is unobservable, so |t| = 1 and the points share it. */
+typedef struct {            /* zero-initialised is NOT valid: fx, fy must be > 0 */
+    float fx, fy, cx, cy;   /* pinhole intrinsics in orb_corner_level0_xy coordinates (literal mode: the mirrored frame) */
+    float max_reproj_px;    /* frame f+1 reprojection error a good point may have (0: 2.0); finite, >= 0 */
+    float max_cos_parallax; /* a point has parallax iff cos(angle between its rays) < this (0: 0.99998); in (0, 1] */
+    uint32_t min_good;      /* good points the winner needs (0: 8) */
+    uint32_t ambiguity_permille; /* AMBIGUOUS iff 1000*second >= this*best (0: 700); 1..1000 */
+} OrbPoseParams;            /* 32 bytes */
+
+#define ORB_POSE_OK 0u           /* R, t and the points can be used */
+#define ORB_POSE_NOMODEL 1u      /* no F (the epipolar status is FEW or DEGENERATE), or E, t or both rotations degenerate: all 0 */
+#define ORB_POSE_FEW 2u          /* fewer than 8 epipolar inliers (all 0), or the winner has fewer than min_good good points */
+#define ORB_POSE_AMBIGUOUS 3u    /* the runner-up explains nearly as many points */
+#define ORB_POSE_LOW_PARALLAX 4u /* fewer than half of the winner's good points have parallax: R holds, t and the depths do not */
+
+typedef struct {
+    float r[9];             /* row-major R, X2 = R X1 + t */
+    float t[3];             /* unit length (scale is unobservable) */
+    uint32_t inliers;       /* epipolar inliers considered */
+    uint32_t good;          /* of them: in front of both cameras and within max_reproj_px, under the winner */
+    uint32_t second;        /* the runner-up candidate's good count */
+    uint32_t status;        /* ORB_POSE_* */
+} OrbPairPose;              /* 64 bytes */
+
+#define ORB_POINT_GOOD 1u
+#define ORB_POINT_PARALLAX 2u
+typedef struct { float x, y, z; uint32_t flags; } OrbPoint;  /* 16 bytes; camera-f frame; flags: ORB_POINT_GOOD, ORB_POINT_PARALLAX */
+
+/* Poses of the pairs (f, f+1), f in [0, n_frames - 1), of the last batch.  ORB_EINVAL for a NULL program or params, fx or fy not
+ * finite or not > 0, cx or cy not finite, another parameter out of range, or n_frames not in 2 .. the last
+ * orb_verify_epipolar's pairs + 1; ORB_ESTATE unless the last orb_match_consecutive and the last orb_verify_epipolar are both of
+ * the current batch and output set.  Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not change it),
+ * ordered behind the matcher's and the epipolar verifier's last calls and the last call of its own when they ran on another
+ * stream; orb_match_consecutive and orb_verify_epipolar wait for such a call on another stream before they overwrite what it
+ * reads.  Result buffers of its own (allocated by the first call): no other stage's results are ever written.  R, t and the
+ * counts are written for every status except NOMODEL and the FEW of fewer than 8 inliers (all 0 then), and so are the points:
+ * the status says what to trust. */
+int orb_pose_consecutive(OrbProgram *p, uint32_t n_frames, const OrbPoseParams *params, void *stream);
+/* Copy the record of pair `pair` of the last orb_pose_consecutive call (pose may be NULL) and up to n points of the queries of
+ * frame `pair` (indexed as orb_match_read; 0, 0, 0, flags 0 for every query that is not a good point) to the host
+ * (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside its pairs or points NULL with n > 0. */
+int orb_pose_read(OrbProgram *p, uint32_t pair, OrbPairPose *pose, OrbPoint *points, size_t n);
+
 /* ---- feature tracks and keyframes (NOT in the reference; definition TK-1..TK-5 in DESIGN.md section 15) ----
  * Over the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: query i of frame f links to target j of frame f+1 by the
  * source's record (VERIFIED: the matcher's record where the last verification's inlier byte is 1; GUIDED / MATCHED: the last

@@ -196,6 +196,57 @@ pub mod orb {
     unsafe impl Send for OrbProgram {}
 
     // ------------------------------------------------------------------------------------------------------------
+    // Relative pose and triangulation of the epipolar inliers (include/tinyorb.h; not in the
+    // reference).  Declarations only: the handle is `orb_program_create`'s, the calls follow orb_match_consecutive
+    // and orb_verify_epipolar on the last batch.
+    // ------------------------------------------------------------------------------------------------------------
+    /// `OrbPoseParams`: a zeroed value is NOT valid (fx, fy must be > 0); the other zero fields mean the defaults.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbPoseParams {
+        pub fx: f32,
+        pub fy: f32,
+        pub cx: f32,
+        pub cy: f32,
+        pub max_reproj_px: f32,      // 0: 2.0
+        pub max_cos_parallax: f32,   // 0: 0.99998
+        pub min_good: u32,           // 0: 8
+        pub ambiguity_permille: u32, // 0: 700
+    }
+    /// `OrbPairPose`: X2 = R X1 + t, R row-major, |t| = 1.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbPairPose {
+        pub r: [f32; 9],
+        pub t: [f32; 3],
+        pub inliers: u32,
+        pub good: u32,
+        pub second: u32,
+        pub status: u32,
+    }
+    /// `OrbPoint`: a triangulated point in camera f's frame; all zero for a query that is not a good point.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbPoint {
+        pub x: f32,
+        pub y: f32,
+        pub z: f32,
+        pub flags: u32,
+    }
+    pub const ORB_POSE_OK: u32 = 0;
+    pub const ORB_POSE_NOMODEL: u32 = 1;
+    pub const ORB_POSE_FEW: u32 = 2;
+    pub const ORB_POSE_AMBIGUOUS: u32 = 3;
+    pub const ORB_POSE_LOW_PARALLAX: u32 = 4;
+    pub const ORB_POINT_GOOD: u32 = 1;
+    pub const ORB_POINT_PARALLAX: u32 = 2;
+
+    extern "C" {
+        pub fn orb_pose_consecutive(p: *mut c_void, n_frames: u32, params: *const OrbPoseParams, stream: *mut c_void) -> c_int;
+        pub fn orb_pose_read(p: *mut c_void, pair: u32, pose: *mut OrbPairPose, points: *mut OrbPoint, n: usize) -> c_int;
+    }
+
+    // ------------------------------------------------------------------------------------------------------------
     // Batched, multi-GPU entry (include/tinyorb.h "one node, several GPUs"; not in the reference, which drives one
     // wgpu device).  The same calls, in the same order, are exercised from C by examples/node_batch.c, which the
     // repository's GPU tests compile with gcc and run -- that C program is the verified twin of this block.

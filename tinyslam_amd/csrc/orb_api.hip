@@ -30,6 +30,7 @@
 #include "orb_kernels_epipolar.h"
 #include "orb_kernels_guide.h"
 #include "orb_kernels_band.h"
+#include "orb_kernels_pose.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -64,14 +65,15 @@ struct ProfSpan {
 // The stages that run after extraction.  Each owns ONE set of buffers per program, shared by both output sets and by whatever stream
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, which the entry point names; and the stages that read what it overwrites, kReadersOf[stage].
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_COUNT };
 const uint32_t kReadersOf[ST_COUNT] = {
-    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it)
+    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it)
     1u << ST_GUIDE | 1u << ST_TRACK,                  // verify: verify.model (guided, ORB_GUIDE_VERIFIED), verify.mask (track, ORB_TRACK_VERIFIED)
-    1u << ST_BAND,                                    // epi: epi.model (band, ORB_BAND_VERIFIED)
+    1u << ST_BAND | 1u << ST_POSE,                    // epi: epi.model (band, ORB_BAND_VERIFIED; pose), epi.mask (pose)
     1u << ST_TRACK,                                   // guide: d_gmatch (track, ORB_TRACK_GUIDED)
     0u,                                               // track: read back by the host
     0u,                                               // band: d_bmatch is read back by the host
+    0u,                                               // pose: read back by the host
 };
 
 // The last call of a stage
@@ -166,6 +168,10 @@ struct OrbProgram {
     MatchRecord* d_bmatch = nullptr;      // [max_batch][max_features] results
     float* d_bmodel = nullptr;            // [max_batch][9] the caller's fundamental matrices (ORB_BAND_HOST)
     float* h_bmodel = nullptr;            // pinned staging of the same
+    // orb_pose_consecutive (orb_kernels_pose.h)
+    uint32_t* d_pose = nullptr;           // [max_batch][16] OrbPairPose
+    float4* d_ppoints = nullptr;          // [max_batch][max_features] OrbPoint
+    uint32_t* d_pcount = nullptr;         // [max_batch][kPoseCounters]
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -332,6 +338,11 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         add(&p->d_bmatch, B * cap * sizeof(MatchRecord));
         add(&p->d_bmodel, B * 9u * sizeof(float));
         add(&p->h_bmodel, B * 9u * sizeof(float), true);
+        break;
+    case ST_POSE:
+        add(&p->d_pose, B * sizeof(OrbPairPose));
+        add(&p->d_ppoints, B * cap * sizeof(OrbPoint));
+        add(&p->d_pcount, B * kPoseCounters * sizeof(uint32_t));
         break;
     }
     return n;
@@ -2498,6 +2509,70 @@ int orb_match_epipolar_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t
     if (n > cap) n = cap;
     static_assert(sizeof(OrbBandParams) == 32, "OrbBandParams layout");
     if (n) HIP_TRY(p, hipMemcpy(dst, p->d_bmatch + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_pose_consecutive(OrbProgram* p, uint32_t n_frames, const OrbPoseParams* params, void* stream) {
+    if (!p || !params) return p ? fail(p, ORB_EINVAL, "pose_consecutive: params is NULL") : ORB_EINVAL;
+    OrbPoseParams g = *params;
+    if (!(std::isfinite(g.fx) && g.fx > 0.0f) || !(std::isfinite(g.fy) && g.fy > 0.0f) || !std::isfinite(g.cx) || !std::isfinite(g.cy))
+        return fail(p, ORB_EINVAL, "pose_consecutive: fx and fy must be finite and > 0, cx and cy finite");
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f) || !(g.max_cos_parallax >= 0.0f && g.max_cos_parallax <= 1.0f) ||
+        g.ambiguity_permille > 1000u)
+        return fail(p, ORB_EINVAL, "pose_consecutive: max_reproj_px must be finite and >= 0, max_cos_parallax in (0, 1] (0: the default), ambiguity_permille 0..1000");
+    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_EPI];
+    if (!stage_fresh(p, m) || !stage_fresh(p, v))
+        return fail(p, ORB_ESTATE, "pose_consecutive: no orb_match_consecutive and orb_verify_epipolar of the current batch and output set");
+    if (n_frames < 2u || n_frames - 1u > v.extent)
+        return fail(p, ORB_EINVAL, "pose_consecutive: need 2..%u frames (the last epipolar verification's pairs + 1)", v.extent + 1u);
+    if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
+    if (g.max_cos_parallax == 0.0f) g.max_cos_parallax = 0.99998f;
+    if (!g.min_good) g.min_good = 8u;
+    if (!g.ambiguity_permille) g.ambiguity_permille = 700u;
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features;
+    if (int rc = alloc_all_or_none(p, ST_POSE, "pose_consecutive")) return rc;
+    hipStream_t s;
+    if (int rc = stage_begin(p, ST_POSE, stream, 1u << ST_MATCH | 1u << ST_EPI, &s)) return rc;
+    const uint32_t pairs = n_frames - 1u;
+    PoseArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.matches = p->d_matches;
+    a.cap = (uint32_t)cap;
+    a.vmodel = p->epi.model;
+    a.vmask = p->epi.mask;
+    a.fx = g.fx;
+    a.fy = g.fy;
+    a.cx = g.cx;
+    a.cy = g.cy;
+    a.r2 = g.max_reproj_px * g.max_reproj_px;
+    a.c2 = g.max_cos_parallax * g.max_cos_parallax;
+    a.min_good = g.min_good;
+    a.permille = g.ambiguity_permille;
+    a.counters = p->d_pcount;
+    a.poses = p->d_pose;
+    a.points = p->d_ppoints;
+    static_assert(sizeof(OrbPairPose) == kPoseWords * sizeof(uint32_t) && sizeof(OrbPoint) == sizeof(float4) && sizeof(OrbPoseParams) == 32,
+                  "pose layouts");
+    const dim3 grid(pairs, (unsigned)((cap + kPoseThreads - 1u) / kPoseThreads));
+    HIP_TRY(p, hipMemsetAsync(p->d_pcount, 0, (size_t)pairs * kPoseCounters * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_pose_count, grid, dim3(kPoseThreads), 0, s, a);
+    hipLaunchKernelGGL(k_pose_points, grid, dim3(kPoseThreads), 0, s, a);
+    return stage_end(p, ST_POSE, s, pairs);  // p->last_stream stays, as after a guided call
+}
+
+int orb_pose_read(OrbProgram* p, uint32_t pair, OrbPairPose* pose, OrbPoint* points, size_t n) {
+    if (!p) return ORB_EINVAL;
+    const Stage& last = p->stage[ST_POSE];
+    if (!last.extent) return fail(p, ORB_ESTATE, "pose_read before pose_consecutive");
+    if (pair >= last.extent || (!points && n)) return fail(p, ORB_EINVAL, "pose_read: pair %u of %u, or points is NULL", pair, last.extent);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    if (pose) HIP_TRY(p, hipMemcpy(pose, p->d_pose + (size_t)pair * kPoseWords, sizeof(OrbPairPose), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(points, p->d_ppoints + (size_t)pair * cap, n * sizeof(OrbPoint), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

@@ -51,6 +51,11 @@ ORB_GUIDE_SCALE_RADIUS = 1
 # epipolar-band guided matching (orb_match_epipolar): where a pair's F comes from, and the flag of OrbBandParams
 ORB_BAND_VERIFIED, ORB_BAND_HOST = 0, 1
 ORB_BAND_SCALE = 1
+# relative pose and triangulation (orb_pose_consecutive): OrbPairPose (64 B), OrbPoint (16 B), status and flags
+POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("inliers", "<u4"), ("good", "<u4"), ("second", "<u4"), ("status", "<u4")])
+POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("flags", "<u4")])
+ORB_POSE_OK, ORB_POSE_NOMODEL, ORB_POSE_FEW, ORB_POSE_AMBIGUOUS, ORB_POSE_LOW_PARALLAX = 0, 1, 2, 3, 4
+ORB_POINT_GOOD, ORB_POINT_PARALLAX = 1, 2
 # feature tracks and keyframes (orb_track_consecutive): the link source, OrbTrack (16 B), OrbTrackFrame (32 B)
 ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
 TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
@@ -76,7 +81,7 @@ EXPORTS = [
     "orb_write_input_image_pinned", "orb_node_set_results", "orb_node_shard_result",
     "orb_verify_consecutive", "orb_verify_read", "orb_match_guided", "orb_match_guided_read",
     "orb_track_consecutive", "orb_track_read", "orb_track_frames", "orb_verify_epipolar", "orb_verify_epipolar_read",
-    "orb_match_epipolar", "orb_match_epipolar_read",
+    "orb_match_epipolar", "orb_match_epipolar_read", "orb_pose_consecutive", "orb_pose_read",
 ]
 
 
@@ -118,6 +123,13 @@ class _BandParams(ctypes.Structure):
     """OrbBandParams (32 bytes; zero fields = the defaults)"""
     _fields_ = [("source", ctypes.c_uint32), ("band_px", ctypes.c_float), ("radius_px", ctypes.c_float),
                 ("octave_window", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class _PoseParams(ctypes.Structure):
+    """OrbPoseParams (32 bytes; fx and fy must be > 0, the other zero fields = the defaults)"""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("max_reproj_px", ctypes.c_float), ("max_cos_parallax", ctypes.c_float), ("min_good", ctypes.c_uint32),
+                ("ambiguity_permille", ctypes.c_uint32)]
 
 
 class _TrackParams(ctypes.Structure):
@@ -205,6 +217,8 @@ def load_library(path=None):
     L.orb_match_guided_read.argtypes = [vp, u32, vp, sz]
     L.orb_match_epipolar.argtypes = [vp, u32, ctypes.POINTER(_BandParams), vp, vp]
     L.orb_match_epipolar_read.argtypes = [vp, u32, vp, sz]
+    L.orb_pose_consecutive.argtypes = [vp, u32, ctypes.POINTER(_PoseParams), vp]
+    L.orb_pose_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -621,6 +635,26 @@ class OrbProgram:
         out = np.zeros(min(n, self.config.max_features), dtype=MATCH_DTYPE)
         self._check(self._lib.orb_match_epipolar_read(self._handle(), frame, _ptr(out) if len(out) else None, len(out)))
         return out
+
+    def pose_consecutive(self, n_frames, fx, fy, cx, cy, max_reproj_px=0.0, max_cos_parallax=0.0, min_good=0, ambiguity_permille=0,
+                         stream=None):
+        """Relative pose and triangulation of the last batch (not in the reference): per pair
+        (f, f+1), f < n_frames - 1, the last verify_epipolar's F and the pinhole intrinsics (fx, fy, cx, cy, in level0_xy
+        coordinates) give the essential matrix, its four (R, t) candidates in closed form, and the one under which the most epipolar
+        inliers triangulate in front of both cameras within max_reproj_px (0: 2.0) of their frame f+1 keypoint.  max_cos_parallax
+        (0: 0.99998), min_good (0: 8) and ambiguity_permille (0: 700) decide the status only.  Asynchronous on `stream` (None: as
+        match_guided chooses)."""
+        prm = _PoseParams(float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
+                          float(np.float32(max_reproj_px)), float(np.float32(max_cos_parallax)), min_good, ambiguity_permille)
+        self._check(self._lib.orb_pose_consecutive(self._handle(), n_frames, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def pose_read(self, pair, n=None):
+        """(record of POSE_DTYPE, POINT_DTYPE[min(n, max_features)] of pair's queries, in camera f's frame; n None: max_features) of
+        the last pose_consecutive -- synchronises.  Queries that are not good points hold zeros."""
+        rec = np.zeros((), dtype=POSE_DTYPE)
+        pts = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=POINT_DTYPE)
+        self._check(self._lib.orb_pose_read(self._handle(), pair, _ptr(rec), _ptr(pts) if len(pts) else None, len(pts)))
+        return rec, pts
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
