@@ -219,6 +219,9 @@ struct OrbProgram {
     CornerData* d_seg = nullptr;     // fused path: [max_batch][n_slots][seg_classes][seg_cap] band segments
     uint32_t* d_seg_counts = nullptr;  // [max_batch][n_slots][seg_classes]
     uint32_t* d_seg_before = nullptr;  // [max_batch][seg_classes][n_slots] exclusive prefix of the stored counts
+    // [max_batch][brief_mask_words(max_features)] per output set, like the final lists it describes: bit i of word c of a frame = keypoint
+    // 64 c + i of the final list is not flat.  k_brief_t writes every word of the frames it runs on, k_brief_nf starts from them.
+    uint64_t* d_nf_mask[2] = {nullptr, nullptr};
     BandGeom bands{};
     RowsGeom rows{};
     BriefTGeom brieft{};       // thread-per-keypoint BRIEF of the fused literal pipelines (plain and arc/NMS)
@@ -663,7 +666,7 @@ bool brieft_geometry(const OrbProgram* p, const RowsGeom& rg, uint32_t n_classes
 // k_slot_prefix + BRIEF over the band (or tile) slots `rows_geom` of frames [f0, f0 + n).
 int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_geom, const uint16_t* d_blur,
                  const uint16_t* d_blur_rowc, const uint32_t* seg_counts, uint32_t* seg_before, const CornerData* seg,
-                 uint32_t* d_counts, CornerData* d_corners, CornerDescriptor* d_desc) {
+                 uint32_t* d_counts, CornerData* d_corners, CornerDescriptor* d_desc, uint32_t f0 = 0) {
     const uint32_t cap = p->cfg.max_features;
     const BriefTables tab{p->d_pattern, p->d_cos, p->d_sin, p->d_rot};
     const bool use_t = p->use_brief_t;
@@ -675,11 +678,14 @@ int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_
     if (use_t) {
         const BriefTGeom& tg = p->brieft;
         const dim3 grid(n, (cap + (uint32_t)kBriefNfChunk - 1u) / (uint32_t)kBriefNfChunk);  // k_brief_nf's
+        // the not-flat mask of these frames in the current output set: written by k_brief_t, read by k_brief_nf behind it on the stream
+        const uint32_t mask_words = brief_mask_words(cap);
+        uint64_t* const nf_mask = p->d_nf_mask[p->cur_set] + (size_t)f0 * mask_words;
         {
             LaunchScope ls(p, s, KID_BRIEF_T);
 #define BRIEF_T_LAUNCH(ROT_)                                                                                                         \
     hipLaunchKernelGGL((k_brief_t<kBriefTWaves, ROT_>), dim3(n, (cap + kBriefTThreads - 1u) / kBriefTThreads), dim3(kBriefTThreads), \
-                       brieft_lds_bytes(tg), s, d_blur_rowc, p->pyr, tg, seg_counts, seg_before, seg, d_corners, cap, d_desc, tab)
+                       brieft_lds_bytes(tg), s, d_blur_rowc, p->pyr, tg, seg_counts, seg_before, seg, d_corners, cap, d_desc, tab, nf_mask, mask_words)
             switch (rot_form(p->opt.fp_contract)) {  // the rotation's form (OrbOptions::fp_contract): a template parameter of the straight-line tests
                 case 1: BRIEF_T_LAUNCH(1); break;
                 case 2: BRIEF_T_LAUNCH(2); break;
@@ -688,12 +694,17 @@ int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_
 #undef BRIEF_T_LAUNCH
         }
         LaunchScope ls(p, s, KID_BRIEF_NF);
-        if (p->oob != kOobZero)
-            hipLaunchKernelGGL(k_brief_nf<true>, grid, dim3(256), 0, s, d_blur, d_blur_rowc, p->pyr, tg, seg_counts, seg_before, d_corners,
-                               cap, d_desc, tab);
-        else
-            hipLaunchKernelGGL(k_brief_nf<false>, grid, dim3(256), 0, s, d_blur, d_blur_rowc, p->pyr, tg, seg_counts, seg_before, d_corners,
-                               cap, d_desc, tab);
+        // the level constants: a scalar select between two levels' kernel arguments, or the LDS table for deeper pyramids
+#define BRIEF_NF_LAUNCH(OOB_, TABLE_)                                                                                                  \
+    hipLaunchKernelGGL((k_brief_nf<OOB_, TABLE_>), grid, dim3(256), 0, s, d_blur, d_blur_rowc, p->pyr, tg, d_corners, cap, d_desc, tab, \
+                       nf_mask, mask_words)
+        const bool table = p->pyr.depth > 2u;
+        if (p->oob != kOobZero) {
+            if (table) BRIEF_NF_LAUNCH(true, true); else BRIEF_NF_LAUNCH(true, false);
+        } else {
+            if (table) BRIEF_NF_LAUNCH(false, true); else BRIEF_NF_LAUNCH(false, false);
+        }
+#undef BRIEF_NF_LAUNCH
     } else {
         LaunchScope ls(p, s, KID_BRIEF_ROWS);
         RowsGeom rg = rows_geom;
@@ -806,7 +817,7 @@ int run_fused_range(OrbProgram* p, const uint8_t* frames_all, uint32_t f0, uint3
         }
     }
     // orb.rs:523-534, plus the compaction of the band segments into the final lists
-    if (with_brief) launch_brief(p, s, n, p->rows, d_blur, d_blur_rowc, d_seg_counts, d_seg_before, d_seg, d_counts, d_corners, d_desc);
+    if (with_brief) launch_brief(p, s, n, p->rows, d_blur, d_blur_rowc, d_seg_counts, d_seg_before, d_seg, d_counts, d_corners, d_desc, f0);
     HIP_TRY(p, hipGetLastError());
     return ORB_OK;
 }
@@ -1417,6 +1428,11 @@ int orb_program_create(const OrbConfig* config, const OrbOptions* options, OrbPr
         CREATE_TRY(hipMemset(p->d_seg_counts, 0, B * lists * sizeof(uint32_t)));
         CREATE_TRY(hipMalloc(&p->d_seg_before, B * lists * sizeof(uint32_t)));
     }
+    if (p->use_brief_t)  // (the band pipeline or the tile pipeline: whichever launch_brief serves)
+        for (int set = 0; set < ((p->opt.flags & ORB_FLAG_DOUBLE_OUTPUT) ? 2 : 1); set++) {
+            // (not cleared: k_brief_t writes every word of the frames of a batch before k_brief_nf reads them)
+            CREATE_TRY(hipMalloc(&p->d_nf_mask[set], B * brief_mask_words((uint32_t)cap) * sizeof(uint64_t)));
+        }
     if (p->fused_x) {
         CREATE_TRY(hipMalloc(&p->d_blur_rowc, B * p->pyr.row_stride * sizeof(uint16_t)));
         CREATE_TRY(hipMemset(p->d_blur_rowc, 0, B * p->pyr.row_stride * sizeof(uint16_t)));
@@ -1523,6 +1539,7 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_seg);
     (void)hipFree(p->d_seg_counts);
     (void)hipFree(p->d_seg_before);
+    for (int set = 0; set < 2; set++) (void)hipFree(p->d_nf_mask[set]);
     (void)hipFree(p->d_score_planes);
     (void)hipFree(p->d_prov_counts);
     (void)hipFree(p->d_prov);

@@ -23,6 +23,9 @@ constexpr int kBriefTThreads = 256;  // four waves share the staging of the fram
 constexpr int kBriefTWaves = 6;       // waves per SIMD the register allocation aims at
 constexpr uint32_t kBriefTMaxSlots = 8192;  // seg_before of a frame is staged in LDS
 constexpr uint32_t kBriefTMaxRows = 12288;  // rows (all levels) + 36 per level, staged in LDS as f16
+// 64-bit words per frame of the not-flat mask k_brief_t leaves for k_brief_nf: one per 64 keypoints of the final list, four per
+// workgroup of k_brief_t (every workgroup stores all of its four, so the count is a multiple of four)
+__host__ __device__ inline uint32_t brief_mask_words(uint32_t cap) { return 4u * ((cap + (uint32_t)kBriefTThreads - 1u) / (uint32_t)kBriefTThreads); }
 
 struct BriefTGeom {
     uint32_t n_slots, seg_cap;
@@ -89,14 +92,20 @@ __device__ __forceinline__ void brief_t_stage_rows(uint16_t* rows, const uint16_
 // put the list prefix and the row constants into lds_raw (k_brief_one does, next to its own prefix scan).
 // ROT: the form matrix * vector takes under the adapter's shader compiler (rot_form(), CRD-13): 0 = both products and the sum rounded
 // (CRD-10, the default); 1 = y' = fma(ct, y, -st*x); 2 = y' = fma(-st, x, ct*y) -- a product fewer per point either way.
-template <int CHUNK = kBriefTThreads, bool STAGED = false, int ROT = 0>
+// MASK (the batch kernel): every wave leaves one 64-bit word in nf_mask[frame][k / 64], bit i set iff keypoint k0 + i is NOT
+// flat -- what the wave decides anyway -- so that k_brief_nf starts from the word instead of a second scan of the records.
+// Every workgroup of the launch writes its four words, the ones past the frame's count zeros: the buffer needs no clearing
+// and a batch with fewer keypoints than the one before reads no stale bit.  mask_words: words per frame (brief_mask_words).
+template <int CHUNK = kBriefTThreads, bool STAGED = false, int ROT = 0, bool MASK = false>
 __device__ __forceinline__ void brief_t_body(uint8_t* lds_raw, uint32_t frame, uint32_t chunk, const uint16_t* __restrict__ blur_rowc,
                                              const Pyramid& pyr, const BriefTGeom& bg, const uint32_t* __restrict__ seg_counts,
                                              const uint32_t* __restrict__ seg_before, const CornerData* __restrict__ segments,
                                              CornerData* __restrict__ corners, uint32_t cap,
                                              CornerDescriptor* __restrict__ descriptors, const BriefTables& tab,
                                              CornerData* __restrict__ host_corners = nullptr,
-                                             CornerDescriptor* __restrict__ host_descriptors = nullptr) {
+                                             CornerDescriptor* __restrict__ host_descriptors = nullptr,
+                                             uint64_t* __restrict__ nf_mask = nullptr, uint32_t mask_words = 0) {
+    static_assert(!MASK || (CHUNK == kBriefTThreads && !STAGED), "the mask is the batch kernel's: 256 keypoints, four words");
     // host_corners / host_descriptors (k_brief_one): every record and descriptor is also written to these (pinned host) arrays
     const uint32_t n_ent = bg.n_slots * bg.n_classes;  // lists of a frame, in final order: class-major, slot-minor
     uint32_t* const before = reinterpret_cast<uint32_t*>(lds_raw);                    // [n_ent + 1]
@@ -116,7 +125,11 @@ __device__ __forceinline__ void brief_t_body(uint8_t* lds_raw, uint32_t frame, u
     }
     const uint32_t n_frame = min(stored_total, cap);
     const uint32_t k0 = chunk * (uint32_t)CHUNK;
-    if (k0 >= n_frame) return;  // uniform for the workgroup
+    uint64_t* const mask_word = MASK ? nf_mask + (size_t)frame * mask_words + (k0 >> 6) + (tid >> 6) : nullptr;  // this wave's
+    if (k0 >= n_frame) {  // uniform for the workgroup
+        if (MASK && (tid & 63u) == 0u) *mask_word = 0ull;
+        return;
+    }
 
     if (!STAGED) {
         // ---- stage the frame's list prefix and row constants (zeros around every level)
@@ -129,22 +142,35 @@ __device__ __forceinline__ void brief_t_body(uint8_t* lds_raw, uint32_t frame, u
 
     // ---- this thread's keypoint: slot by binary search in the prefix, record from the band segment
     const uint32_t k = k0 + tid;
-    if (tid >= (uint32_t)CHUNK || k >= n_frame) return;
-    uint32_t lo = 0, hi = n_ent;  // largest e with before[e] <= k (empty lists repeat the value: take the last)
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (before[mid] <= k)
-            lo = mid;
-        else
-            hi = mid;
+    // MASK: the lanes at or past n_frame stay (the ballot below wants all 64 lanes of the wave) and touch no memory
+    const bool live = k < n_frame;
+    if (!MASK && (tid >= (uint32_t)CHUNK || !live)) return;
+    uint4 fetched = make_uint4(0u, 0u, 0u, 0u);
+    if (!MASK || live) {
+        uint32_t lo = 0, hi = n_ent;  // largest e with before[e] <= k (empty lists repeat the value: take the last)
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (before[mid] <= k)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const uint32_t cls = lo >= bg.n_slots ? 1u : 0u, slot = lo - cls * bg.n_slots;
+        fetched = *reinterpret_cast<const uint4*>(
+            &segments[(((size_t)frame * bg.n_slots + slot) * bg.n_classes + cls) * bg.seg_cap + (k - before[lo])]);
+        *reinterpret_cast<uint4*>(&corners[(size_t)frame * cap + k]) = fetched;  // final list = the lists back to back
+        if (host_corners) store_host_16(&host_corners[k], fetched);
     }
-    const uint32_t cls = lo >= bg.n_slots ? 1u : 0u, slot = lo - cls * bg.n_slots;
-    const uint4 rec = *reinterpret_cast<const uint4*>(
-        &segments[(((size_t)frame * bg.n_slots + slot) * bg.n_classes + cls) * bg.seg_cap + (k - before[lo])]);
-    *reinterpret_cast<uint4*>(&corners[(size_t)frame * cap + k]) = rec;  // final list = the lists back to back
-    if (host_corners) store_host_16(&host_corners[k], rec);
+    const uint4 rec = fetched;
     const uint32_t lvl = min(rec.w, pyr.depth - 1u);
-    if (!(rec.x >= (uint32_t)kBriefHalo && rec.x < lv[lvl][0])) return;  // not flat: k_brief_nf takes it
+    if constexpr (MASK) {  // before any lane leaves: bit i = keypoint k0 + 64 * wave + i exists and is not flat
+        const bool flat = live && rec.x >= (uint32_t)kBriefHalo && rec.x < lv[lvl][0];
+        const uint64_t not_flat = __ballot(live && !flat);
+        if ((tid & 63u) == 0u) *mask_word = not_flat;
+        if (!flat) return;  // k_brief_nf takes it (or there is no such keypoint)
+    } else {
+        if (!(rec.x >= (uint32_t)kBriefHalo && rec.x < lv[lvl][0])) return;  // not flat: k_brief_nf takes it
+    }
 
     uint32_t d[8];
     uint4* const o = reinterpret_cast<uint4*>(descriptors + (size_t)frame * cap + k);
@@ -216,11 +242,13 @@ __global__ __launch_bounds__(kBriefTThreads, kWavesPerSimd) void k_brief_t(const
                                                                 const uint32_t* __restrict__ seg_before,
                                                                 const CornerData* __restrict__ segments,
                                                                 CornerData* __restrict__ corners, uint32_t cap,
-                                                                CornerDescriptor* __restrict__ descriptors, BriefTables tab) {
+                                                                CornerDescriptor* __restrict__ descriptors, BriefTables tab,
+                                                                uint64_t* __restrict__ nf_mask, uint32_t mask_words) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     // The frame is the FAST grid index: chunks past a frame's keypoint count exit at once, and with the chunk as the fast
     // index their regular pattern (15 busy, 17 idle, ...) lands every busy workgroup on the same half of the CUs.
-    brief_t_body<kBriefTThreads, false, ROT>(lds_raw, blockIdx.x, blockIdx.y, blur_rowc, pyr, bg, seg_counts, seg_before, segments, corners, cap, descriptors, tab);
+    brief_t_body<kBriefTThreads, false, ROT, true>(lds_raw, blockIdx.x, blockIdx.y, blur_rowc, pyr, bg, seg_counts, seg_before, segments, corners, cap, descriptors, tab,
+                                                   nullptr, nullptr, nf_mask, mask_words);
 }
 
 // The keypoints k_brief_t leaves (not flat, 12 %: a sample may come from the stored tail of the blur plane, or lie left
@@ -343,121 +371,80 @@ __device__ __forceinline__ void brief_nf_body(uint32_t frame, uint32_t chunk, ui
         const int qa = (int)__builtin_amdgcn_readfirstlane(lv[lvl][2]);
         const uint16_t* rowc = blur_rowc + (size_t)frame * pyr.row_stride + __builtin_amdgcn_readfirstlane(lv[lvl][3]);
         const uint16_t* plane = blur + (size_t)frame * pyr.stride + __builtin_amdgcn_readfirstlane(lv[lvl][4]);
-        // this lane's eight rotated points (brief.wgsl:50-57), from the table of the keypoint's angle code: issued here, used
-        // behind the patch fill
-        const uint4 tt = tab.rot[(size_t)min(r.z, (uint32_t)(ORB_ANGLE_STEPS - 1)) * 64u + lane];
-        const uint32_t tw[4] = {tt.x, tt.y, tt.z, tt.w};
-        uint64_t bal[4];
-        if ((w & 1) == 0) {
-            // ---- patch in LDS: rows y-18..y+18, columns c0..c0+47 with c0 = (x - 18) rounded down to 8.  A piece
-            //      (8 columns) lies entirely left of the level (zeros), below qa (the row constant) or in the stored
-            //      tail (one 16-byte load); the four pieces of a lane are loaded back to back from addresses that are
-            //      always valid (the plane's first texels where none is needed) and composed afterwards.
-            const int c0 = ((int)r.x - kBriefHalo) & ~7;
-            constexpr int kPiecesPerRow = kNfPatchCols / 8, kPieces = kNfPatchRows * kPiecesPerRow;
-            constexpr int kRounds = (kPieces + 63) / 64;
-            uint4 tv[kRounds];
-            uint32_t rcv[kRounds];
-            int kind[kRounds], where[kRounds];  // 0: zeros, 1: row constant, 2: loaded, 3: the level ends inside the piece
-#pragma unroll
-            for (int rr = 0; rr < kRounds; rr++) {
-                const int p = (int)lane + 64 * rr;
-                const int pr = (int)(((float)p + 0.5f) * (1.0f / (float)kPiecesPerRow));
-                const int pc = p - pr * kPiecesPerRow;
-                const int gy0 = (int)r.y - kBriefHalo + pr, cx = c0 + 8 * pc;
-                const int gy = OOB ? oob_index(gy0, h, bg.oob) : gy0;  // OOB: a row outside the level reads a row of the level
-                const bool in = p < kPieces && gy >= 0 && gy < h && cx >= 0 && cx < w;
-                kind[rr] = !in ? 0 : (cx < qa ? 1 : (cx + 8 <= w ? 2 : 3));
-                where[rr] = p < kPieces ? pr * kNfPatchCols + 8 * pc : -1;
-                rcv[rr] = rowc[min(max(gy, 0), h - 1)];
-                if (OOB && p < kPieces && !(cx >= 0 && cx < w)) {
-                    // the whole piece lies left (cx <= -8) or right (cx >= w) of the level: one texel of row gy repeated -- its first
-                    // (clamp, left) or its last one (right; umin: left as well); a column below qa is the row constant
-                    const int xm = oob_index(cx, w, bg.oob);
-                    if (xm >= qa) rcv[rr] = plane[(size_t)(uint32_t)(__mul24(gy, w) + xm)];
-                    kind[rr] = 1;
-                }
-                // 4-byte aligned: even width, cx a multiple of 8
-                tv[rr] = *reinterpret_cast<const uint4*>(plane + (kind[rr] == 2 ? (size_t)(uint32_t)(__mul24(gy, w) + cx) : (size_t)0));
-            }
-#pragma unroll
-            for (int rr = 0; rr < kRounds; rr++) {
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (kind[rr] == 1) {
-                    const uint32_t c2 = rcv[rr] | (rcv[rr] << 16);
-                    v = make_uint4(c2, c2, c2, c2);
-                } else if (kind[rr] == 2) {
-                    v = tv[rr];
-                } else if (kind[rr] == 3) {  // width not a multiple of 8: the last piece of a row, texel by texel
-                    const int p = (int)lane + 64 * rr;
-                    const int pr = (int)(((float)p + 0.5f) * (1.0f / (float)kPiecesPerRow));
-                    const int gy0 = (int)r.y - kBriefHalo + pr, cx = c0 + 8 * (p - pr * kPiecesPerRow);
-                    const int gy = OOB ? oob_index(gy0, h, bg.oob) : gy0;
-                    const uint16_t* src = plane + (size_t)(uint32_t)(__mul24(gy, w) + cx);
-                    uint32_t t[8];
-#pragma unroll
-                    for (int q = 0; q < 8; q++) t[q] = cx + q < w ? (uint32_t)src[q] : (OOB ? (uint32_t)src[w - 1 - cx] : 0u);  // OOB: the row's last texel (cx >= qa here)
-                    v = make_uint4(t[0] | (t[1] << 16), t[2] | (t[3] << 16), t[4] | (t[5] << 16), t[6] | (t[7] << 16));
-                }
-                if (where[rr] >= 0) *reinterpret_cast<uint4*>(&patch[where[rr]]) = v;
-            }
-            // the patch is filled with 16-byte stores and sampled as halfs by OTHER lanes of this wave: order the two
-            // (LDS is in order within a wave; the fence keeps the compiler from moving the differently typed accesses)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int xo = (int)r.x - c0;  // 18..25
-            const uint8_t* const centre = reinterpret_cast<const uint8_t*>(patch + kBriefHalo * kNfPatchCols + xo);  // the keypoint's texel
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const uint32_t va = *reinterpret_cast<const uint16_t*>(centre + rot_a(tw[e]));
-                const uint32_t vb = *reinterpret_cast<const uint16_t*>(centre + rot_b(tw[e]));
-                bal[e] = __ballot(va > vb);  // non-negative f16: bit patterns order like the values (brief.wgsl:62)
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next keypoint's fill overwrites what was just sampled
-            __builtin_amdgcn_wave_barrier();
-        } else {
-            // ---- odd width: rows of the plane are only 2-byte aligned; gather sample by sample
-            const int gy = (int)r.y - kBriefHalo + (int)lane;  // lanes 0..36 are the patch rows
-            const uint32_t rowv = (gy >= 0 && gy < h && lane < 37u) ? (uint32_t)rowc[gy] : 0u;
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                // the table holds 2 * (dy * kNfPatchCols + dx) with |dx| < kNfPatchCols / 2: take it apart again
-                const int oa = rot_a(tw[e]) >> 1, ob = rot_b(tw[e]) >> 1;
-                const int dya = (oa + kNfPatchCols / 2 + 64 * kNfPatchCols) / kNfPatchCols - 64, dxa = oa - dya * kNfPatchCols;
-                const int dyb = (ob + kNfPatchCols / 2 + 64 * kNfPatchCols) / kNfPatchCols - 64, dxb = ob - dyb * kNfPatchCols;
-                const int xa = (int)r.x + dxa, ya = (int)r.y + dya;
-                const int xb = (int)r.x + dxb, yb = (int)r.y + dyb;
-                uint32_t va = (uint32_t)__shfl((int)rowv, dya + kBriefHalo);  // 0 when the row is outside the level
-                uint32_t vb = (uint32_t)__shfl((int)rowv, dyb + kBriefHalo);
-                const bool ina = xa >= 0 && xa < w && ya >= 0 && ya < h;
-                const bool inb = xb >= 0 && xb < w && yb >= 0 && yb < h;
-                if (!ina)
-                    va = OOB ? blur_sample_mapped(plane, rowc, w, h, qa, xa, ya, bg.oob) : 0u;
-                else if (xa >= qa)
-                    va = plane[(size_t)(uint32_t)(__mul24(ya, w) + xa)];
-                if (!inb)
-                    vb = OOB ? blur_sample_mapped(plane, rowc, w, h, qa, xb, yb, bg.oob) : 0u;
-                else if (xb >= qa)
-                    vb = plane[(size_t)(uint32_t)(__mul24(yb, w) + xb)];
-                bal[e] = __ballot(va > vb);
-            }
-        }
-        if (lane < 8u) {
-            const uint64_t src = lane < 2u ? bal[0] : (lane < 4u ? bal[1] : (lane < 6u ? bal[2] : bal[3]));
-            out_desc[(size_t)idx * 8u + lane] = (uint32_t)(src >> ((lane & 1u) * 32u));
-            if (host_descriptors) store_host_u32(reinterpret_cast<uint32_t*>(host_descriptors + k0) + (size_t)idx * 8u + lane, (uint32_t)(src >> ((lane & 1u) * 32u)));
-        }
+#include "orb_brief_nf_keypoint.inc"
     }
 }
 
-constexpr int kBriefNfChunk = 64;  // keypoints of the final list a workgroup scans
-template <bool OOB = false>
+constexpr int kBriefNfChunk = 64;  // keypoints of the final list a workgroup takes: one word of the mask
+// The form k_brief_nf runs: k_brief_t, one launch earlier, decided "flat or not" for every record it copied and left the answer in
+// nf_mask (brief_t_body, MASK), so nothing is scanned here.  Every wave loads the chunk's word with one scalar load -- a zero word
+// ends the workgroup: an empty chunk, or one past the frame's count, costs 8 bytes and no count look-up --, takes the set bits of
+// rank w, w + 4, ..., loads their records with ONE vector load (the lane whose bit it is loads it) and walks them with scalar bit
+// operations and v_readlane: no records, list or wave counts in LDS and no barrier.  TABLE = false (depth <= 2): the level's
+// constants are a scalar select between two levels' kernel arguments and the patches are the workgroup's only LDS; TABLE = true
+// (deeper pyramids): the LDS table of the scanning form behind one barrier.
+template <bool OOB = false, bool TABLE = false>
+__device__ __forceinline__ void brief_nf_mask_body(uint32_t frame, uint32_t chunk, const uint16_t* __restrict__ blur,
+                                                   const uint16_t* __restrict__ blur_rowc, const Pyramid& pyr, const BriefTGeom& bg,
+                                                   const CornerData* __restrict__ corners, uint32_t cap,
+                                                   CornerDescriptor* __restrict__ descriptors, const BriefTables& tab,
+                                                   const uint64_t* __restrict__ nf_mask, uint32_t mask_words) {
+    constexpr int NW = 4;
+    __shared__ __attribute__((aligned(16))) uint16_t patches[NW][kNfPatchHalfs];
+    __shared__ uint32_t lv[kMaxLevels][5];  // w, h, qa, row_off, off (TABLE only: an array no code touches is not allocated)
+    CornerDescriptor* const host_descriptors = nullptr;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t k0 = chunk * (uint32_t)kBriefNfChunk;
+    const uint64_t m = nf_mask[(size_t)frame * mask_words + chunk];  // uniform address: one scalar 8-byte load
+    if (m == 0ull) return;  // uniform for the workgroup: nothing here that is not flat, or nothing at all
+    if constexpr (TABLE) {
+        if (tid < pyr.depth) {
+            lv[tid][0] = pyr.w[tid], lv[tid][1] = pyr.h[tid], lv[tid][2] = bg.qa[tid], lv[tid][3] = pyr.row_off[tid];
+            lv[tid][4] = pyr.off[tid];
+        }
+        __syncthreads();
+    }
+    // the set bit of rank r goes to wave r % 4; the lane whose bit it is loads the record: all of the wave's in one instruction
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const bool mine = ((m >> lane) & 1ull) != 0ull && rank % (uint32_t)NW == wave;
+    uint64_t left = __ballot(mine);  // this wave's keypoints
+    if (left == 0ull) return;        // fewer set bits than waves
+    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+    if (mine) rec = *reinterpret_cast<const uint4*>(&corners[(size_t)frame * cap + k0 + lane]);
+
+    uint32_t* out_desc = reinterpret_cast<uint32_t*>(descriptors + (size_t)frame * cap + k0);
+    uint16_t* const patch = patches[wave];
+    do {
+        // the whole wave works on one keypoint, the lowest bit left: its lane holds the record, v_readlane makes the fields scalars
+        const uint32_t idx = (uint32_t)__builtin_ctzll(left);
+        left &= left - 1ull;
+        uint4 r;  // x, y, angle, octave
+        r.x = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, (int)idx), r.y = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, (int)idx);
+        r.z = (uint32_t)__builtin_amdgcn_readlane((int)rec.z, (int)idx), r.w = (uint32_t)__builtin_amdgcn_readlane((int)rec.w, (int)idx);
+        const uint32_t lvl = min(r.w, pyr.depth - 1u);
+        int w, h, qa;
+        const uint16_t *rowc, *plane;
+        if constexpr (TABLE) {
+            w = (int)__builtin_amdgcn_readfirstlane(lv[lvl][0]), h = (int)__builtin_amdgcn_readfirstlane(lv[lvl][1]);
+            qa = (int)__builtin_amdgcn_readfirstlane(lv[lvl][2]);
+            rowc = blur_rowc + (size_t)frame * pyr.row_stride + __builtin_amdgcn_readfirstlane(lv[lvl][3]);
+            plane = blur + (size_t)frame * pyr.stride + __builtin_amdgcn_readfirstlane(lv[lvl][4]);
+        } else {  // both levels' constants are scalar kernel arguments: selects, no memory
+            const bool up = lvl != 0u;
+            w = (int)(up ? pyr.w[1] : pyr.w[0]), h = (int)(up ? pyr.h[1] : pyr.h[0]), qa = (int)(up ? bg.qa[1] : bg.qa[0]);
+            rowc = blur_rowc + (size_t)frame * pyr.row_stride + (up ? pyr.row_off[1] : pyr.row_off[0]);
+            plane = blur + (size_t)frame * pyr.stride + (up ? pyr.off[1] : pyr.off[0]);
+        }
+#include "orb_brief_nf_keypoint.inc"
+    } while (left != 0ull);
+}
+
+template <bool OOB = false, bool TABLE = false>
 __global__ __launch_bounds__(256) void k_brief_nf(const uint16_t* __restrict__ blur, const uint16_t* __restrict__ blur_rowc,
-                                                  Pyramid pyr, BriefTGeom bg, const uint32_t* __restrict__ seg_counts,
-                                                  const uint32_t* __restrict__ seg_before,
-                                                  const CornerData* __restrict__ corners, uint32_t cap,
-                                                  CornerDescriptor* __restrict__ descriptors, BriefTables tab) {
-    brief_nf_body<kBriefNfChunk, 4, OOB>(blockIdx.x, blockIdx.y, ~0u, blur, blur_rowc, pyr, bg, seg_counts, seg_before, corners, cap, descriptors, tab);  // frame = fast index, as above
+                                                  Pyramid pyr, BriefTGeom bg, const CornerData* __restrict__ corners, uint32_t cap,
+                                                  CornerDescriptor* __restrict__ descriptors, BriefTables tab,
+                                                  const uint64_t* __restrict__ nf_mask, uint32_t mask_words) {
+    brief_nf_mask_body<OOB, TABLE>(blockIdx.x, blockIdx.y, blur, blur_rowc, pyr, bg, corners, cap, descriptors, tab, nf_mask, mask_words);  // frame = fast index, as above
 }
 
 // ---------------------------------------------------------------------------------------------
