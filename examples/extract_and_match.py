@@ -61,5 +61,10 @@ with orb.OrbProgram(cfg) as prog:  # == OrbProgram { config, .. }.init() in the 
         good = (points["flags"] & orb.ORB_POINT_GOOD) != 0
         print("frame 0 -> 1 pose: status %d, %d of %d inliers triangulated, R =\n%s\nt = %s"
               % (int(pose["status"]), int(good.sum()), int(pose["inliers"]), pose["r"].reshape(3, 3), pose["t"]))
+        # --- the pair poses chained into one path and one map; two frames: the origin and one START --------
+        prog.trajectory_consecutive(2)
+        frame1, world = prog.trajectory_read(1, 0)[0], prog.trajectory_read(0, int(counts[0]))[1]
+        print("frame 1 in frame %d's coordinates: status %d, scale %.3f, %d map points"
+              % (int(frame1["origin"]), int(frame1["status"]), float(frame1["scale"]), int(((world["flags"] & orb.ORB_POINT_GOOD) != 0).sum())))
     else:
         print("frame 0 -> 1: no fundamental matrix (status %d), no band search and no pose" % int(fmodel["status"]))

@@ -553,6 +553,63 @@ int orb_pose_consecutive(OrbProgram *p, uint32_t n_frames, const OrbPoseParams *
  * (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside its pairs or points NULL with n > 0. */
 int orb_pose_read(OrbProgram *p, uint32_t pair, OrbPairPose *pose, OrbPoint *points, size_t n);
 
+/* ---- trajectory: the pair poses chained into one camera path and one point map with a common scale (NOT in the reference;
+ * definition TJ-1..TJ-7 in DESIGN.md section 20) ----
+ * Every pair of orb_pose_consecutive stands alone: |t| = 1 and the points are in the pair's own camera frame and unit.  Frame f is
+ * the joint of the pairs (f-1, f) and (f, f+1): pair f-1 triangulated point i from camera f-1, the matcher's index j says which
+ * keypoint of frame f it is, and pair f triangulated j again from camera f.  When both poses are OK and both points GOOD, the
+ * depth of R X + t (pair f-1's pose and point) over the depth of pair f's point is the ratio of the two baselines.  The joint's
+ * step g is the lower median of its ratios; the joint holds when there are at least min_shared ratios of which at least
+ * consistent_permille per thousand lie within scale_tolerance * g of g.  Frame poses follow in sequence: a pose that is not OK
+ * loses the frame (LOST: a new origin), an OK pose after one that is not starts a segment (START: the pair's own pose, scale 1),
+ * a joint that does not hold restarts one (RESTART_FEW, RESTART_SPREAD), and one that holds chains: scale = scale * g,
+ * R = P.r R', t = P.r t' + scale P.t, with R taken one polar step towards a rotation.  The points of pair f are mapped into the
+ * frame and unit of frame f+1's origin.  Binary32 arithmetic in a fixed order, no fused operations: a CPU restatement gives the
+ * same bits. */
+typedef struct {                  /* zero-initialised = the defaults */
+    uint32_t min_shared;          /* ratios a joint needs (0: 8) */
+    float scale_tolerance;        /* a ratio is consistent within this share of the median (0: 0.1); finite, >= 0 */
+    uint32_t consistent_permille; /* consistent ratios a joint needs, per thousand (0: 500); 0..1000 */
+    uint32_t flags;               /* ORB_TRAJ_NEED_PARALLAX */
+    uint32_t reserved[4];         /* must be 0 */
+} OrbTrajectoryParams;            /* 32 bytes */
+
+#define ORB_TRAJ_NEED_PARALLAX 1u /* only points with ORB_POINT_PARALLAX in both pairs give a ratio */
+
+#define ORB_TRAJ_CHAINED 0u        /* the joint before the frame holds: the pose continues its segment */
+#define ORB_TRAJ_START 1u          /* the pair before the frame is OK, the one before that is not (or there is none) */
+#define ORB_TRAJ_RESTART_FEW 2u    /* both pairs are OK, the joint has fewer than min_shared ratios */
+#define ORB_TRAJ_RESTART_SPREAD 3u /* both pairs are OK, too few of the joint's ratios agree with their median */
+#define ORB_TRAJ_LOST 4u           /* the pair before the frame is not OK: identity, the frame is its own origin */
+#define ORB_TRAJ_ORIGIN 5u         /* frame 0 */
+
+typedef struct {
+    float r[9];             /* row-major R, X_f = R X_origin + t */
+    float t[3];             /* in units of the baseline of the pair (origin, origin + 1) */
+    float scale;            /* the baseline of the pair (f-1, f) in that unit (START, RESTART_*: 1; LOST, ORIGIN: 0) */
+    float step;             /* g of the joint before the frame (CHAINED, RESTART_SPREAD), else 0 */
+    uint32_t origin;        /* the frame whose camera frame this pose starts from */
+    uint32_t shared;        /* ratios of the joint before the frame (0 where none was evaluated) */
+    uint32_t consistent;    /* of them: within scale_tolerance of the median */
+    uint32_t status;        /* ORB_TRAJ_* */
+    uint32_t reserved[2];   /* 0 */
+} OrbFramePose;             /* 80 bytes */
+
+/* Poses of the frames 0 .. n_frames - 1 of the last batch and the map points of its pairs.  params NULL: the defaults.
+ * ORB_EINVAL for a NULL program, n_frames not in 2 .. min(4096, the last orb_pose_consecutive's pairs + 1), scale_tolerance not
+ * finite or < 0, consistent_permille > 1000, an unknown flag, a reserved word that is not 0, or a program with max_features above
+ * 2^23; ORB_ESTATE unless the last orb_match_consecutive and the last orb_pose_consecutive are both of the current batch and
+ * output set.  Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not change it), ordered behind the
+ * matcher's and the pose stage's last calls and the last call of its own when they ran on another stream;
+ * orb_match_consecutive and orb_pose_consecutive wait for such a call on another stream before they overwrite what it reads.
+ * Result buffers of its own (allocated by the first call): no other stage's results are ever written. */
+int orb_trajectory_consecutive(OrbProgram *p, uint32_t n_frames, const OrbTrajectoryParams *params, void *stream);
+/* Copy the record of frame `frame` of the last orb_trajectory_consecutive call (pose may be NULL) and up to n map points of the
+ * pair (frame, frame + 1) -- indexed as orb_pose_read's, in the frame and unit of the origin of frame + 1; zeros for every slot
+ * that is not a good point, for a pair whose next frame is LOST and for the last frame -- to the host (synchronises); ORB_ESTATE
+ * before any call, ORB_EINVAL for a frame outside the call's frames or points NULL with n > 0. */
+int orb_trajectory_read(OrbProgram *p, uint32_t frame, OrbFramePose *pose, OrbPoint *points, size_t n);
+
 /* ---- feature tracks and keyframes (NOT in the reference; definition TK-1..TK-5 in DESIGN.md section 15) ----
  * Over the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: query i of frame f links to target j of frame f+1 by the
  * source's record (VERIFIED: the matcher's record where the last verification's inlier byte is 1; GUIDED / MATCHED: the last

@@ -247,6 +247,48 @@ pub mod orb {
     }
 
     // ------------------------------------------------------------------------------------------------------------
+    // Trajectory: the pair poses chained into one camera path and one point map with a common scale
+    // (include/tinyorb.h; not in the reference).  Declarations only: the calls follow
+    // orb_pose_consecutive on the last batch.
+    // ------------------------------------------------------------------------------------------------------------
+    /// `OrbTrajectoryParams`: a zeroed value means the defaults.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbTrajectoryParams {
+        pub min_shared: u32,          // 0: 8
+        pub scale_tolerance: f32,     // 0: 0.1
+        pub consistent_permille: u32, // 0: 500
+        pub flags: u32,               // ORB_TRAJ_NEED_PARALLAX
+        pub reserved: [u32; 4],       // must be 0
+    }
+    /// `OrbFramePose`: X_f = R X_origin + t, R row-major, t in units of the baseline of the pair (origin, origin + 1).
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbFramePose {
+        pub r: [f32; 9],
+        pub t: [f32; 3],
+        pub scale: f32,
+        pub step: f32,
+        pub origin: u32,
+        pub shared: u32,
+        pub consistent: u32,
+        pub status: u32,
+        pub reserved: [u32; 2],
+    }
+    pub const ORB_TRAJ_NEED_PARALLAX: u32 = 1;
+    pub const ORB_TRAJ_CHAINED: u32 = 0;
+    pub const ORB_TRAJ_START: u32 = 1;
+    pub const ORB_TRAJ_RESTART_FEW: u32 = 2;
+    pub const ORB_TRAJ_RESTART_SPREAD: u32 = 3;
+    pub const ORB_TRAJ_LOST: u32 = 4;
+    pub const ORB_TRAJ_ORIGIN: u32 = 5;
+
+    extern "C" {
+        pub fn orb_trajectory_consecutive(p: *mut c_void, n_frames: u32, params: *const OrbTrajectoryParams, stream: *mut c_void) -> c_int;
+        pub fn orb_trajectory_read(p: *mut c_void, frame: u32, pose: *mut OrbFramePose, points: *mut OrbPoint, n: usize) -> c_int;
+    }
+
+    // ------------------------------------------------------------------------------------------------------------
     // Batched, multi-GPU entry (include/tinyorb.h "one node, several GPUs"; not in the reference, which drives one
     // wgpu device).  The same calls, in the same order, are exercised from C by examples/node_batch.c, which the
     // repository's GPU tests compile with gcc and run -- that C program is the verified twin of this block.

@@ -31,6 +31,7 @@
 #include "orb_kernels_guide.h"
 #include "orb_kernels_band.h"
 #include "orb_kernels_pose.h"
+#include "orb_kernels_traj.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -65,15 +66,16 @@ struct ProfSpan {
 // The stages that run after extraction.  Each owns ONE set of buffers per program, shared by both output sets and by whatever stream
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, which the entry point names; and the stages that read what it overwrites, kReadersOf[stage].
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_COUNT };
 const uint32_t kReadersOf[ST_COUNT] = {
-    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it)
+    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE | 1u << ST_TRAJ,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it; trajectory pairs the points of two pairs by it)
     1u << ST_GUIDE | 1u << ST_TRACK,                  // verify: verify.model (guided, ORB_GUIDE_VERIFIED), verify.mask (track, ORB_TRACK_VERIFIED)
     1u << ST_BAND | 1u << ST_POSE,                    // epi: epi.model (band, ORB_BAND_VERIFIED; pose), epi.mask (pose)
     1u << ST_TRACK,                                   // guide: d_gmatch (track, ORB_TRACK_GUIDED)
     0u,                                               // track: read back by the host
     0u,                                               // band: d_bmatch is read back by the host
-    0u,                                               // pose: read back by the host
+    1u << ST_TRAJ,                                    // pose: d_pose, d_ppoints (trajectory)
+    0u,                                               // trajectory: read back by the host
 };
 
 // The last call of a stage
@@ -172,6 +174,11 @@ struct OrbProgram {
     uint32_t* d_pose = nullptr;           // [max_batch][16] OrbPairPose
     float4* d_ppoints = nullptr;          // [max_batch][max_features] OrbPoint
     uint32_t* d_pcount = nullptr;         // [max_batch][kPoseCounters]
+    // orb_trajectory_consecutive (orb_kernels_traj.h)
+    uint32_t* d_jframe = nullptr;         // [max_batch][20] OrbFramePose
+    float4* d_jmap = nullptr;             // [max_batch][max_features] OrbPoint in the origin's frame and unit
+    uint32_t* d_jratio = nullptr;         // [max_batch][max_features] the bits of a joint's ratios
+    uint32_t* d_jjoint = nullptr;         // [max_batch][kTrajJointWords]
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -346,6 +353,12 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         add(&p->d_pose, B * sizeof(OrbPairPose));
         add(&p->d_ppoints, B * cap * sizeof(OrbPoint));
         add(&p->d_pcount, B * kPoseCounters * sizeof(uint32_t));
+        break;
+    case ST_TRAJ:
+        add(&p->d_jframe, B * sizeof(OrbFramePose));
+        add(&p->d_jmap, B * cap * sizeof(OrbPoint));
+        add(&p->d_jratio, B * cap * sizeof(uint32_t));
+        add(&p->d_jjoint, B * kTrajJointWords * sizeof(uint32_t));
         break;
     }
     return n;
@@ -2590,6 +2603,65 @@ int orb_pose_read(OrbProgram* p, uint32_t pair, OrbPairPose* pose, OrbPoint* poi
     if (n > cap) n = cap;
     if (pose) HIP_TRY(p, hipMemcpy(pose, p->d_pose + (size_t)pair * kPoseWords, sizeof(OrbPairPose), hipMemcpyDeviceToHost));
     if (n) HIP_TRY(p, hipMemcpy(points, p->d_ppoints + (size_t)pair * cap, n * sizeof(OrbPoint), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_trajectory_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrajectoryParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbTrajectoryParams g{};
+    if (params) g = *params;
+    if (g.reserved[0] | g.reserved[1] | g.reserved[2] | g.reserved[3]) return fail(p, ORB_EINVAL, "trajectory_consecutive: reserved words must be 0");
+    if (g.flags & ~ORB_TRAJ_NEED_PARALLAX) return fail(p, ORB_EINVAL, "trajectory_consecutive: unknown flags 0x%x", g.flags);
+    if (!(std::isfinite(g.scale_tolerance) && g.scale_tolerance >= 0.0f) || g.consistent_permille > 1000u)
+        return fail(p, ORB_EINVAL, "trajectory_consecutive: scale_tolerance must be finite and >= 0, consistent_permille 0..1000");
+    const size_t cap = p->cfg.max_features;
+    if (cap > (1u << 23)) return fail(p, ORB_EINVAL, "trajectory_consecutive: max_features above 2^23");
+    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_POSE];
+    if (!stage_fresh(p, m) || !stage_fresh(p, v))
+        return fail(p, ORB_ESTATE, "trajectory_consecutive: no orb_match_consecutive and orb_pose_consecutive of the current batch and output set");
+    const uint32_t most = std::min(4096u, v.extent + 1u);
+    if (n_frames < 2u || n_frames > most) return fail(p, ORB_EINVAL, "trajectory_consecutive: need 2..%u frames (the last pose call's pairs + 1, at most 4096)", most);
+    if (!g.min_shared) g.min_shared = 8u;
+    if (g.scale_tolerance == 0.0f) g.scale_tolerance = 0.1f;
+    if (!g.consistent_permille) g.consistent_permille = 500u;
+    HIP_TRY(p, hipSetDevice(p->device));
+    if (int rc = alloc_all_or_none(p, ST_TRAJ, "trajectory_consecutive")) return rc;
+    hipStream_t s;
+    if (int rc = stage_begin(p, ST_TRAJ, stream, 1u << ST_MATCH | 1u << ST_POSE, &s)) return rc;
+    TrajArgs a{};
+    a.counts = p->d_counts;
+    a.matches = p->d_matches;
+    a.cap = (uint32_t)cap;
+    a.n_frames = n_frames;
+    a.poses = p->d_pose;
+    a.points = p->d_ppoints;
+    a.min_shared = g.min_shared;
+    a.tol = g.scale_tolerance;
+    a.permille = g.consistent_permille;
+    a.need_parallax = g.flags & ORB_TRAJ_NEED_PARALLAX;
+    a.ratios = p->d_jratio;
+    a.joints = p->d_jjoint;
+    a.frames = p->d_jframe;
+    a.map = p->d_jmap;
+    static_assert(sizeof(OrbFramePose) == kTrajFrameWords * sizeof(uint32_t) && sizeof(OrbTrajectoryParams) == 32, "trajectory layouts");
+    if (n_frames > 2u) hipLaunchKernelGGL(k_traj_joint, dim3(n_frames - 2u), dim3(kTrajThreads), 0, s, a);
+    hipLaunchKernelGGL(k_traj_chain, dim3(1), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_traj_map, dim3(n_frames - 1u, (unsigned)((cap + kTrajThreads - 1u) / kTrajThreads)), dim3(kTrajThreads), 0, s, a);
+    HIP_TRY(p, hipMemsetAsync(p->d_jmap + (size_t)(n_frames - 1u) * cap, 0, cap * sizeof(OrbPoint), s));  // TJ-6: the last frame's row
+    return stage_end(p, ST_TRAJ, s, n_frames);  // p->last_stream stays, as after a guided call
+}
+
+int orb_trajectory_read(OrbProgram* p, uint32_t frame, OrbFramePose* pose, OrbPoint* points, size_t n) {
+    if (!p) return ORB_EINVAL;
+    const Stage& last = p->stage[ST_TRAJ];
+    if (!last.extent) return fail(p, ORB_ESTATE, "trajectory_read before trajectory_consecutive");
+    if (frame >= last.extent || (!points && n)) return fail(p, ORB_EINVAL, "trajectory_read: frame %u of %u, or points is NULL", frame, last.extent);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    if (pose) HIP_TRY(p, hipMemcpy(pose, p->d_jframe + (size_t)frame * kTrajFrameWords, sizeof(OrbFramePose), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(points, p->d_jmap + (size_t)frame * cap, n * sizeof(OrbPoint), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

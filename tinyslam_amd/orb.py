@@ -56,6 +56,12 @@ POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("inliers", "<u4"
 POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("flags", "<u4")])
 ORB_POSE_OK, ORB_POSE_NOMODEL, ORB_POSE_FEW, ORB_POSE_AMBIGUOUS, ORB_POSE_LOW_PARALLAX = 0, 1, 2, 3, 4
 ORB_POINT_GOOD, ORB_POINT_PARALLAX = 1, 2
+# trajectory and map in one frame and one unit (orb_trajectory_consecutive): OrbFramePose (80 B), its status,
+# the flag of OrbTrajectoryParams
+FRAME_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4"), ("step", "<f4"), ("origin", "<u4"),
+                             ("shared", "<u4"), ("consistent", "<u4"), ("status", "<u4"), ("reserved", "<u4", (2,))])
+ORB_TRAJ_CHAINED, ORB_TRAJ_START, ORB_TRAJ_RESTART_FEW, ORB_TRAJ_RESTART_SPREAD, ORB_TRAJ_LOST, ORB_TRAJ_ORIGIN = 0, 1, 2, 3, 4, 5
+ORB_TRAJ_NEED_PARALLAX = 1
 # feature tracks and keyframes (orb_track_consecutive): the link source, OrbTrack (16 B), OrbTrackFrame (32 B)
 ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
 TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
@@ -82,6 +88,7 @@ EXPORTS = [
     "orb_verify_consecutive", "orb_verify_read", "orb_match_guided", "orb_match_guided_read",
     "orb_track_consecutive", "orb_track_read", "orb_track_frames", "orb_verify_epipolar", "orb_verify_epipolar_read",
     "orb_match_epipolar", "orb_match_epipolar_read", "orb_pose_consecutive", "orb_pose_read",
+    "orb_trajectory_consecutive", "orb_trajectory_read",
 ]
 
 
@@ -130,6 +137,15 @@ class _PoseParams(ctypes.Structure):
     _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
                 ("max_reproj_px", ctypes.c_float), ("max_cos_parallax", ctypes.c_float), ("min_good", ctypes.c_uint32),
                 ("ambiguity_permille", ctypes.c_uint32)]
+
+
+class _TrajectoryParams(ctypes.Structure):
+    """OrbTrajectoryParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("min_shared", ctypes.c_uint32), ("scale_tolerance", ctypes.c_float), ("consistent_permille", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+OrbTrajectoryParams = _TrajectoryParams
 
 
 class _TrackParams(ctypes.Structure):
@@ -219,6 +235,8 @@ def load_library(path=None):
     L.orb_match_epipolar_read.argtypes = [vp, u32, vp, sz]
     L.orb_pose_consecutive.argtypes = [vp, u32, ctypes.POINTER(_PoseParams), vp]
     L.orb_pose_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_trajectory_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrajectoryParams), vp]
+    L.orb_trajectory_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -654,6 +672,26 @@ class OrbProgram:
         rec = np.zeros((), dtype=POSE_DTYPE)
         pts = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=POINT_DTYPE)
         self._check(self._lib.orb_pose_read(self._handle(), pair, _ptr(rec), _ptr(pts) if len(pts) else None, len(pts)))
+        return rec, pts
+
+    def trajectory_consecutive(self, n_frames, min_shared=0, scale_tolerance=0.0, consistent_permille=0, flags=0, stream=None,
+                               reserved=(0, 0, 0, 0)):
+        """Camera path and point map of the last batch in one frame and one unit (not in the reference; DESIGN.md section 20,
+        TJ-1..TJ-7): the landmarks that two consecutive pairs of the last pose_consecutive both triangulated give the ratio of the
+        pairs' baselines (the lower median of the depth ratios), and the pair poses are chained with it.  A joint holds when it has
+        min_shared ratios (0: 8) of which consistent_permille (0: 500) per thousand lie within scale_tolerance (0: 0.1) of the
+        median; otherwise a new segment starts.  flags: ORB_TRAJ_NEED_PARALLAX.  Asynchronous on `stream` (None: as match_guided
+        chooses)."""
+        prm = _TrajectoryParams(min_shared, float(np.float32(scale_tolerance)), consistent_permille, flags, (ctypes.c_uint32 * 4)(*reserved))
+        self._check(self._lib.orb_trajectory_consecutive(self._handle(), n_frames, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def trajectory_read(self, frame, n=None):
+        """(record of FRAME_POSE_DTYPE, POINT_DTYPE[min(n, max_features)]; n None: max_features) of the last trajectory_consecutive
+        -- synchronises.  The record takes the frame of `origin` to camera `frame`'s; the points are those of the pair
+        (frame, frame + 1), indexed as pose_read's, in the frame and unit of the origin of frame + 1."""
+        rec = np.zeros((), dtype=FRAME_POSE_DTYPE)
+        pts = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=POINT_DTYPE)
+        self._check(self._lib.orb_trajectory_read(self._handle(), frame, _ptr(rec), _ptr(pts) if len(pts) else None, len(pts)))
         return rec, pts
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
