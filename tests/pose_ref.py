@@ -33,8 +33,8 @@ def _cof(m):
     return _cross(r1, r2) + _cross(r2, r0) + _cross(r0, r1)
 
 
-def essential(f, fx, fy, cx, cy):
-    """RP-2: E = K^T (F K) entry by entry, then divided by n = sqrt(0.5 sum E^2) (row-major sum).  None: n not finite or not > 0."""
+def essential_raw(f, fx, fy, cx, cy):
+    """RP-2 before the division: (E = K^T (F K) entry by entry, n = sqrt(0.5 sum E^2) (row-major sum))."""
     f = [F(v) for v in f]
     g = []
     for r in range(3):
@@ -43,14 +43,19 @@ def essential(f, fx, fy, cx, cy):
     s = e[0] * e[0]
     for v in e[1:]:
         s = s + v * v
-    n = np.sqrt(F(0.5) * s)
+    return e, np.sqrt(F(0.5) * s)
+
+
+def essential(f, fx, fy, cx, cy):
+    """RP-2: essential_raw's E divided by its n.  None: n not finite or not > 0."""
+    e, n = essential_raw(f, fx, fy, cx, cy)
     if not (np.isfinite(n) and n > F(0)):
         return None
     return [v / n for v in e]
 
 
-def baseline(e):
-    """RP-3: T = I - E E^T, i the first index of the largest T[i][i], t = T[i] / sqrt(T[i][i]).  None: that entry is not > 0."""
+def baseline_row(e):
+    """RP-3: T = I - E E^T (list of 9) and i, the first index of the largest T[i][i]."""
     T = []
     for i in range(3):
         for j in range(3):
@@ -61,6 +66,13 @@ def baseline(e):
         i, best = 1, T[4]
     if T[8] > best:
         i, best = 2, T[8]
+    return T, i
+
+
+def baseline(e):
+    """RP-3: t = T[i] / sqrt(T[i][i]) for baseline_row's T and i.  None: that entry is not > 0."""
+    T, i = baseline_row(e)
+    best = T[4 * i]
     if not best > F(0):
         return None
     q = np.sqrt(best)
@@ -78,6 +90,16 @@ def polar(r):
     return r, ok
 
 
+def rotations_raw(e, t):
+    """RP-4 before the polar steps: (Ra, Rb) = Cof(E) -+ [t]x E, lists of 9."""
+    c = _cof(e)
+    s = [None] * 9
+    for col in range(3):  # S = [t]x E: column by column t x E[:, col]
+        x = _cross(t, [e[col], e[3 + col], e[6 + col]])
+        s[col], s[3 + col], s[6 + col] = x
+    return [c[k] - s[k] for k in range(9)], [c[k] + s[k] for k in range(9)]
+
+
 def candidates(f, fx, fy, cx, cy):
     """RP-2..RP-4: None (no model), or (Ra, Rb, t, valid_a, valid_b) with the rotations as lists of 9 and t of 3 np.float32."""
     with np.errstate(all="ignore"):
@@ -87,13 +109,9 @@ def candidates(f, fx, fy, cx, cy):
         t = baseline(e)
         if t is None:
             return None
-        c = _cof(e)
-        s = [None] * 9
-        for col in range(3):  # S = [t]x E: column by column t x E[:, col]
-            x = _cross(t, [e[col], e[3 + col], e[6 + col]])
-            s[col], s[3 + col], s[6 + col] = x
-        ra, va = polar([c[k] - s[k] for k in range(9)])
-        rb, vb = polar([c[k] + s[k] for k in range(9)])
+        ra0, rb0 = rotations_raw(e, t)
+        ra, va = polar(ra0)
+        rb, vb = polar(rb0)
         if not (va or vb):
             return None
         return ra, rb, t, va, vb
