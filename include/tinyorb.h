@@ -689,6 +689,13 @@ int orb_debug_angle_code(OrbProgram *p, const float *cy, const float *cx, uint32
  * stored [code][lane 0..63][test lane + 64 e, e = 0..3][a, b].  Writes min(n_entries, codes * 512) values; *codes and *pitch
  * (either may be NULL) say what the table was built for. */
 int orb_debug_rot_table(OrbProgram *p, int16_t *dst, size_t n_entries, uint32_t *codes, uint32_t *pitch);
+/* For tests: device pointers of what orb_trajectory_consecutive reads besides the raw counters (any of the three may be NULL):
+ * matches[max_batch][max_features] OrbMatch (row f: the queries of frame f), poses[max_batch] OrbPairPose and
+ * points[max_batch][max_features] OrbPoint (row f: pair (f, f + 1)).  ORB_ESTATE until an orb_match_consecutive and an
+ * orb_pose_consecutive call have allocated them.  A test that writes them orders its own writes: orb_batch_sync / orb_stream_sync
+ * on every stream a stage ran on before writing, a device synchronise after writing and before the next call.  No stage's
+ * freshness state is touched: the library goes on treating the buffers as the results of its last match and pose calls. */
+int orb_debug_pose_buffers(OrbProgram *p, void **matches, void **poses, void **points);
 
 /* ---- measurement ---- */
 #define ORB_KERNEL_COUNT 25

@@ -38,8 +38,10 @@ def test_structs_and_constants(tinyorb):
 
 def test_exports_and_null_program(tinyorb):
     L = tinyorb.load_library()
-    for n in ("orb_trajectory_consecutive", "orb_trajectory_read"):
+    for n in ("orb_trajectory_consecutive", "orb_trajectory_read", "orb_debug_pose_buffers"):
         assert n in tinyorb.EXPORTS and hasattr(L, n)
+    out = ctypes.c_void_p()
+    assert L.orb_debug_pose_buffers(None, ctypes.byref(out), None, None) == tinyorb.ORB_EINVAL and not out.value
     prm = tinyorb.OrbTrajectoryParams()
     assert L.orb_trajectory_consecutive(None, 2, ctypes.byref(prm), None) == tinyorb.ORB_EINVAL
     assert L.orb_trajectory_consecutive(None, 2, None, None) == tinyorb.ORB_EINVAL

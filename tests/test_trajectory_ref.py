@@ -1,12 +1,13 @@
 """The CPU restatement of the trajectory stage (tests/trajectory_ref.py, TJ-1..TJ-7 of DESIGN.md section 20): hand-built pose and point
-arrays that pin the definition (they have no GPU counterpart), and its accuracy on constructed camera paths through the project's own
-restatements: match_ref -> epipolar_ref.verify_pair -> pose_ref.pose_pair -> trajectory."""
+arrays that pin the definition, and its accuracy on constructed camera paths through the project's own restatements: match_ref ->
+epipolar_ref.verify_pair -> pose_ref.pose_pair -> trajectory."""
 import numpy as np
 import pytest
 
 import constructed as C
 import epipolar_ref as er
 import pose_ref as pr
+import trajectory_cases as tc
 import trajectory_ref as tr
 from tinyslam_amd import orb
 
@@ -17,26 +18,16 @@ GOOD, PAR = orb.ORB_POINT_GOOD, orb.ORB_POINT_PARALLAX
 IDENTITY = np.eye(3, dtype=F).ravel()
 
 
-# ---- hand-built inputs ---------------------------------------------------------------------------------------------------------
-def _pose(status=orb.ORB_POSE_OK, r=IDENTITY, t=(0, 0, 0)):
-    p = np.zeros((), orb.POSE_DTYPE)
-    p["r"], p["t"], p["status"] = r, t, status
-    return p
+# ---- hand-built inputs (the builders are tests/trajectory_cases.py's, which the GPU tests share) -------------------------------
+_pose = tc.pose
 
 
 def _joint_case(rho, index=None, flags_a=None, flags_b=None, zb=None, **params):
     """Three frames, both pairs OK with R = I and t = 0, so that Yz = Xz exactly; pair 0's point i is (0, 0, rho[i]) and pair 1's
     point j is (0, 0, zb[j]) (1 by default): the ratio of i is rho[i] / zb[index[i]], exactly rho[i] by default."""
-    n = len(rho)
-    index = np.arange(n) if index is None else np.asarray(index)
-    cap = n + 3
-    pa, pb = np.zeros(cap, orb.POINT_DTYPE), np.zeros(cap, orb.POINT_DTYPE)
-    pa["z"][:n], pa["flags"][:n] = rho, GOOD if flags_a is None else flags_a
-    pb["z"][:n], pb["flags"][:n] = 1.0 if zb is None else zb, GOOD if flags_b is None else flags_b
-    m = np.zeros(n, orb.MATCH_DTYPE)
-    m["index"] = index
-    frames, world = tr.trajectory([n, n, n], [m, m], [_pose(), _pose()], [pa, pb], cap, **params)
-    return frames, world
+    if index is not None:
+        index = np.where(np.asarray(index) == orb.ORB_MATCH_NONE, tc.NONE, np.asarray(index))
+    return tc.run_case(tc.joint_case("", rho, index=index, flags_a=flags_a, flags_b=flags_b, zb=zb), **params)
 
 
 def test_verdicts_and_the_lower_median():
@@ -144,14 +135,9 @@ CHAIN_ORTH = 2.23e-7
 
 
 def test_a_4096_frame_chain_stays_orthonormal():
-    n, k = 4096, 8
-    Rs = (tr.rot("y", 0.7) @ tr.rot("x", 0.2) @ tr.rot("z", 0.1)).astype(F).ravel()
-    pose = _pose(r=Rs, t=(0.6, 0.0, 0.8))
-    pts = np.zeros(k, orb.POINT_DTYPE)
-    pts["z"], pts["flags"] = F(0.8) / (F(1) - Rs[8]), GOOD  # r22 z + t2 = z up to rounding: every g is 1 within a few ulp
-    m = np.zeros(k, orb.MATCH_DTYPE)
-    m["index"] = np.arange(k)
-    fr, _ = tr.trajectory([k] * n, [m] * (n - 1), [pose] * (n - 1), [pts] * (n - 1), k)
+    n = 4096
+    b, Rs = tc.long_chain(n)
+    fr, _ = tc.reference(b)
     assert (fr["status"][2:] == orb.ORB_TRAJ_CHAINED).all() and (fr["origin"] == 0).all() and np.isfinite(fr["scale"]).all()
     R = fr["r"].astype(np.float64).reshape(n, 3, 3)
     orth = np.abs(np.einsum("nki,nkj->nij", R, R) - np.eye(3)).max()

@@ -2802,6 +2802,16 @@ int orb_batch_device_buffers(OrbProgram* p, void** counts, void** corners, void*
     return ORB_OK;
 }
 
+int orb_debug_pose_buffers(OrbProgram* p, void** matches, void** poses, void** points) {
+    if (!p) return ORB_EINVAL;
+    if (!p->d_matches || !p->d_pose || !p->d_ppoints)
+        return fail(p, ORB_ESTATE, "debug_pose_buffers before orb_match_consecutive and orb_pose_consecutive");
+    if (matches) *matches = p->d_matches;
+    if (poses) *poses = p->d_pose;
+    if (points) *points = p->d_ppoints;
+    return ORB_OK;
+}
+
 int orb_level_size(const OrbProgram* p, uint32_t level, uint32_t* width, uint32_t* height) {
     if (!p || level >= p->pyr.depth) return ORB_EINVAL;
     if (width) *width = p->pyr.w[level];

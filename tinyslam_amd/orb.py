@@ -88,7 +88,7 @@ EXPORTS = [
     "orb_verify_consecutive", "orb_verify_read", "orb_match_guided", "orb_match_guided_read",
     "orb_track_consecutive", "orb_track_read", "orb_track_frames", "orb_verify_epipolar", "orb_verify_epipolar_read",
     "orb_match_epipolar", "orb_match_epipolar_read", "orb_pose_consecutive", "orb_pose_read",
-    "orb_trajectory_consecutive", "orb_trajectory_read",
+    "orb_trajectory_consecutive", "orb_trajectory_read", "orb_debug_pose_buffers",
 ]
 
 
@@ -219,6 +219,7 @@ def load_library(path=None):
     L.orb_batch_select_output.argtypes = [vp, u32]
     L.orb_batch_device_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.orb_level_size.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.orb_debug_pose_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.orb_debug_read_plane.argtypes = [vp, u32, ctypes.c_int, u32, vp, sz]
     L.orb_debug_f32_to_f16.argtypes = [vp, vp, vp, sz]
     L.orb_debug_angle_code.argtypes = [vp, vp, vp, vp, sz]
@@ -725,6 +726,13 @@ class OrbProgram:
     def batch_device_buffers(self):
         a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._check(self._lib.orb_batch_device_buffers(self._handle(), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def debug_pose_buffers(self):
+        """For tests: device addresses of (matches [max_batch][max_features] MATCH_DTYPE, poses [max_batch] POSE_DTYPE, points
+        [max_batch][max_features] POINT_DTYPE), what trajectory_consecutive reads.  The caller orders its own writes."""
+        a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.orb_debug_pose_buffers(self._handle(), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
 
     # ---- inspection / measurement -------------------------------------------------------------
