@@ -610,6 +610,59 @@ int orb_trajectory_consecutive(OrbProgram *p, uint32_t n_frames, const OrbTrajec
  * before any call, ORB_EINVAL for a frame outside the call's frames or points NULL with n > 0. */
 int orb_trajectory_read(OrbProgram *p, uint32_t frame, OrbFramePose *pose, OrbPoint *points, size_t n);
 
+/* ---- absolute pose from the previous pair's map points: PnP RANSAC (NOT in the reference; definition LO-1..LO-7 in DESIGN.md
+ * section 21) ----
+ * Pair f - 1 of the last orb_pose_consecutive triangulated landmarks from cameras f - 1 and f.  The matcher's records carry each
+ * of them on: slot i of frame f - 1 matched keypoint j of frame f, and j matched keypoint k of frame f + 1 (that second hop under
+ * max_distance and ratio).  A GOOD point X of pair f - 1, moved into camera f's frame by that pair's pose (Y = R X + t), and the
+ * level-0 position of k are a 3D-2D correspondence.  They give the pose of camera f + 1 relative to camera f with a metric
+ * translation, in units of pair f - 1's baseline, without pair f's fundamental matrix: a RANSAC over six-point DLT samples (the
+ * first 11 of the 12 equations, solved by complete pivoting; sign from det, scale from the Frobenius norm, three polar steps),
+ * scored by the reprojection error in frame f + 1, then four Gauss-Newton steps on the winner's inliers, kept when they hold at
+ * least 15/16 of the winner's count.  So a pair with little or no translation, whose two-view pose is LOW_PARALLAX or AMBIGUOUS,
+ * still gets a pose while the map of the pair before is in view.  Binary32 arithmetic in a fixed order, no fused operations: a
+ * CPU restatement gives the same bits.  Nothing is fed back into orb_trajectory_consecutive. */
+typedef struct {            /* zero-initialised is NOT valid: fx, fy must be > 0 */
+    float fx, fy, cx, cy;   /* the intrinsics given to orb_pose_consecutive */
+    float max_reproj_px;    /* frame f+1 reprojection error an inlier may have (0: 2.0); finite, >= 0 */
+    uint32_t hypotheses;    /* minimal samples per pair, 1..4096 (0: 512) */
+    uint32_t max_distance;  /* second hop: a match is a candidate iff distance <= this (0: 64); 0..256 */
+    float ratio;            /* ... and distance < ratio * second (0: 0.8); finite, >= 0 */
+    uint32_t seed;          /* of the sampling; the same seed gives the same result */
+    uint32_t reserved[7];   /* must be 0 (ORB_EINVAL otherwise) */
+} OrbLocalizeParams;        /* 64 bytes */
+
+#define ORB_LOCALIZE_OK 0u         /* the refit was kept */
+#define ORB_LOCALIZE_NOMAP 1u      /* pair 0, or the pose of pair f - 1 is not ORB_POSE_OK: all 0 */
+#define ORB_LOCALIZE_FEW 2u        /* fewer than 6 correspondences: all 0 */
+#define ORB_LOCALIZE_DEGENERATE 3u /* no valid hypothesis (coplanar, collinear or repeated points): all 0 */
+#define ORB_LOCALIZE_MINIMAL 4u    /* the refit failed or lost more than 1/16 of the inliers: the winning six-point model */
+
+typedef struct {
+    float r[9];             /* row-major R, X(f+1) = R X(f) + t */
+    float t[3];             /* in units of the baseline of pair f - 1 */
+    float step;             /* |t|: the baseline of pair f over that of pair f - 1 (compare OrbFramePose.step) */
+    uint32_t candidates;    /* 3D-2D correspondences */
+    uint32_t inliers;       /* of them: within max_reproj_px under the model written */
+    uint32_t hypothesis;    /* the winning sample */
+    uint32_t status;        /* ORB_LOCALIZE_* */
+    uint32_t reserved[3];   /* 0 */
+} OrbFrameFix;              /* 80 bytes */
+
+/* Fixes of the pairs (f, f+1), f in [0, n_frames - 1), of the last batch (pair 0 is NOMAP).  ORB_EINVAL for a NULL program or
+ * params, fx or fy not finite or not > 0, cx or cy not finite, another parameter out of range, a reserved word that is not 0, or
+ * n_frames not in 3 .. the last orb_pose_consecutive's pairs + 1; ORB_ESTATE unless the last orb_match_consecutive and the last
+ * orb_pose_consecutive are both of the current batch and output set.  Asynchronous on `stream` (NULL: as orb_match_guided
+ * chooses; the call does not change it), ordered behind the matcher's and the pose stage's last calls and the last call of its
+ * own when they ran on another stream; orb_match_consecutive and orb_pose_consecutive wait for such a call on another stream
+ * before they overwrite what it reads.  Result buffers of its own (allocated by the first call): no other stage's results are
+ * ever written. */
+int orb_localize_consecutive(OrbProgram *p, uint32_t n_frames, const OrbLocalizeParams *params, void *stream);
+/* Copy the record of pair `pair` of the last orb_localize_consecutive call (fix may be NULL) and up to n inlier bytes -- byte i is
+ * 1 iff slot i of frame pair - 1 (indexed as orb_match_read) gave a correspondence that is an inlier of the model written -- to the
+ * host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside its pairs or inliers NULL with n > 0. */
+int orb_localize_read(OrbProgram *p, uint32_t pair, OrbFrameFix *fix, uint8_t *inliers, size_t n);
+
 /* ---- feature tracks and keyframes (NOT in the reference; definition TK-1..TK-5 in DESIGN.md section 15) ----
  * Over the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: query i of frame f links to target j of frame f+1 by the
  * source's record (VERIFIED: the matcher's record where the last verification's inlier byte is 1; GUIDED / MATCHED: the last

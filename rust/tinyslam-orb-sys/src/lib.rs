@@ -289,6 +289,51 @@ pub mod orb {
     }
 
     // ------------------------------------------------------------------------------------------------------------
+    // Localisation: the pose of camera f + 1 relative to camera f from the map points of pair f - 1, PnP RANSAC
+    // (include/tinyorb.h; not in the reference).  Declarations only: the calls follow
+    // orb_pose_consecutive on the last batch.
+    // ------------------------------------------------------------------------------------------------------------
+    /// `OrbLocalizeParams`: NOT valid zeroed -- fx and fy must be > 0 (the intrinsics given to orb_pose_consecutive); the other zero
+    /// fields mean the defaults.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbLocalizeParams {
+        pub fx: f32,
+        pub fy: f32,
+        pub cx: f32,
+        pub cy: f32,
+        pub max_reproj_px: f32, // 0: 2.0
+        pub hypotheses: u32,    // 0: 512; at most 4096
+        pub max_distance: u32,  // 0: 64
+        pub ratio: f32,         // 0: 0.8
+        pub seed: u32,
+        pub reserved: [u32; 7], // must be 0
+    }
+    /// `OrbFrameFix`: X_{f+1} = R X_f + t, R row-major, t in units of the baseline of pair f - 1.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbFrameFix {
+        pub r: [f32; 9],
+        pub t: [f32; 3],
+        pub step: f32,
+        pub candidates: u32,
+        pub inliers: u32,
+        pub hypothesis: u32,
+        pub status: u32,
+        pub reserved: [u32; 3],
+    }
+    pub const ORB_LOCALIZE_OK: u32 = 0;
+    pub const ORB_LOCALIZE_NOMAP: u32 = 1;
+    pub const ORB_LOCALIZE_FEW: u32 = 2;
+    pub const ORB_LOCALIZE_DEGENERATE: u32 = 3;
+    pub const ORB_LOCALIZE_MINIMAL: u32 = 4;
+
+    extern "C" {
+        pub fn orb_localize_consecutive(p: *mut c_void, n_frames: u32, params: *const OrbLocalizeParams, stream: *mut c_void) -> c_int;
+        pub fn orb_localize_read(p: *mut c_void, pair: u32, fix: *mut OrbFrameFix, inliers: *mut u8, n: usize) -> c_int;
+    }
+
+    // ------------------------------------------------------------------------------------------------------------
     // Batched, multi-GPU entry (include/tinyorb.h "one node, several GPUs"; not in the reference, which drives one
     // wgpu device).  The same calls, in the same order, are exercised from C by examples/node_batch.c, which the
     // repository's GPU tests compile with gcc and run -- that C program is the verified twin of this block.

@@ -32,6 +32,7 @@
 #include "orb_kernels_band.h"
 #include "orb_kernels_pose.h"
 #include "orb_kernels_traj.h"
+#include "orb_kernels_localize.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -66,16 +67,17 @@ struct ProfSpan {
 // The stages that run after extraction.  Each owns ONE set of buffers per program, shared by both output sets and by whatever stream
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, which the entry point names; and the stages that read what it overwrites, kReadersOf[stage].
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_COUNT };
 const uint32_t kReadersOf[ST_COUNT] = {
-    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE | 1u << ST_TRAJ,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it; trajectory pairs the points of two pairs by it)
+    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE | 1u << ST_TRAJ | 1u << ST_LOCALIZE,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it; trajectory pairs the points of two pairs by it; localize carries a point over two pairs by it)
     1u << ST_GUIDE | 1u << ST_TRACK,                  // verify: verify.model (guided, ORB_GUIDE_VERIFIED), verify.mask (track, ORB_TRACK_VERIFIED)
     1u << ST_BAND | 1u << ST_POSE,                    // epi: epi.model (band, ORB_BAND_VERIFIED; pose), epi.mask (pose)
     1u << ST_TRACK,                                   // guide: d_gmatch (track, ORB_TRACK_GUIDED)
     0u,                                               // track: read back by the host
     0u,                                               // band: d_bmatch is read back by the host
-    1u << ST_TRAJ,                                    // pose: d_pose, d_ppoints (trajectory)
+    1u << ST_TRAJ | 1u << ST_LOCALIZE,                // pose: d_pose, d_ppoints (trajectory, localize)
     0u,                                               // trajectory: read back by the host
+    0u,                                               // localize: read back by the host
 };
 
 // The last call of a stage
@@ -179,6 +181,14 @@ struct OrbProgram {
     float4* d_jmap = nullptr;             // [max_batch][max_features] OrbPoint in the origin's frame and unit
     uint32_t* d_jratio = nullptr;         // [max_batch][max_features] the bits of a joint's ratios
     uint32_t* d_jjoint = nullptr;         // [max_batch][kTrajJointWords]
+    // orb_localize_consecutive (orb_kernels_localize.h)
+    uint32_t* d_lfix = nullptr;           // [max_batch][20] OrbFrameFix
+    float4* d_lreca = nullptr;            // [max_batch][max_features] candidates: the landmark in camera f's frame
+    float4* d_lrecb = nullptr;            // [max_batch][max_features] candidates: the keypoint of frame f + 1 and its ray
+    uint32_t* d_lcand = nullptr;          // [max_batch][max_features] candidate of each slot of frame f - 1
+    uint32_t* d_ln = nullptr;             // [max_batch] candidates per pair
+    unsigned long long* d_lkeys = nullptr; // [max_batch][kVerifyMaxHyp]
+    uint8_t* d_lmask = nullptr;           // [max_batch][max_features] inlier bytes
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -359,6 +369,15 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         add(&p->d_jmap, B * cap * sizeof(OrbPoint));
         add(&p->d_jratio, B * cap * sizeof(uint32_t));
         add(&p->d_jjoint, B * kTrajJointWords * sizeof(uint32_t));
+        break;
+    case ST_LOCALIZE:
+        add(&p->d_lfix, B * sizeof(OrbFrameFix));
+        add(&p->d_lreca, B * cap * sizeof(float4));
+        add(&p->d_lrecb, B * cap * sizeof(float4));
+        add(&p->d_lcand, B * cap * sizeof(uint32_t));
+        add(&p->d_ln, B * sizeof(uint32_t));
+        add(&p->d_lkeys, B * kVerifyMaxHyp * sizeof(unsigned long long));
+        add(&p->d_lmask, B * cap);
         break;
     }
     return n;
@@ -2662,6 +2681,77 @@ int orb_trajectory_read(OrbProgram* p, uint32_t frame, OrbFramePose* pose, OrbPo
     if (n > cap) n = cap;
     if (pose) HIP_TRY(p, hipMemcpy(pose, p->d_jframe + (size_t)frame * kTrajFrameWords, sizeof(OrbFramePose), hipMemcpyDeviceToHost));
     if (n) HIP_TRY(p, hipMemcpy(points, p->d_jmap + (size_t)frame * cap, n * sizeof(OrbPoint), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_localize_consecutive(OrbProgram* p, uint32_t n_frames, const OrbLocalizeParams* params, void* stream) {
+    if (!p || !params) return p ? fail(p, ORB_EINVAL, "localize_consecutive: params is NULL") : ORB_EINVAL;
+    OrbLocalizeParams g = *params;
+    for (uint32_t w : g.reserved)
+        if (w) return fail(p, ORB_EINVAL, "localize_consecutive: reserved words must be 0");
+    if (!(std::isfinite(g.fx) && g.fx > 0.0f) || !(std::isfinite(g.fy) && g.fy > 0.0f) || !std::isfinite(g.cx) || !std::isfinite(g.cy))
+        return fail(p, ORB_EINVAL, "localize_consecutive: fx and fy must be finite and > 0, cx and cy finite");
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f) || !(std::isfinite(g.ratio) && g.ratio >= 0.0f))
+        return fail(p, ORB_EINVAL, "localize_consecutive: max_reproj_px and ratio must be finite and >= 0");
+    if (g.hypotheses > kVerifyMaxHyp || g.max_distance > 256u)
+        return fail(p, ORB_EINVAL, "localize_consecutive: hypotheses must be 0..%u and max_distance 0..256", kVerifyMaxHyp);
+    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_POSE];
+    if (!stage_fresh(p, m) || !stage_fresh(p, v))
+        return fail(p, ORB_ESTATE, "localize_consecutive: no orb_match_consecutive and orb_pose_consecutive of the current batch and output set");
+    const uint32_t most = std::min(m.extent, v.extent + 1u);  // pair f reads the matches of frame f and the pose of pair f - 1
+    if (n_frames < 3u || n_frames > most)
+        return fail(p, ORB_EINVAL, "localize_consecutive: need 3..%u frames (the last pose call's pairs + 1)", most);
+    if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
+    if (!g.hypotheses) g.hypotheses = 512u;
+    if (!g.max_distance) g.max_distance = 64u;
+    if (g.ratio == 0.0f) g.ratio = 0.8f;
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features;
+    if (int rc = alloc_all_or_none(p, ST_LOCALIZE, "localize_consecutive")) return rc;
+    hipStream_t s;
+    if (int rc = stage_begin(p, ST_LOCALIZE, stream, 1u << ST_MATCH | 1u << ST_POSE, &s)) return rc;
+    const uint32_t pairs = n_frames - 1u;
+    LocArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.matches = p->d_matches;
+    a.cap = (uint32_t)cap;
+    a.poses = p->d_pose;
+    a.points = p->d_ppoints;
+    a.hyps = g.hypotheses;
+    a.max_distance = g.max_distance;
+    a.ratio = g.ratio;
+    a.fx = g.fx;
+    a.fy = g.fy;
+    a.cx = g.cx;
+    a.cy = g.cy;
+    a.r2 = g.max_reproj_px * g.max_reproj_px;
+    a.seed_mix = lowbias32(g.seed ^ kLocSeedSalt);
+    a.reca = p->d_lreca;
+    a.recb = p->d_lrecb;
+    a.cand_of = p->d_lcand;
+    a.n_cand = p->d_ln;
+    a.keys = p->d_lkeys;
+    a.fix = p->d_lfix;
+    a.mask = p->d_lmask;
+    static_assert(sizeof(OrbFrameFix) == kLocFixWords * sizeof(uint32_t) && sizeof(OrbLocalizeParams) == 64, "localize layouts");
+    hipLaunchKernelGGL(k_loc_gather, dim3(pairs), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_loc_score, dim3(pairs, (g.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_loc_refine, dim3(pairs), dim3(256), 0, s, a);
+    return stage_end(p, ST_LOCALIZE, s, pairs);  // p->last_stream stays, as after a guided call
+}
+
+int orb_localize_read(OrbProgram* p, uint32_t pair, OrbFrameFix* fix, uint8_t* inliers, size_t n) {
+    if (!p) return ORB_EINVAL;
+    const Stage& last = p->stage[ST_LOCALIZE];
+    if (!last.extent) return fail(p, ORB_ESTATE, "localize_read before localize_consecutive");
+    if (pair >= last.extent || (!inliers && n)) return fail(p, ORB_EINVAL, "localize_read: pair %u of %u, or inliers is NULL", pair, last.extent);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    if (fix) HIP_TRY(p, hipMemcpy(fix, p->d_lfix + (size_t)pair * kLocFixWords, sizeof(OrbFrameFix), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(inliers, p->d_lmask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

@@ -258,42 +258,46 @@ __device__ __forceinline__ void verify_score_tail(const VerifyArgs& a, const flo
     }
 }
 
-// GV-6's solver on one lane: the 44 sums (column 0 of `part`) spread into the symmetric 8 x 9 system `aug`, Gaussian elimination
-// with partial pivoting (first maximal |pivot|), back substitution into sol[0..7].  0: a zero pivot or a non-finite entry.
-__device__ __forceinline__ uint32_t verify_solve(const float (*part)[256], float (*aug)[9], float* sol) {
-    for (int i = 0, e = 0; i < 8; i++)
-        for (int j = i; j < 8; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
-    for (int i = 0; i < 8; i++) aug[i][8] = part[36 + i][0];
+// GV-6's solver on one lane at size N x (N + 1): the N (N + 1) / 2 + N sums (column 0 of `part`) spread into the symmetric system
+// `aug`, Gaussian elimination with partial pivoting (first maximal |pivot|), back substitution into sol[0..N-1].  0: a zero pivot or
+// a non-finite entry.  The verifiers solve at N = 8 (verify_solve), the localisation's refit at N = 6.
+template <int N>
+__device__ __forceinline__ uint32_t verify_solve_n(const float (*part)[256], float (*aug)[N + 1], float* sol) {
+    for (int i = 0, e = 0; i < N; i++)
+        for (int j = i; j < N; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
+    for (int i = 0; i < N; i++) aug[i][N] = part[N * (N + 1) / 2 + i][0];
     uint32_t ok = 1u;
-    for (int c = 0; c < 8 && ok; c++) {
+    for (int c = 0; c < N && ok; c++) {
         int piv = c;
         float pmax = fabsf(aug[c][c]);
-        for (int r = c + 1; r < 8; r++)
+        for (int r = c + 1; r < N; r++)
             if (fabsf(aug[r][c]) > pmax) pmax = fabsf(aug[r][c]), piv = r;
         if (pmax == 0.0f) {
             ok = 0u;
             break;
         }
         if (piv != c)
-            for (int q = 0; q < 9; q++) {
+            for (int q = 0; q < N + 1; q++) {
                 const float tmp = aug[c][q];
                 aug[c][q] = aug[piv][q];
                 aug[piv][q] = tmp;
             }
-        for (int r = c + 1; r < 8; r++) {
+        for (int r = c + 1; r < N; r++) {
             const float f = aug[r][c] / aug[c][c];
-            for (int q = c + 1; q < 9; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
+            for (int q = c + 1; q < N + 1; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
         }
     }
     if (ok)
-        for (int r = 7; r >= 0; r--) {
-            float s = aug[r][8];
-            for (int q = r + 1; q < 8; q++) s = s - aug[r][q] * sol[q];
+        for (int r = N - 1; r >= 0; r--) {
+            float s = aug[r][N];
+            for (int q = r + 1; q < N; q++) s = s - aug[r][q] * sol[q];
             sol[r] = s / aug[r][r];
             if (!isfinite(sol[r])) ok = 0u;
         }
     return ok;
 }
+
+__device__ __forceinline__ uint32_t verify_solve(const float (*part)[256], float (*aug)[9], float* sol) { return verify_solve_n<8>(part, aug, sol); }
 
 // The refine kernels, one workgroup of 256 per pair: the best key and what it encodes, the winner rebuilt (Model::winner), the
 // normal equations of its inliers summed in GV-6's order (thread t owns partial sum t, then the tree), solved on one lane, the

@@ -62,6 +62,10 @@ FRAME_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "
                              ("shared", "<u4"), ("consistent", "<u4"), ("status", "<u4"), ("reserved", "<u4", (2,))])
 ORB_TRAJ_CHAINED, ORB_TRAJ_START, ORB_TRAJ_RESTART_FEW, ORB_TRAJ_RESTART_SPREAD, ORB_TRAJ_LOST, ORB_TRAJ_ORIGIN = 0, 1, 2, 3, 4, 5
 ORB_TRAJ_NEED_PARALLAX = 1
+# absolute pose from the previous pair's map points (orb_localize_consecutive): OrbFrameFix (80 B), its status
+FIX_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("step", "<f4"), ("candidates", "<u4"), ("inliers", "<u4"),
+                      ("hypothesis", "<u4"), ("status", "<u4"), ("reserved", "<u4", (3,))])
+ORB_LOCALIZE_OK, ORB_LOCALIZE_NOMAP, ORB_LOCALIZE_FEW, ORB_LOCALIZE_DEGENERATE, ORB_LOCALIZE_MINIMAL = 0, 1, 2, 3, 4
 # feature tracks and keyframes (orb_track_consecutive): the link source, OrbTrack (16 B), OrbTrackFrame (32 B)
 ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
 TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
@@ -89,6 +93,7 @@ EXPORTS = [
     "orb_track_consecutive", "orb_track_read", "orb_track_frames", "orb_verify_epipolar", "orb_verify_epipolar_read",
     "orb_match_epipolar", "orb_match_epipolar_read", "orb_pose_consecutive", "orb_pose_read",
     "orb_trajectory_consecutive", "orb_trajectory_read", "orb_debug_pose_buffers",
+    "orb_localize_consecutive", "orb_localize_read",
 ]
 
 
@@ -146,6 +151,16 @@ class _TrajectoryParams(ctypes.Structure):
 
 
 OrbTrajectoryParams = _TrajectoryParams
+
+
+class _LocalizeParams(ctypes.Structure):
+    """OrbLocalizeParams (64 bytes; fx and fy must be > 0, the other zero fields = the defaults)"""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("max_reproj_px", ctypes.c_float), ("hypotheses", ctypes.c_uint32), ("max_distance", ctypes.c_uint32),
+                ("ratio", ctypes.c_float), ("seed", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+OrbLocalizeParams = _LocalizeParams
 
 
 class _TrackParams(ctypes.Structure):
@@ -238,6 +253,8 @@ def load_library(path=None):
     L.orb_pose_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_trajectory_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrajectoryParams), vp]
     L.orb_trajectory_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_localize_consecutive.argtypes = [vp, u32, ctypes.POINTER(_LocalizeParams), vp]
+    L.orb_localize_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -694,6 +711,27 @@ class OrbProgram:
         pts = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=POINT_DTYPE)
         self._check(self._lib.orb_trajectory_read(self._handle(), frame, _ptr(rec), _ptr(pts) if len(pts) else None, len(pts)))
         return rec, pts
+
+    def localize_consecutive(self, n_frames, fx, fy, cx, cy, max_reproj_px=0.0, hypotheses=0, max_distance=0, ratio=0.0, seed=0,
+                             stream=None, reserved=(0, 0, 0, 0, 0, 0, 0)):
+        """Absolute pose of camera f + 1 relative to camera f from the map points of the pair before (not in the reference; DESIGN.md
+        section 21, LO-1..LO-7): per pair (f, f+1), 1 <= f < n_frames - 1, the GOOD points of pair f - 1 in the last pose_consecutive,
+        carried by the matcher's records to a keypoint of frame f + 1 (the second hop filtered by max_distance (0: 64) and ratio
+        (0: 0.8)), give 3D-2D correspondences; a RANSAC over `hypotheses` (0: 512) six-point DLT samples within max_reproj_px
+        (0: 2.0) and four Gauss-Newton steps on the winner's inliers give R and a metric t in units of pair f - 1's baseline.  The
+        intrinsics are those given to pose_consecutive.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        prm = _LocalizeParams(float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
+                              float(np.float32(max_reproj_px)), hypotheses, max_distance, float(np.float32(ratio)), seed & 0xFFFFFFFF,
+                              (ctypes.c_uint32 * 7)(*reserved))
+        self._check(self._lib.orb_localize_consecutive(self._handle(), n_frames, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def localize_read(self, pair, n=None):
+        """(record of FIX_DTYPE, uint8[min(n, max_features)]: the inlier bytes of frame pair - 1's slots; n None: max_features) of the
+        last localize_consecutive -- synchronises."""
+        rec = np.zeros((), dtype=FIX_DTYPE)
+        mask = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=np.uint8)
+        self._check(self._lib.orb_localize_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
+        return rec, mask
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
