@@ -663,6 +663,52 @@ int orb_localize_consecutive(OrbProgram *p, uint32_t n_frames, const OrbLocalize
  * host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside its pairs or inliers NULL with n > 0. */
 int orb_localize_read(OrbProgram *p, uint32_t pair, OrbFrameFix *fix, uint8_t *inliers, size_t n);
 
+/* ---- one multi-view map point per landmark (NOT in the reference; definition LM-1..LM-6 in DESIGN.md section 22) ----
+ * The map of orb_trajectory_consecutive holds a landmark once per pair that triangulated it, each copy with the error of one short
+ * baseline.  Here the matcher's records chain the GOOD points of consecutive pairs of one segment: slot i of pair p continues into
+ * slot j = matches[p][i].index of pair p + 1 when that point is GOOD too and frame p + 2 is CHAINED.  A GOOD slot that no GOOD slot
+ * of the pair before continues into is a start, and each start is one landmark: the point nearest to the rays of all its views
+ * (midpoint method) under the frame poses of the last orb_trajectory_consecutive, in the frame and unit of its segment's origin,
+ * then checked by reprojection into every view.  Binary32 arithmetic in a fixed order, no fused operations, no square root: a CPU
+ * restatement gives the same bits.  Nothing is fed back into another stage. */
+typedef struct {            /* zero-initialised is NOT valid: fx, fy must be > 0 */
+    float fx, fy, cx, cy;   /* the intrinsics given to orb_pose_consecutive */
+    float max_reproj_px;    /* reprojection error a view may have (0: 2.0); finite, >= 0 */
+    uint32_t min_views;     /* views a GOOD landmark needs (0: 2) */
+    uint32_t reserved[2];   /* must be 0 (ORB_EINVAL otherwise) */
+} OrbLandmarkParams;        /* 32 bytes */
+
+typedef struct {
+    float x, y, z;          /* in the frame and unit of frame `origin`; 0 when the solve failed */
+    uint32_t flags;         /* ORB_POINT_GOOD: solved, views >= min_views and every view an inlier; ORB_POINT_PARALLAX: GOOD and a point of the chain has it */
+    uint16_t views;         /* 0: this slot starts no landmark (then the whole record is 0) */
+    uint16_t inliers;       /* views within max_reproj_px of the point's reprojection */
+    uint32_t origin;        /* the segment's origin frame (OrbFramePose.origin) */
+    uint32_t tail_index;    /* keypoint slot of the last view, in frame pair + views - 1 */
+    uint32_t reserved[1];   /* 0 */
+} OrbLandmark;              /* 32 bytes */
+
+typedef struct {
+    uint32_t landmarks;     /* starts of this pair */
+    uint32_t good;          /* of them GOOD */
+    uint32_t longest;       /* the largest `views` */
+    uint32_t origin;        /* the pair's segment, 0xffffffff when frame pair + 1 is LOST (no landmarks) */
+} OrbLandmarkRow;           /* 16 bytes */
+
+/* Landmarks of the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: the record of a landmark is at the pair and slot of its
+ * first view.  ORB_EINVAL for a NULL program or params, fx or fy not finite or not > 0, cx or cy not finite, max_reproj_px not
+ * finite or < 0, a reserved word that is not 0, or n_frames not in 2 .. the last orb_trajectory_consecutive's frames; ORB_ESTATE
+ * unless the last orb_match_consecutive, orb_pose_consecutive and orb_trajectory_consecutive are all of the current batch and
+ * output set.  Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not change it), ordered behind those
+ * three stages' last calls and the last call of its own when they ran on another stream; the three wait for such a call on another
+ * stream before they overwrite what it reads.  Result buffers of its own (allocated by the first call): no other stage's results
+ * are ever written. */
+int orb_landmarks_consecutive(OrbProgram *p, uint32_t n_frames, const OrbLandmarkParams *params, void *stream);
+/* Copy the row of pair `pair` of the last orb_landmarks_consecutive call (row may be NULL) and its first n landmark records (indexed
+ * as orb_match_read) to the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside its pairs or landmarks
+ * NULL with n > 0. */
+int orb_landmarks_read(OrbProgram *p, uint32_t pair, OrbLandmarkRow *row, OrbLandmark *landmarks, size_t n);
+
 /* ---- feature tracks and keyframes (NOT in the reference; definition TK-1..TK-5 in DESIGN.md section 15) ----
  * Over the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: query i of frame f links to target j of frame f+1 by the
  * source's record (VERIFIED: the matcher's record where the last verification's inlier byte is 1; GUIDED / MATCHED: the last

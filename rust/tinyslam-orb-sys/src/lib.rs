@@ -334,6 +334,53 @@ pub mod orb {
     }
 
     // ------------------------------------------------------------------------------------------------------------
+    // Landmarks: one multi-view map point per chain of GOOD points across the consecutive pairs of a segment
+    // (include/tinyorb.h; not in the reference).  Declarations only: the calls follow
+    // orb_trajectory_consecutive on the last batch.
+    // ------------------------------------------------------------------------------------------------------------
+    /// `OrbLandmarkParams`: NOT valid zeroed -- fx and fy must be > 0 (the intrinsics given to orb_pose_consecutive); the other zero
+    /// fields mean the defaults.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbLandmarkParams {
+        pub fx: f32,
+        pub fy: f32,
+        pub cx: f32,
+        pub cy: f32,
+        pub max_reproj_px: f32, // 0: 2.0
+        pub min_views: u32,     // 0: 2
+        pub reserved: [u32; 2], // must be 0
+    }
+    /// `OrbLandmark`: at the pair and slot of its first view; `views == 0`: the slot starts no landmark.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbLandmark {
+        pub x: f32,
+        pub y: f32,
+        pub z: f32,
+        pub flags: u32, // ORB_POINT_GOOD, ORB_POINT_PARALLAX
+        pub views: u16,
+        pub inliers: u16,
+        pub origin: u32,
+        pub tail_index: u32,
+        pub reserved: [u32; 1],
+    }
+    /// `OrbLandmarkRow`: the counts of a pair; `origin` 0xffffffff: frame pair + 1 is LOST.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbLandmarkRow {
+        pub landmarks: u32,
+        pub good: u32,
+        pub longest: u32,
+        pub origin: u32,
+    }
+
+    extern "C" {
+        pub fn orb_landmarks_consecutive(p: *mut c_void, n_frames: u32, params: *const OrbLandmarkParams, stream: *mut c_void) -> c_int;
+        pub fn orb_landmarks_read(p: *mut c_void, pair: u32, row: *mut OrbLandmarkRow, landmarks: *mut OrbLandmark, n: usize) -> c_int;
+    }
+
+    // ------------------------------------------------------------------------------------------------------------
     // Batched, multi-GPU entry (include/tinyorb.h "one node, several GPUs"; not in the reference, which drives one
     // wgpu device).  The same calls, in the same order, are exercised from C by examples/node_batch.c, which the
     // repository's GPU tests compile with gcc and run -- that C program is the verified twin of this block.

@@ -33,6 +33,7 @@
 #include "orb_kernels_pose.h"
 #include "orb_kernels_traj.h"
 #include "orb_kernels_localize.h"
+#include "orb_kernels_landmark.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -67,17 +68,18 @@ struct ProfSpan {
 // The stages that run after extraction.  Each owns ONE set of buffers per program, shared by both output sets and by whatever stream
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, which the entry point names; and the stages that read what it overwrites, kReadersOf[stage].
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_COUNT };
 const uint32_t kReadersOf[ST_COUNT] = {
-    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE | 1u << ST_TRAJ | 1u << ST_LOCALIZE,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it; trajectory pairs the points of two pairs by it; localize carries a point over two pairs by it)
+    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE | 1u << ST_TRAJ | 1u << ST_LOCALIZE | 1u << ST_LANDMARK,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it; trajectory pairs the points of two pairs by it; localize carries a point over two pairs by it; landmarks chains the pairs' points by it)
     1u << ST_GUIDE | 1u << ST_TRACK,                  // verify: verify.model (guided, ORB_GUIDE_VERIFIED), verify.mask (track, ORB_TRACK_VERIFIED)
     1u << ST_BAND | 1u << ST_POSE,                    // epi: epi.model (band, ORB_BAND_VERIFIED; pose), epi.mask (pose)
     1u << ST_TRACK,                                   // guide: d_gmatch (track, ORB_TRACK_GUIDED)
     0u,                                               // track: read back by the host
     0u,                                               // band: d_bmatch is read back by the host
-    1u << ST_TRAJ | 1u << ST_LOCALIZE,                // pose: d_pose, d_ppoints (trajectory, localize)
-    0u,                                               // trajectory: read back by the host
+    1u << ST_TRAJ | 1u << ST_LOCALIZE | 1u << ST_LANDMARK,  // pose: d_pose, d_ppoints (trajectory, localize; landmarks reads d_ppoints)
+    1u << ST_LANDMARK,                                // trajectory: d_jframe (landmarks)
     0u,                                               // localize: read back by the host
+    0u,                                               // landmarks: read back by the host
 };
 
 // The last call of a stage
@@ -189,6 +191,10 @@ struct OrbProgram {
     uint32_t* d_ln = nullptr;             // [max_batch] candidates per pair
     unsigned long long* d_lkeys = nullptr; // [max_batch][kVerifyMaxHyp]
     uint8_t* d_lmask = nullptr;           // [max_batch][max_features] inlier bytes
+    // orb_landmarks_consecutive (orb_kernels_landmark.h)
+    float4* d_mland = nullptr;            // [max_batch][max_features][2] OrbLandmark
+    uint32_t* d_mrow = nullptr;           // [max_batch][4] OrbLandmarkRow
+    uint8_t* d_mpred = nullptr;           // [max_batch][max_features] a live slot of the pair before continues into this slot
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -378,6 +384,11 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         add(&p->d_ln, B * sizeof(uint32_t));
         add(&p->d_lkeys, B * kVerifyMaxHyp * sizeof(unsigned long long));
         add(&p->d_lmask, B * cap);
+        break;
+    case ST_LANDMARK:
+        add(&p->d_mland, B * cap * sizeof(OrbLandmark));
+        add(&p->d_mrow, B * sizeof(OrbLandmarkRow));
+        add(&p->d_mpred, B * cap);
         break;
     }
     return n;
@@ -2752,6 +2763,65 @@ int orb_localize_read(OrbProgram* p, uint32_t pair, OrbFrameFix* fix, uint8_t* i
     if (n > cap) n = cap;
     if (fix) HIP_TRY(p, hipMemcpy(fix, p->d_lfix + (size_t)pair * kLocFixWords, sizeof(OrbFrameFix), hipMemcpyDeviceToHost));
     if (n) HIP_TRY(p, hipMemcpy(inliers, p->d_lmask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_landmarks_consecutive(OrbProgram* p, uint32_t n_frames, const OrbLandmarkParams* params, void* stream) {
+    if (!p || !params) return p ? fail(p, ORB_EINVAL, "landmarks_consecutive: params is NULL") : ORB_EINVAL;
+    OrbLandmarkParams g = *params;
+    if (g.reserved[0] | g.reserved[1]) return fail(p, ORB_EINVAL, "landmarks_consecutive: reserved words must be 0");
+    if (!(std::isfinite(g.fx) && g.fx > 0.0f) || !(std::isfinite(g.fy) && g.fy > 0.0f) || !std::isfinite(g.cx) || !std::isfinite(g.cy))
+        return fail(p, ORB_EINVAL, "landmarks_consecutive: fx and fy must be finite and > 0, cx and cy finite");
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f)) return fail(p, ORB_EINVAL, "landmarks_consecutive: max_reproj_px must be finite and >= 0");
+    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_POSE], &t = p->stage[ST_TRAJ];
+    if (!stage_fresh(p, m) || !stage_fresh(p, v) || !stage_fresh(p, t))
+        return fail(p, ORB_ESTATE, "landmarks_consecutive: no orb_match_consecutive, orb_pose_consecutive and orb_trajectory_consecutive of the current batch and output set");
+    const uint32_t most = std::min(std::min(m.extent, v.extent + 1u), t.extent);  // pair p reads the matches of frame p, the points of pair p, the records of frames p and p + 1
+    if (n_frames < 2u || n_frames > most) return fail(p, ORB_EINVAL, "landmarks_consecutive: need 2..%u frames (the last trajectory call's frames)", most);
+    if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
+    if (!g.min_views) g.min_views = 2u;
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features;
+    if (int rc = alloc_all_or_none(p, ST_LANDMARK, "landmarks_consecutive")) return rc;
+    hipStream_t s;
+    if (int rc = stage_begin(p, ST_LANDMARK, stream, 1u << ST_MATCH | 1u << ST_POSE | 1u << ST_TRAJ, &s)) return rc;
+    const uint32_t pairs = n_frames - 1u;
+    LmArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.matches = p->d_matches;
+    a.cap = (uint32_t)cap;
+    a.n_frames = n_frames;
+    a.points = p->d_ppoints;
+    a.frames = p->d_jframe;
+    a.fx = g.fx;
+    a.fy = g.fy;
+    a.cx = g.cx;
+    a.cy = g.cy;
+    a.r2 = g.max_reproj_px * g.max_reproj_px;
+    a.min_views = g.min_views;
+    a.pred = p->d_mpred;
+    a.rows = p->d_mrow;
+    a.out = p->d_mland;
+    static_assert(sizeof(OrbLandmark) == 32 && sizeof(OrbLandmarkRow) == kLmRowWords * sizeof(uint32_t) && sizeof(OrbLandmarkParams) == 32, "landmark layouts");
+    const dim3 grid(pairs, (unsigned)((cap + kLmThreads - 1u) / kLmThreads));
+    HIP_TRY(p, hipMemsetAsync(p->d_mpred, 0, (size_t)pairs * cap, s));
+    hipLaunchKernelGGL(k_lm_mark, grid, dim3(kLmThreads), 0, s, a);
+    hipLaunchKernelGGL(k_lm_fuse, grid, dim3(kLmThreads), 0, s, a);
+    return stage_end(p, ST_LANDMARK, s, pairs);  // p->last_stream stays, as after a guided call
+}
+
+int orb_landmarks_read(OrbProgram* p, uint32_t pair, OrbLandmarkRow* row, OrbLandmark* landmarks, size_t n) {
+    if (!p) return ORB_EINVAL;
+    const Stage& last = p->stage[ST_LANDMARK];
+    if (!last.extent) return fail(p, ORB_ESTATE, "landmarks_read before landmarks_consecutive");
+    if (pair >= last.extent || (!landmarks && n)) return fail(p, ORB_EINVAL, "landmarks_read: pair %u of %u, or landmarks is NULL", pair, last.extent);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    if (row) HIP_TRY(p, hipMemcpy(row, p->d_mrow + (size_t)pair * kLmRowWords, sizeof(OrbLandmarkRow), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(landmarks, p->d_mland + (size_t)pair * cap * 2u, n * sizeof(OrbLandmark), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

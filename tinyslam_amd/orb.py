@@ -66,6 +66,11 @@ ORB_TRAJ_NEED_PARALLAX = 1
 FIX_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("step", "<f4"), ("candidates", "<u4"), ("inliers", "<u4"),
                       ("hypothesis", "<u4"), ("status", "<u4"), ("reserved", "<u4", (3,))])
 ORB_LOCALIZE_OK, ORB_LOCALIZE_NOMAP, ORB_LOCALIZE_FEW, ORB_LOCALIZE_DEGENERATE, ORB_LOCALIZE_MINIMAL = 0, 1, 2, 3, 4
+# one multi-view map point per landmark (orb_landmarks_consecutive): OrbLandmark (32 B), OrbLandmarkRow (16 B)
+LANDMARK_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("flags", "<u4"), ("views", "<u2"), ("inliers", "<u2"),
+                           ("origin", "<u4"), ("tail_index", "<u4"), ("reserved", "<u4", (1,))])
+LANDMARK_ROW_DTYPE = np.dtype([("landmarks", "<u4"), ("good", "<u4"), ("longest", "<u4"), ("origin", "<u4")])
+ORB_LANDMARK_NO_ORIGIN = 0xFFFFFFFF
 # feature tracks and keyframes (orb_track_consecutive): the link source, OrbTrack (16 B), OrbTrackFrame (32 B)
 ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
 TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
@@ -94,6 +99,7 @@ EXPORTS = [
     "orb_match_epipolar", "orb_match_epipolar_read", "orb_pose_consecutive", "orb_pose_read",
     "orb_trajectory_consecutive", "orb_trajectory_read", "orb_debug_pose_buffers",
     "orb_localize_consecutive", "orb_localize_read",
+    "orb_landmarks_consecutive", "orb_landmarks_read",
 ]
 
 
@@ -161,6 +167,15 @@ class _LocalizeParams(ctypes.Structure):
 
 
 OrbLocalizeParams = _LocalizeParams
+
+
+class _LandmarkParams(ctypes.Structure):
+    """OrbLandmarkParams (32 bytes; fx and fy must be > 0, the other zero fields = the defaults)"""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("max_reproj_px", ctypes.c_float), ("min_views", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+OrbLandmarkParams = _LandmarkParams
 
 
 class _TrackParams(ctypes.Structure):
@@ -255,6 +270,8 @@ def load_library(path=None):
     L.orb_trajectory_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_localize_consecutive.argtypes = [vp, u32, ctypes.POINTER(_LocalizeParams), vp]
     L.orb_localize_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_landmarks_consecutive.argtypes = [vp, u32, ctypes.POINTER(_LandmarkParams), vp]
+    L.orb_landmarks_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -732,6 +749,24 @@ class OrbProgram:
         mask = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=np.uint8)
         self._check(self._lib.orb_localize_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
         return rec, mask
+
+    def landmarks_consecutive(self, n_frames, fx, fy, cx, cy, max_reproj_px=0.0, min_views=0, stream=None, reserved=(0, 0)):
+        """One multi-view map point per landmark (not in the reference): the GOOD points of the last
+        pose_consecutive chained by the matcher's records across the consecutive pairs of one segment of the last
+        trajectory_consecutive; every chain's start is a landmark, the point nearest to the rays of all its views under the frame
+        poses, GOOD when it has min_views (0: 2) views and all reproject within max_reproj_px (0: 2.0).  The intrinsics are those
+        given to pose_consecutive.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        prm = _LandmarkParams(float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
+                              float(np.float32(max_reproj_px)), min_views, (ctypes.c_uint32 * 2)(*reserved))
+        self._check(self._lib.orb_landmarks_consecutive(self._handle(), n_frames, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def landmarks_read(self, pair, n=None):
+        """(row of LANDMARK_ROW_DTYPE, LANDMARK_DTYPE[min(n, max_features)]: the records at pair `pair`'s slots; n None: max_features)
+        of the last landmarks_consecutive -- synchronises."""
+        row = np.zeros((), dtype=LANDMARK_ROW_DTYPE)
+        lm = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=LANDMARK_DTYPE)
+        self._check(self._lib.orb_landmarks_read(self._handle(), pair, _ptr(row), _ptr(lm) if len(lm) else None, len(lm)))
+        return row, lm
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
