@@ -621,7 +621,8 @@ int orb_trajectory_read(OrbProgram *p, uint32_t frame, OrbFramePose *pose, OrbPo
  * scored by the reprojection error in frame f + 1, then four Gauss-Newton steps on the winner's inliers, kept when they hold at
  * least 15/16 of the winner's count.  So a pair with little or no translation, whose two-view pose is LOW_PARALLAX or AMBIGUOUS,
  * still gets a pose while the map of the pair before is in view.  Binary32 arithmetic in a fixed order, no fused operations: a
- * CPU restatement gives the same bits.  Nothing is fed back into orb_trajectory_consecutive. */
+ * CPU restatement gives the same bits.  Nothing is fed back into orb_trajectory_consecutive; orb_bridge_consecutive below runs the
+ * same RANSAC on the landmarks of orb_landmarks_consecutive to carry the trajectory across LOST frames. */
 typedef struct {            /* zero-initialised is NOT valid: fx, fy must be > 0 */
     float fx, fy, cx, cy;   /* the intrinsics given to orb_pose_consecutive */
     float max_reproj_px;    /* frame f+1 reprojection error an inlier may have (0: 2.0); finite, >= 0 */
@@ -670,7 +671,7 @@ int orb_localize_read(OrbProgram *p, uint32_t pair, OrbFrameFix *fix, uint8_t *i
  * of the pair before continues into is a start, and each start is one landmark: the point nearest to the rays of all its views
  * (midpoint method) under the frame poses of the last orb_trajectory_consecutive, in the frame and unit of its segment's origin,
  * then checked by reprojection into every view.  Binary32 arithmetic in a fixed order, no fused operations, no square root: a CPU
- * restatement gives the same bits.  Nothing is fed back into another stage. */
+ * restatement gives the same bits.  Nothing is fed back into another stage; orb_bridge_consecutive below reads the landmarks. */
 typedef struct {            /* zero-initialised is NOT valid: fx, fy must be > 0 */
     float fx, fy, cx, cy;   /* the intrinsics given to orb_pose_consecutive */
     float max_reproj_px;    /* reprojection error a view may have (0: 2.0); finite, >= 0 */
@@ -708,6 +709,70 @@ int orb_landmarks_consecutive(OrbProgram *p, uint32_t n_frames, const OrbLandmar
  * as orb_match_read) to the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside its pairs or landmarks
  * NULL with n > 0. */
 int orb_landmarks_read(OrbProgram *p, uint32_t pair, OrbLandmarkRow *row, OrbLandmark *landmarks, size_t n);
+
+/* ---- a trajectory carried across LOST frames (NOT in the reference; definition BR-1..BR-7 in DESIGN.md section 23) ----
+ * One pair with little translation ends a segment of orb_trajectory_consecutive: its frame is LOST and the frames behind it start
+ * a new segment with a new origin and a new unit, although the landmarks built just before are still in view.  For every LOST
+ * frame g, with T the last frame before it that is not LOST (its anchor), the GOOD landmarks of the last
+ * orb_landmarks_consecutive whose last view is in frame T are followed through the matcher's records from their tail_index hop
+ * by hop into frame g (every hop under max_distance and ratio).  Each, moved into camera T's frame, and the level-0 position of
+ * its keypoint in frame g are a 3D-2D correspondence; orb_localize_consecutive's RANSAC and refit give camera g relative to
+ * camera T in the unit of T's segment.  When frame g + 1 starts a segment, the new segment's points at those keypoints give the
+ * ratio of the two units (lower median of depth ratios, accepted as a joint of the trajectory is).  The call writes, for every
+ * frame of the batch, a pose in the frame and unit of the earliest origin the frame can be traced back to (its root).  A batch
+ * without a LOST frame gives the trajectory's poses bit for bit.  Binary32 arithmetic in a fixed order, no fused operations: a
+ * CPU restatement gives the same bits.  RESTART_FEW and RESTART_SPREAD frames are not joined. */
+typedef struct {                  /* zero-initialised is NOT valid: fx, fy must be > 0 */
+    float fx, fy, cx, cy;         /* the intrinsics given to orb_pose_consecutive */
+    float max_reproj_px;          /* frame g reprojection error an inlier may have (0: 2.0); finite, >= 0 */
+    uint32_t hypotheses;          /* minimal samples per LOST frame, 1..4096 (0: 512) */
+    uint32_t max_distance;        /* a hop is followed iff distance <= this (0: 64); 0..256 */
+    float ratio;                  /* ... and distance < ratio * second (0: 0.8); finite, >= 0 */
+    uint32_t seed;                /* of the sampling; the same seed gives the same result */
+    uint32_t max_hops;            /* a LOST frame further than this behind its anchor is not fixed (0: 4); 0..16 */
+    uint32_t window;              /* landmark rows T - window .. T - 1 are searched (0: 32); 0..4095 */
+    uint32_t min_shared;          /* depth ratios a join needs (0: 8) */
+    float scale_tolerance;        /* a ratio is consistent within this, relative to the median (0: 0.1); finite, >= 0 */
+    uint32_t consistent_permille; /* share of the ratios that must be consistent (0: 500); 0..1000 */
+    uint32_t reserved[2];         /* must be 0 (ORB_EINVAL otherwise) */
+} OrbBridgeParams;                /* 64 bytes */
+
+#define ORB_BRIDGE_COPIED 0u  /* not LOST, in a segment whose origin is its own root: the trajectory's pose and scale, gain 1 */
+#define ORB_BRIDGE_MOVED 1u   /* not LOST, in a segment joined to an earlier one: the trajectory's pose moved into the root's frame and unit */
+#define ORB_BRIDGE_FIXED 2u   /* LOST, fixed against its anchor; the frames behind it are a map of their own (gain 0) */
+#define ORB_BRIDGE_JOINED 3u  /* LOST, fixed, and the segment that starts behind it measured against the old one */
+#define ORB_BRIDGE_UNFIXED 4u /* LOST and not fixed: the trajectory's record (identity), root = the frame itself, gain 0 */
+
+typedef struct {
+    float r[9];             /* row-major R, X_f = R X_root + t */
+    float t[3];             /* in units of the root segment */
+    float scale;            /* COPIED, MOVED: the trajectory's scale in root units; FIXED, JOINED: |t| of the fix in root units; UNFIXED: 0 */
+    float gain;             /* root units per unit of the segment this frame belongs to (COPIED: 1) or starts (JOINED); else 0 */
+    uint32_t root;          /* the origin frame the pose refers to */
+    uint32_t anchor;        /* LOST frames: the last frame before that is not LOST; else 0 */
+    uint32_t candidates;    /* LOST frames: 3D-2D correspondences (at most the capacity) */
+    uint32_t inliers;       /* of them: within max_reproj_px under the fix */
+    uint32_t hypothesis;    /* the winning sample */
+    uint32_t shared;        /* depth ratios of the join, when one was evaluated */
+    uint32_t consistent;    /* of them within scale_tolerance of their median */
+    uint32_t fix;           /* ORB_LOCALIZE_*; ORB_LOCALIZE_NOMAP for frames that are not LOST */
+    uint32_t status;        /* ORB_BRIDGE_* */
+    uint32_t reserved[1];   /* 0 */
+} OrbBridgePose;            /* 96 bytes */
+
+/* Bridged poses of frames 0 .. n_frames - 1 of the last batch.  ORB_EINVAL for a NULL program or params, fx or fy not finite or
+ * not > 0, cx or cy not finite, another parameter out of range, a reserved word that is not 0, or n_frames not in 2 .. the last
+ * orb_landmarks_consecutive's frames; ORB_ESTATE unless the last orb_match_consecutive, orb_pose_consecutive,
+ * orb_trajectory_consecutive and orb_landmarks_consecutive are all of the current batch and output set.  Asynchronous on `stream`
+ * (NULL: as orb_match_guided chooses; the call does not change it), ordered behind those four stages' last calls and the last
+ * call of its own when they ran on another stream; the four wait for such a call on another stream before they overwrite what
+ * it reads.  Result buffers of its own (allocated by the first call): no other stage's results are ever written. */
+int orb_bridge_consecutive(OrbProgram *p, uint32_t n_frames, const OrbBridgeParams *params, void *stream);
+/* Copy the record of frame `frame` of the last orb_bridge_consecutive call (pose may be NULL) and up to n inlier bytes -- byte k is
+ * 1 iff keypoint k of a LOST frame (indexed as orb_match_read) ends a correspondence that is an inlier of the fix written; all 0
+ * for every other frame -- to the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a frame outside its frames or
+ * inliers NULL with n > 0. */
+int orb_bridge_read(OrbProgram *p, uint32_t frame, OrbBridgePose *pose, uint8_t *inliers, size_t n);
 
 /* ---- feature tracks and keyframes (NOT in the reference; definition TK-1..TK-5 in DESIGN.md section 15) ----
  * Over the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: query i of frame f links to target j of frame f+1 by the

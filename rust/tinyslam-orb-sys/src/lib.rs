@@ -381,6 +381,62 @@ pub mod orb {
     }
 
     // ------------------------------------------------------------------------------------------------------------
+    // Bridge: the trajectory carried across LOST frames by the landmarks that are still in view (include/tinyorb.h,
+    // DESIGN.md section 23; not in the reference).  Declarations only: the calls follow orb_landmarks_consecutive on
+    // the last batch.
+    // ------------------------------------------------------------------------------------------------------------
+    /// `OrbBridgeParams`: NOT valid zeroed -- fx and fy must be > 0 (the intrinsics given to orb_pose_consecutive); the other zero
+    /// fields mean the defaults.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbBridgeParams {
+        pub fx: f32,
+        pub fy: f32,
+        pub cx: f32,
+        pub cy: f32,
+        pub max_reproj_px: f32,      // 0: 2.0
+        pub hypotheses: u32,         // 0: 512; at most 4096
+        pub max_distance: u32,       // 0: 64; at most 256
+        pub ratio: f32,              // 0: 0.8
+        pub seed: u32,
+        pub max_hops: u32,           // 0: 4; at most 16
+        pub window: u32,             // 0: 32; at most 4095
+        pub min_shared: u32,         // 0: 8
+        pub scale_tolerance: f32,    // 0: 0.1
+        pub consistent_permille: u32, // 0: 500; at most 1000
+        pub reserved: [u32; 2],      // must be 0
+    }
+    pub const ORB_BRIDGE_COPIED: u32 = 0;
+    pub const ORB_BRIDGE_MOVED: u32 = 1;
+    pub const ORB_BRIDGE_FIXED: u32 = 2;
+    pub const ORB_BRIDGE_JOINED: u32 = 3;
+    pub const ORB_BRIDGE_UNFIXED: u32 = 4;
+    /// `OrbBridgePose`: X_f = R X_root + t in units of the root segment; `fix` is an ORB_LOCALIZE_* status, `status` an ORB_BRIDGE_* one.
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct OrbBridgePose {
+        pub r: [f32; 9],
+        pub t: [f32; 3],
+        pub scale: f32,
+        pub gain: f32,
+        pub root: u32,
+        pub anchor: u32,
+        pub candidates: u32,
+        pub inliers: u32,
+        pub hypothesis: u32,
+        pub shared: u32,
+        pub consistent: u32,
+        pub fix: u32,
+        pub status: u32,
+        pub reserved: [u32; 1],
+    }
+
+    extern "C" {
+        pub fn orb_bridge_consecutive(p: *mut c_void, n_frames: u32, params: *const OrbBridgeParams, stream: *mut c_void) -> c_int;
+        pub fn orb_bridge_read(p: *mut c_void, frame: u32, pose: *mut OrbBridgePose, inliers: *mut u8, n: usize) -> c_int;
+    }
+
+    // ------------------------------------------------------------------------------------------------------------
     // Batched, multi-GPU entry (include/tinyorb.h "one node, several GPUs"; not in the reference, which drives one
     // wgpu device).  The same calls, in the same order, are exercised from C by examples/node_batch.c, which the
     // repository's GPU tests compile with gcc and run -- that C program is the verified twin of this block.

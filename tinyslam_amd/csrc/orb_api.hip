@@ -34,6 +34,7 @@
 #include "orb_kernels_traj.h"
 #include "orb_kernels_localize.h"
 #include "orb_kernels_landmark.h"
+#include "orb_kernels_bridge.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -68,18 +69,19 @@ struct ProfSpan {
 // The stages that run after extraction.  Each owns ONE set of buffers per program, shared by both output sets and by whatever stream
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, which the entry point names; and the stages that read what it overwrites, kReadersOf[stage].
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_COUNT };
 const uint32_t kReadersOf[ST_COUNT] = {
-    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE | 1u << ST_TRAJ | 1u << ST_LOCALIZE | 1u << ST_LANDMARK,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it; trajectory pairs the points of two pairs by it; localize carries a point over two pairs by it; landmarks chains the pairs' points by it)
+    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE | 1u << ST_TRAJ | 1u << ST_LOCALIZE | 1u << ST_LANDMARK | 1u << ST_BRIDGE,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it; trajectory pairs the points of two pairs by it; localize carries a point over two pairs by it; landmarks chains the pairs' points by it; bridge carries a landmark into a LOST frame by it)
     1u << ST_GUIDE | 1u << ST_TRACK,                  // verify: verify.model (guided, ORB_GUIDE_VERIFIED), verify.mask (track, ORB_TRACK_VERIFIED)
     1u << ST_BAND | 1u << ST_POSE,                    // epi: epi.model (band, ORB_BAND_VERIFIED; pose), epi.mask (pose)
     1u << ST_TRACK,                                   // guide: d_gmatch (track, ORB_TRACK_GUIDED)
     0u,                                               // track: read back by the host
     0u,                                               // band: d_bmatch is read back by the host
-    1u << ST_TRAJ | 1u << ST_LOCALIZE | 1u << ST_LANDMARK,  // pose: d_pose, d_ppoints (trajectory, localize; landmarks reads d_ppoints)
-    1u << ST_LANDMARK,                                // trajectory: d_jframe (landmarks)
+    1u << ST_TRAJ | 1u << ST_LOCALIZE | 1u << ST_LANDMARK | 1u << ST_BRIDGE,  // pose: d_pose, d_ppoints (trajectory, localize; landmarks and bridge read d_ppoints)
+    1u << ST_LANDMARK | 1u << ST_BRIDGE,              // trajectory: d_jframe (landmarks, bridge)
     0u,                                               // localize: read back by the host
-    0u,                                               // landmarks: read back by the host
+    1u << ST_BRIDGE,                                  // landmarks: d_mland (bridge)
+    0u,                                               // bridge: read back by the host
 };
 
 // The last call of a stage
@@ -195,6 +197,15 @@ struct OrbProgram {
     float4* d_mland = nullptr;            // [max_batch][max_features][2] OrbLandmark
     uint32_t* d_mrow = nullptr;           // [max_batch][4] OrbLandmarkRow
     uint8_t* d_mpred = nullptr;           // [max_batch][max_features] a live slot of the pair before continues into this slot
+    // orb_bridge_consecutive (orb_kernels_bridge.h)
+    uint32_t* d_bout = nullptr;           // [max_batch][24] OrbBridgePose
+    uint32_t* d_bfix = nullptr;           // [max_batch][kBrFixWords] the fix and join of every frame
+    float4* d_breca = nullptr;            // [max_batch][max_features] candidates: the landmark in the anchor's frame, the keypoint slot
+    float4* d_brecb = nullptr;            // [max_batch][max_features] candidates: the keypoint of the LOST frame and its ray
+    uint32_t* d_bn = nullptr;             // [max_batch] candidates per frame
+    unsigned long long* d_bkeys = nullptr; // [max_batch][kVerifyMaxHyp]
+    uint8_t* d_bmask = nullptr;           // [max_batch][max_features] inlier bytes
+    uint32_t* d_bratio = nullptr;         // [max_batch][max_features] the bits of a join's ratios
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -389,6 +400,16 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         add(&p->d_mland, B * cap * sizeof(OrbLandmark));
         add(&p->d_mrow, B * sizeof(OrbLandmarkRow));
         add(&p->d_mpred, B * cap);
+        break;
+    case ST_BRIDGE:
+        add(&p->d_bout, B * sizeof(OrbBridgePose));
+        add(&p->d_bfix, B * kBrFixWords * sizeof(uint32_t));
+        add(&p->d_breca, B * cap * sizeof(float4));
+        add(&p->d_brecb, B * cap * sizeof(float4));
+        add(&p->d_bn, B * sizeof(uint32_t));
+        add(&p->d_bkeys, B * kVerifyMaxHyp * sizeof(unsigned long long));
+        add(&p->d_bmask, B * cap);
+        add(&p->d_bratio, B * cap * sizeof(uint32_t));
         break;
     }
     return n;
@@ -2822,6 +2843,94 @@ int orb_landmarks_read(OrbProgram* p, uint32_t pair, OrbLandmarkRow* row, OrbLan
     if (n > cap) n = cap;
     if (row) HIP_TRY(p, hipMemcpy(row, p->d_mrow + (size_t)pair * kLmRowWords, sizeof(OrbLandmarkRow), hipMemcpyDeviceToHost));
     if (n) HIP_TRY(p, hipMemcpy(landmarks, p->d_mland + (size_t)pair * cap * 2u, n * sizeof(OrbLandmark), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_bridge_consecutive(OrbProgram* p, uint32_t n_frames, const OrbBridgeParams* params, void* stream) {
+    if (!p || !params) return p ? fail(p, ORB_EINVAL, "bridge_consecutive: params is NULL") : ORB_EINVAL;
+    OrbBridgeParams g = *params;
+    if (g.reserved[0] | g.reserved[1]) return fail(p, ORB_EINVAL, "bridge_consecutive: reserved words must be 0");
+    if (!(std::isfinite(g.fx) && g.fx > 0.0f) || !(std::isfinite(g.fy) && g.fy > 0.0f) || !std::isfinite(g.cx) || !std::isfinite(g.cy))
+        return fail(p, ORB_EINVAL, "bridge_consecutive: fx and fy must be finite and > 0, cx and cy finite");
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f) || !(std::isfinite(g.ratio) && g.ratio >= 0.0f) ||
+        !(std::isfinite(g.scale_tolerance) && g.scale_tolerance >= 0.0f))
+        return fail(p, ORB_EINVAL, "bridge_consecutive: max_reproj_px, ratio and scale_tolerance must be finite and >= 0");
+    if (g.hypotheses > kVerifyMaxHyp || g.max_distance > 256u || g.max_hops > kBrMaxHops || g.window > 4095u || g.consistent_permille > 1000u)
+        return fail(p, ORB_EINVAL, "bridge_consecutive: hypotheses must be 0..%u, max_distance 0..256, max_hops 0..%u, window 0..4095, consistent_permille 0..1000",
+                    kVerifyMaxHyp, kBrMaxHops);
+    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_POSE], &t = p->stage[ST_TRAJ], &l = p->stage[ST_LANDMARK];
+    if (!stage_fresh(p, m) || !stage_fresh(p, v) || !stage_fresh(p, t) || !stage_fresh(p, l))
+        return fail(p, ORB_ESTATE, "bridge_consecutive: no orb_match_consecutive, orb_pose_consecutive, orb_trajectory_consecutive and orb_landmarks_consecutive of the current batch and output set");
+    const uint32_t most = std::min(std::min(m.extent, v.extent + 1u), std::min(t.extent, l.extent + 1u));
+    if (n_frames < 2u || n_frames > most) return fail(p, ORB_EINVAL, "bridge_consecutive: need 2..%u frames (the last landmarks call's frames)", most);
+    if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
+    if (!g.hypotheses) g.hypotheses = 512u;
+    if (!g.max_distance) g.max_distance = 64u;
+    if (g.ratio == 0.0f) g.ratio = 0.8f;
+    if (!g.max_hops) g.max_hops = 4u;
+    if (!g.window) g.window = 32u;
+    if (!g.min_shared) g.min_shared = 8u;
+    if (g.scale_tolerance == 0.0f) g.scale_tolerance = 0.1f;
+    if (!g.consistent_permille) g.consistent_permille = 500u;
+    HIP_TRY(p, hipSetDevice(p->device));
+    const size_t cap = p->cfg.max_features;
+    if (int rc = alloc_all_or_none(p, ST_BRIDGE, "bridge_consecutive")) return rc;
+    hipStream_t s;
+    if (int rc = stage_begin(p, ST_BRIDGE, stream, 1u << ST_MATCH | 1u << ST_POSE | 1u << ST_TRAJ | 1u << ST_LANDMARK, &s)) return rc;
+    BrArgs a{};
+    a.loc.counts = p->d_counts;
+    a.loc.corners = p->d_corners;
+    a.loc.matches = p->d_matches;
+    a.loc.cap = (uint32_t)cap;
+    a.loc.poses = p->d_pose;
+    a.loc.points = p->d_ppoints;
+    a.loc.hyps = g.hypotheses;
+    a.loc.max_distance = g.max_distance;
+    a.loc.ratio = g.ratio;
+    a.loc.fx = g.fx;
+    a.loc.fy = g.fy;
+    a.loc.cx = g.cx;
+    a.loc.cy = g.cy;
+    a.loc.r2 = g.max_reproj_px * g.max_reproj_px;
+    a.loc.seed_mix = lowbias32(g.seed ^ kBrSeedSalt);
+    a.loc.reca = p->d_breca;
+    a.loc.recb = p->d_brecb;
+    a.loc.cand_of = nullptr;  // k_loc_score reads none
+    a.loc.n_cand = p->d_bn;
+    a.loc.keys = p->d_bkeys;
+    a.loc.fix = p->d_bfix;
+    a.loc.mask = p->d_bmask;
+    a.frames = p->d_jframe;
+    a.lms = p->d_mland;
+    a.n_frames = n_frames;
+    a.max_hops = g.max_hops;
+    a.window = g.window;
+    a.min_shared = g.min_shared;
+    a.tol = g.scale_tolerance;
+    a.permille = g.consistent_permille;
+    a.ratios = p->d_bratio;
+    a.out = p->d_bout;
+    static_assert(sizeof(OrbBridgePose) == kBrOutWords * sizeof(uint32_t) && sizeof(OrbBridgeParams) == 64 && kBrFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose),
+                  "bridge layouts");
+    HIP_TRY(p, hipMemsetAsync(p->d_bmask, 0, (size_t)n_frames * cap, s));
+    hipLaunchKernelGGL(k_br_gather, dim3(n_frames), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_loc_score, dim3(n_frames, (g.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a.loc);
+    hipLaunchKernelGGL(k_br_refine, dim3(n_frames), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_br_chain, dim3(1), dim3(64), 0, s, a);
+    return stage_end(p, ST_BRIDGE, s, n_frames);  // p->last_stream stays, as after a guided call
+}
+
+int orb_bridge_read(OrbProgram* p, uint32_t frame, OrbBridgePose* pose, uint8_t* inliers, size_t n) {
+    if (!p) return ORB_EINVAL;
+    const Stage& last = p->stage[ST_BRIDGE];
+    if (!last.extent) return fail(p, ORB_ESTATE, "bridge_read before bridge_consecutive");
+    if (frame >= last.extent || (!inliers && n)) return fail(p, ORB_EINVAL, "bridge_read: frame %u of %u, or inliers is NULL", frame, last.extent);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    if (pose) HIP_TRY(p, hipMemcpy(pose, p->d_bout + (size_t)frame * kBrOutWords, sizeof(OrbBridgePose), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(inliers, p->d_bmask + (size_t)frame * cap, n, hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

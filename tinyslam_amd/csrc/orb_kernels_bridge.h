@@ -1,0 +1,545 @@
+// orb_kernels_bridge.h -- a trajectory carried across LOST frames (not in the reference; the definition is the build's own,
+// BR-1..BR-7 in DESIGN.md section 23).  One pair with little translation ends the trajectory's segment although the landmarks built
+// just before it (orb_landmarks_consecutive) are still in view.  Here the matcher's records carry the GOOD landmarks whose last
+// view is the frame before the gap (the anchor T) hop by hop into the LOST frame g, section 21's six-point DLT RANSAC and
+// Gauss-Newton refit give camera g relative to camera T in the unit of T's segment, and when a new segment starts behind g the
+// lower median of depth ratios measures its unit against the old one.  A serial chain then writes every frame's pose in the frame
+// and unit of the earliest origin it can be traced back to.  Every binary32 operation below is written out in the order the
+// definition gives (-ffp-contract=off, correctly rounded division and square root), so the CPU restatement (tests/bridge_ref.py)
+// reproduces every bit.
+//
+//   k_br_gather   one workgroup of 256 per frame: the anchor from the frame records (BR-1), the landmark rows of the window in
+//                 order, the hops, the candidate (BR-2), compacted by a wave ballot and a workgroup prefix (as k_loc_gather) and
+//                 clipped at the capacity; a frame that is no gap end leaves at once with a count of 0
+//   k_loc_score   of orb_kernels_localize.h, as it is, on the bridge's buffers with grid.x = frames (BR-3)
+//   k_br_refine   one workgroup per frame: k_loc_refine's steps through the loc_* functions and GV-6's solver at 6 x 7, the inlier bytes
+//                 by keypoint slot, then BR-5: the ratios' bits, the element of rank (m - 1) / 2 by k_traj_joint's radix select on
+//                 uint32 and the consistent count (integer atomics only: no result depends on an order), the per-frame fix record
+//   k_br_chain    one wave, the arithmetic on lane 0 (BR-6 is sequential by definition); all 64 lanes stage the frame and fix
+//                 records of the next 64 frames in LDS
+#pragma once
+#include "orb_kernels_localize.h"
+#include "orb_kernels_traj.h"
+
+namespace orb {
+
+constexpr uint32_t kBrSeedSalt = 0x42523031u;  // BR-3: the draw stream's seed is lowbias32(seed ^ kBrSeedSalt)
+constexpr uint32_t kBrFrameWords = 20u;        // OrbFramePose
+constexpr uint32_t kBrFixWords = 24u;          // r[9], t[3], step, candidates, inliers, hypothesis, fix, shared, g, consistent, joined, 3 x 0
+constexpr uint32_t kBrOutWords = 24u;          // OrbBridgePose
+constexpr uint32_t kBrChunk = 64u;             // frames k_br_chain stages at a time
+constexpr uint32_t kBrMaxHops = 16u;
+
+struct BrArgs {
+    LocArgs loc;             // k_loc_score's view of the stage's own buffers: rows per frame; fix: [frames][kBrFixWords]; cand_of unused
+    const uint32_t* frames;  // [frames][kBrFrameWords] of the last orb_trajectory_consecutive
+    const float4* lms;       // [pairs][cap][2] OrbLandmark of the last orb_landmarks_consecutive
+    uint32_t n_frames;
+    uint32_t max_hops;       // BR-1
+    uint32_t window;         // BR-2
+    uint32_t min_shared;     // BR-5 (TJ-4)
+    float tol;               // BR-5 (TJ-3)
+    uint32_t permille;       // BR-5 (TJ-4)
+    uint32_t* ratios;        // [frames][cap] the bits of a join's ratios by candidate (0: none)
+    uint32_t* out;           // [frames][kBrOutWords] OrbBridgePose
+};
+
+// BR-1: 0: frame g is no gap end; 1: a gap end without a usable map (NOMAP); 2: a gap end whose anchor is T
+__device__ __forceinline__ uint32_t br_anchor(const BrArgs& a, uint32_t g, uint32_t& T) {
+    T = 0u;
+    if (a.frames[(size_t)g * kBrFrameWords + 17u] != ORB_TRAJ_LOST) return 0u;
+    for (uint32_t d = 1u; d <= a.max_hops && d <= g; d++) {
+        const uint32_t st = a.frames[(size_t)(g - d) * kBrFrameWords + 17u];
+        if (st != ORB_TRAJ_LOST) {
+            T = g - d;
+            return st == ORB_TRAJ_ORIGIN ? 1u : 2u;
+        }
+    }
+    return 1u;  // g - T > max_hops
+}
+
+// BR-4: R = Ra Rb after one polar step of RP-4 (the product itself when its det is not finite or not > 0), t = Ra tb + s ta
+__device__ __forceinline__ void br_compose(const float Ra[9], const float ta[3], float s, const float Rb[9], const float tb[3], float R[9],
+                                           float t[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) R[3 * r + c] = (Ra[3 * r] * Rb[c] + Ra[3 * r + 1] * Rb[3 + c]) + Ra[3 * r + 2] * Rb[6 + c];
+        t[r] = ((Ra[3 * r] * tb[0] + Ra[3 * r + 1] * tb[1]) + Ra[3 * r + 2] * tb[2]) + s * ta[r];
+    }
+    traj_polar_step(R);
+}
+
+// grid (frames), block 256
+__global__ __launch_bounds__(256) void k_br_gather(BrArgs a) {
+    __shared__ uint32_t wave_n[4];
+    const LocArgs& L = a.loc;
+    const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t T;
+    if (br_anchor(a, g, T) != 2u) {  // uniform
+        if (tid == 0u) L.n_cand[g] = 0u;
+        return;
+    }
+    const uint32_t* const recT = a.frames + (size_t)T * kBrFrameWords;
+    const uint32_t o = recT[14];
+    float R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; k++) R[k] = __uint_as_float(recT[k]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) t[k] = __uint_as_float(recT[9 + k]);
+    const CornerData* const cg = L.corners + (size_t)g * L.cap;
+    float4* const reca = L.reca + (size_t)g * L.cap;
+    float4* const recb = L.recb + (size_t)g * L.cap;
+    const uint32_t first = T > a.window ? T - a.window : 0u;  // BR-2: p + window >= T
+    uint32_t base = 0;
+    for (uint32_t p = max(o, first); p < T; p++) {
+        const uint32_t np = min(L.counts[p], L.cap);
+        const float4* const lm = a.lms + (size_t)p * L.cap * 2u;
+        for (uint32_t i0 = 0; i0 < np; i0 += 256u) {
+            const uint32_t i = i0 + tid;
+            bool keep = false;
+            uint32_t k = 0;
+            float4 X = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (i < np) {
+                X = lm[2u * i];
+                const float4 hi = lm[2u * i + 1u];
+                const uint32_t views = __float_as_uint(hi.x) & 0xffffu;
+                if (views != 0u && (__float_as_uint(X.w) & ORB_POINT_GOOD) != 0u && p + views - 1u == T) {
+                    k = __float_as_uint(hi.z);  // tail_index
+                    keep = true;
+                    for (uint32_t s = T; s < g && keep; s++) {  // GV-1's filter on every hop; no row is read past its stored count
+                        keep = k < min(L.counts[s], L.cap);
+                        if (keep) {
+                            const MatchRecord m = L.matches[(size_t)s * L.cap + k];
+                            const uint32_t d = m.dist & 0xffffu, second = m.dist >> 16;
+                            k = m.index;
+                            keep = k != kVerifyNone && k < min(L.counts[s + 1u], L.cap) && d <= L.max_distance && (float)d < L.ratio * (float)second;
+                        }
+                    }
+                }
+            }
+            const unsigned long long bal = __ballot(keep);
+            const uint32_t before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(bal);
+            __syncthreads();
+            uint32_t off = base;
+            for (uint32_t w = 0; w < wave; w++) off += wave_n[w];
+            const uint32_t total = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+            if (keep && off + before < L.cap) {  // the first `capacity` candidates
+                float x, y, z;
+                loc_transform(R, t, X.x, X.y, X.z, x, y, z);
+                const CornerData c = cg[k];
+                const float s = (float)(1u << (c.octave & 31u));
+                const float u2 = ((float)c.x + 0.5f) * s - 0.5f, v2 = ((float)c.y + 0.5f) * s - 0.5f;
+                reca[off + before] = make_float4(x, y, z, __uint_as_float(k));
+                recb[off + before] = make_float4(u2, v2, (u2 - L.cx) / L.fx, (v2 - L.cy) / L.fy);
+            }
+            base += total;
+            __syncthreads();
+        }
+    }
+    if (tid == 0u) L.n_cand[g] = min(base, L.cap);
+}
+
+
+// GV-6's solver at 6 x 7, written out here: a second inlined copy of verify_solve_n<6> in this translation unit changes the register
+// allocation of k_loc_refine, which must stay as it is
+__device__ __forceinline__ uint32_t br_solve6(const float (*part)[256], float (*aug)[7], float* sol) {
+    constexpr int N = 6;
+    for (int i = 0, e = 0; i < N; i++)
+        for (int j = i; j < N; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
+    for (int i = 0; i < N; i++) aug[i][N] = part[N * (N + 1) / 2 + i][0];
+    uint32_t ok = 1u;
+    for (int c = 0; c < N && ok; c++) {
+        int piv = c;
+        float pmax = fabsf(aug[c][c]);
+        for (int r = c + 1; r < N; r++)
+            if (fabsf(aug[r][c]) > pmax) pmax = fabsf(aug[r][c]), piv = r;
+        if (pmax == 0.0f) {
+            ok = 0u;
+            break;
+        }
+        if (piv != c)
+            for (int q = 0; q < N + 1; q++) {
+                const float tmp = aug[c][q];
+                aug[c][q] = aug[piv][q];
+                aug[piv][q] = tmp;
+            }
+        for (int r = c + 1; r < N; r++) {
+            const float f = aug[r][c] / aug[c][c];
+            for (int q = c + 1; q < N + 1; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
+        }
+    }
+    if (ok)
+        for (int r = N - 1; r >= 0; r--) {
+            float s = aug[r][N];
+            for (int q = r + 1; q < N; q++) s = s - aug[r][q] * sol[q];
+            sol[r] = s / aug[r][r];
+            if (!isfinite(sol[r])) ok = 0u;
+        }
+    return ok;
+}
+
+// grid (frames), block 256; the inlier bytes are cleared by a memset before
+__global__ __launch_bounds__(256) void k_br_refine(BrArgs a) {
+    __shared__ float part[kLocSums][256];  // [sum][thread]: conflict-free columns
+    __shared__ float aug[6][7];
+    __shared__ float sol[6];
+    __shared__ float rowbuf[kLocRow];
+    __shared__ float cur[12];  // the model one lane made, for every thread: the winner, then each step's
+    __shared__ unsigned long long wkey[4];
+    __shared__ uint32_t s_ok, s_count;
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t s_join[2];  // m, consistent
+    __shared__ uint32_t s_sel[2];   // the prefix found so far, the rank within it
+    const LocArgs& L = a.loc;
+    const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t T;
+    const uint32_t kind = br_anchor(a, g, T);  // uniform
+    const uint32_t M = kind == 2u ? L.n_cand[g] : 0u;
+    const float4* const reca = L.reca + (size_t)g * L.cap;
+    const float4* const recb = L.recb + (size_t)g * L.cap;
+    unsigned long long best = 0ull;
+    if (M >= kLocSample)
+        for (uint32_t h = tid; h < L.hyps; h += 256u) best = max(best, L.keys[(size_t)g * kVerifyMaxHyp + h]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) best = max(best, (unsigned long long)__shfl_xor(best, off));
+    if (lane == 0u) wkey[wave] = best;
+    if (tid == 0u) s_count = 0u;
+    if (tid < 2u) s_join[tid] = 0u;
+    __syncthreads();
+    best = max(max(wkey[0], wkey[1]), max(wkey[2], wkey[3]));
+    const bool has_min = best != 0ull;  // uniform
+    const uint32_t h = has_min ? (kVerifyMaxHyp - 1u) - (uint32_t)(best & (kVerifyMaxHyp - 1u)) : 0u;
+    const uint32_t n_min = has_min ? (uint32_t)(best >> 12) - 1u : 0u;
+    float Rm[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, tm[3] = {0.f, 0.f, 0.f};
+    float Rc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, tc[3] = {0.f, 0.f, 0.f};
+    bool keep = false;
+    if (has_min) {
+        if (tid == 0u) {  // the winner rebuilt on one lane through an LDS row (valid: it scored a key)
+            float R[9], t[3];
+            (void)loc_model(reca, recb, M, lowbias32(L.seed_mix ^ g), h, rowbuf, R, t);
+#pragma unroll
+            for (int e = 0; e < 9; e++) cur[e] = R[e];
+#pragma unroll
+            for (int e = 0; e < 3; e++) cur[9 + e] = t[e];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 9; e++) Rc[e] = Rm[e] = cur[e];
+#pragma unroll
+        for (int e = 0; e < 3; e++) tc[e] = tm[e] = cur[9 + e];
+        bool fit = true;
+        for (uint32_t step = 0; step < kLocSteps && fit; step++) {  // LO-6; `fit` is uniform
+            float acc[kLocSums];
+#pragma unroll
+            for (uint32_t e = 0; e < kLocSums; e++) acc[e] = 0.0f;
+            for (uint32_t j = tid; j < M; j += 256u) {  // candidate j into partial sum j mod 256, ascending j; the inlier set is the winner's
+                const float4 Y = reca[j], k = recb[j];
+                if (loc_inlier(Rm, tm, Y.x, Y.y, Y.z, k.x, k.y, L)) loc_accumulate(acc, Rc, tc, Y, k, L);
+            }
+#pragma unroll
+            for (uint32_t e = 0; e < kLocSums; e++) part[e][tid] = acc[e];
+            __syncthreads();
+            for (uint32_t s = 128u; s >= 1u; s >>= 1) {  // pairwise tree, strides 128 .. 1
+                if (tid < s)
+                    for (uint32_t e = 0; e < kLocSums; e++) part[e][tid] = part[e][tid] + part[e][tid + s];
+                __syncthreads();
+            }
+            if (tid == 0u) {
+                uint32_t ok = br_solve6(part, aug, sol);
+                if (ok) {
+                    float R[9], t[3];
+#pragma unroll
+                    for (int e = 0; e < 9; e++) R[e] = Rc[e];
+#pragma unroll
+                    for (int e = 0; e < 3; e++) t[e] = tc[e];
+                    ok = loc_update(sol, R, t) ? 1u : 0u;
+#pragma unroll
+                    for (int e = 0; e < 9; e++) cur[e] = R[e];
+#pragma unroll
+                    for (int e = 0; e < 3; e++) cur[9 + e] = t[e];
+                }
+                s_ok = ok;
+            }
+            __syncthreads();
+            fit = s_ok != 0u;
+            if (fit) {
+#pragma unroll
+                for (int e = 0; e < 9; e++) Rc[e] = cur[e];
+#pragma unroll
+                for (int e = 0; e < 3; e++) tc[e] = cur[9 + e];
+            }
+            __syncthreads();  // s_ok and cur are read before the next step's lane writes them
+        }
+        if (fit) {
+            uint32_t n = 0;
+            for (uint32_t j = tid; j < M; j += 256u) {
+                const float4 Y = reca[j], k = recb[j];
+                n += loc_inlier(Rc, tc, Y.x, Y.y, Y.z, k.x, k.y, L) ? 1u : 0u;
+            }
+            atomicAdd(&s_count, n);
+        }
+        __syncthreads();
+        keep = fit && 16u * s_count >= 15u * n_min;  // GV-6's rule
+    }
+    float Rk[9], tk[3];
+#pragma unroll
+    for (int e = 0; e < 9; e++) Rk[e] = keep ? Rc[e] : Rm[e];
+#pragma unroll
+    for (int e = 0; e < 3; e++) tk[e] = keep ? tc[e] : tm[e];
+    // BR-7: an inlier byte per keypoint slot of frame g (same-value byte stores cannot race)
+    uint8_t* const mask = L.mask + (size_t)g * L.cap;
+    if (has_min)
+        for (uint32_t j = tid; j < M; j += 256u) {
+            const float4 Y = reca[j], k = recb[j];
+            if (loc_inlier(Rk, tk, Y.x, Y.y, Y.z, k.x, k.y, L)) mask[__float_as_uint(Y.w)] = 1u;
+        }
+    // BR-5
+    const bool join = keep && g + 2u <= a.n_frames && a.frames[(size_t)(g + 1u) * kBrFrameWords + 17u] == ORB_TRAJ_START;  // uniform
+    uint32_t m = 0u, gam = 0u, consistent = 0u, verdict = kTrajFew;
+    if (join) {
+        uint32_t* const row = a.ratios + (size_t)g * L.cap;
+        const float4* const pts = L.points + (size_t)g * L.cap;
+        const bool first = lane == 0u;
+        // A: the ratio's bits of every candidate (0: none)
+        for (uint32_t j0 = 0u; j0 < M; j0 += 256u) {  // uniform trip count: the ballots see whole waves
+            const uint32_t j = j0 + tid;
+            uint32_t bits = 0u;
+            if (j < M) {
+                const float4 Y = reca[j], k = recb[j];
+                if (loc_inlier(Rk, tk, Y.x, Y.y, Y.z, k.x, k.y, L)) {
+                    const float4 P = pts[__float_as_uint(Y.w)];
+                    if ((__float_as_uint(P.w) & ORB_POINT_GOOD) != 0u) {
+                        float x, y, z;
+                        loc_transform(Rk, tk, Y.x, Y.y, Y.z, x, y, z);
+                        const float rho = z / P.z;
+                        bits = isfinite(rho) && rho > 0.0f ? __float_as_uint(rho) : 0u;
+                    }
+                }
+                row[j] = bits;
+            }
+            const uint32_t n = (uint32_t)__popcll(__ballot(bits != 0u));
+            if (first && n) atomicAdd(&s_join[0], n);
+        }
+        __syncthreads();  // every thread reads back its own stores only; the barrier publishes the count
+        m = s_join[0];
+        if (m) {  // uniform
+            // B: the element of rank (m - 1) / 2 in ascending order of the bits (k_traj_joint's radix select)
+            if (tid == 0u) {
+                s_sel[0] = 0u;
+                s_sel[1] = (m - 1u) / 2u;
+            }
+#pragma unroll 1
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                hist[tid] = 0u;
+                __syncthreads();
+                const uint32_t prefix = s_sel[0];
+                for (uint32_t j = tid; j < M; j += 256u) {
+                    const uint32_t bits = row[j];
+                    const bool in = bits != 0u && (shift == 24 || (bits >> (shift + 8)) == prefix);
+                    if (in) atomicAdd(&hist[bits >> shift & 255u], 1u);
+                }
+                __syncthreads();
+                if (tid < 64u) {  // lane l owns bins 4 l .. 4 l + 3
+                    const uint32_t k = s_sel[1];
+                    const uint32_t h0 = hist[4u * tid], h1 = hist[4u * tid + 1u], h2 = hist[4u * tid + 2u], h3 = hist[4u * tid + 3u];
+                    const uint32_t sum = (h0 + h1) + (h2 + h3);
+                    uint32_t incl = sum;
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const uint32_t up = __shfl_up(incl, d);
+                        if ((int)tid >= d) incl += up;
+                    }
+                    uint32_t lo = incl - sum;  // ratios in the bins below this lane's
+                    if (k >= lo && k < incl) {  // one lane
+                        uint32_t bin = 4u * tid;
+                        const uint32_t hh[3] = {h0, h1, h2};
+                        bool past = true;
+#pragma unroll
+                        for (int q = 0; q < 3; q++) {
+                            past = past && k >= lo + hh[q];
+                            lo += past ? hh[q] : 0u;
+                            bin += past ? 1u : 0u;
+                        }
+                        s_sel[0] = prefix << 8 | bin;
+                        s_sel[1] = k - lo;
+                    }
+                }
+                __syncthreads();
+            }
+            gam = s_sel[0];
+            // C
+            const float gf = __uint_as_float(gam), tg = a.tol * gf;
+            for (uint32_t j0 = 0u; j0 < M; j0 += 256u) {
+                const uint32_t j = j0 + tid;
+                const uint32_t bits = j < M ? row[j] : 0u;
+                const bool in = bits != 0u && fabsf(__uint_as_float(bits) - gf) <= tg;
+                const uint32_t n = (uint32_t)__popcll(__ballot(in));
+                if (first && n) atomicAdd(&s_join[1], n);
+            }
+            __syncthreads();
+            consistent = s_join[1];
+        }
+        verdict = m < a.min_shared ? kTrajFew : (1000ull * consistent < (unsigned long long)a.permille * m ? kTrajSpread : kTrajHolds);
+    }
+    if (tid == 0u) {  // the fix record
+        uint32_t* const out = L.fix + (size_t)g * kBrFixWords;
+#pragma unroll
+        for (int e = 0; e < 9; e++) out[e] = has_min ? __float_as_uint(Rk[e]) : 0u;
+#pragma unroll
+        for (int e = 0; e < 3; e++) out[9 + e] = has_min ? __float_as_uint(tk[e]) : 0u;
+        out[12] = has_min ? __float_as_uint(sqrtf((tk[0] * tk[0] + tk[1] * tk[1]) + tk[2] * tk[2])) : 0u;
+        out[13] = has_min ? M : 0u;
+        out[14] = has_min ? (keep ? s_count : n_min) : 0u;
+        out[15] = h;
+        out[16] = kind != 2u ? (uint32_t)ORB_LOCALIZE_NOMAP
+                  : M < kLocSample ? (uint32_t)ORB_LOCALIZE_FEW
+                  : !has_min ? (uint32_t)ORB_LOCALIZE_DEGENERATE
+                  : keep ? (uint32_t)ORB_LOCALIZE_OK
+                         : (uint32_t)ORB_LOCALIZE_MINIMAL;
+        out[17] = m;
+        out[18] = gam;
+        out[19] = consistent;
+        out[20] = join && verdict == kTrajHolds ? 1u : 0u;
+        out[21] = out[22] = out[23] = 0u;
+    }
+}
+
+// BR-6: S_o of origin o, read back from the record this lane wrote for frame o: the frame's own pose, gain and root when it is
+// JOINED, else (I, 0, 1, o).  The records of the frames below f are written (frame 0 is its own origin and never JOINED).
+__device__ __forceinline__ void br_similarity(const uint32_t* out, uint32_t o, uint32_t f, float A[9], float t[3], float& sigma, uint32_t& root) {
+    const uint32_t* const rec = out + (size_t)o * kBrOutWords;
+    const bool joined = o < f && rec[22] == ORB_BRIDGE_JOINED;
+#pragma unroll
+    for (int k = 0; k < 9; k++) A[k] = joined ? __uint_as_float(rec[k]) : ((k & 3) == 0 ? 1.0f : 0.0f);
+#pragma unroll
+    for (int k = 0; k < 3; k++) t[k] = joined ? __uint_as_float(rec[9 + k]) : 0.0f;
+    sigma = joined ? __uint_as_float(rec[13]) : 1.0f;
+    root = joined ? rec[14] : o;
+}
+
+// grid 1, block 64
+__global__ __launch_bounds__(64) void k_br_chain(BrArgs a) {
+    __shared__ uint32_t s_frame[kBrChunk * kBrFrameWords];  // frame[base + k], k < 64
+    __shared__ uint32_t s_fix[kBrChunk * kBrFixWords];      // fix[base + k]
+    const uint32_t lane = threadIdx.x;
+    float RT[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f}, tT[3] = {0.0f, 0.0f, 0.0f};  // the last frame that is not LOST
+    uint32_t T = 0u, oT = 0u;
+    for (uint32_t base = 0u; base < a.n_frames; base += kBrChunk) {
+        __syncthreads();  // lane 0 is done with the chunk before
+        {
+            const uint32_t w0 = base * kBrFrameWords, wn = a.n_frames * kBrFrameWords;
+#pragma unroll
+            for (uint32_t k = 0u; k < kBrFrameWords; k++) {
+                const uint32_t w = k * 64u + lane;
+                s_frame[w] = w0 + w < wn ? a.frames[w0 + w] : 0u;
+            }
+            const uint32_t x0 = base * kBrFixWords, xn = a.n_frames * kBrFixWords;
+#pragma unroll
+            for (uint32_t k = 0u; k < kBrFixWords; k++) {
+                const uint32_t w = k * 64u + lane;
+                s_fix[w] = x0 + w < xn ? a.loc.fix[x0 + w] : 0u;
+            }
+        }
+        __syncthreads();
+        const uint32_t end = min(base + kBrChunk, a.n_frames);
+#pragma unroll 1
+        for (uint32_t f = base; lane == 0u && f < end; f++) {
+            const uint32_t* const P = s_frame + (f - base) * kBrFrameWords;
+            const uint32_t* const X = s_fix + (f - base) * kBrFixWords;
+            float R[9], t[3];
+#pragma unroll
+            for (int k = 0; k < 9; k++) R[k] = __uint_as_float(P[k]);
+#pragma unroll
+            for (int k = 0; k < 3; k++) t[k] = __uint_as_float(P[9 + k]);
+            float scale = __uint_as_float(P[12]), gain = 0.0f;
+            uint32_t root = f, status, anchor = 0u;
+            if (P[17] != ORB_TRAJ_LOST) {
+                const uint32_t o = P[14];
+                float A[9], av[3], sigma;
+                br_similarity(a.out, o, f, A, av, sigma, root);
+#pragma unroll
+                for (int k = 0; k < 9; k++) RT[k] = R[k];
+#pragma unroll
+                for (int k = 0; k < 3; k++) tT[k] = t[k];
+                T = f;
+                oT = o;
+                if (f == 0u || root == o) {
+                    status = ORB_BRIDGE_COPIED;
+                    gain = 1.0f;
+                    root = f == 0u ? 0u : o;
+                } else {
+                    status = ORB_BRIDGE_MOVED;
+                    float Rn[9], tn[3];
+                    br_compose(R, t, sigma, A, av, Rn, tn);
+#pragma unroll
+                    for (int k = 0; k < 9; k++) R[k] = Rn[k];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) t[k] = tn[k];
+                    scale = sigma * scale;
+                    gain = sigma;
+                }
+            } else {
+                status = ORB_BRIDGE_UNFIXED;
+                anchor = T;
+                if (X[16] == ORB_LOCALIZE_OK) {
+                    float Rx[9], tx[3], Rg[9], tg[3], A[9], av[3], sigma;
+                    uint32_t ro;
+#pragma unroll
+                    for (int k = 0; k < 9; k++) Rx[k] = __uint_as_float(X[k]);
+#pragma unroll
+                    for (int k = 0; k < 3; k++) tx[k] = __uint_as_float(X[9 + k]);
+                    br_compose(Rx, tx, 1.0f, RT, tT, Rg, tg);  // BR-4: camera g in segment oT
+                    br_similarity(a.out, oT, f, A, av, sigma, ro);
+                    if (ro != oT) {
+                        float Rn[9], tn[3];
+                        br_compose(Rg, tg, sigma, A, av, Rn, tn);
+#pragma unroll
+                        for (int k = 0; k < 9; k++) Rg[k] = Rn[k];
+#pragma unroll
+                        for (int k = 0; k < 3; k++) tg[k] = tn[k];
+                    }
+                    const float sc = sigma * __uint_as_float(X[12]);
+                    const bool joined = X[20] != 0u;
+                    const float sg = joined ? sigma * __uint_as_float(X[18]) : 0.0f;
+                    bool fin = isfinite(sc) && isfinite(sg);
+#pragma unroll
+                    for (int k = 0; k < 9; k++) fin = fin && isfinite(Rg[k]);
+#pragma unroll
+                    for (int k = 0; k < 3; k++) fin = fin && isfinite(tg[k]);
+                    if (fin) {
+                        status = joined ? ORB_BRIDGE_JOINED : ORB_BRIDGE_FIXED;
+#pragma unroll
+                        for (int k = 0; k < 9; k++) R[k] = Rg[k];
+#pragma unroll
+                        for (int k = 0; k < 3; k++) t[k] = tg[k];
+                        scale = sc;
+                        gain = sg;
+                        root = ro;
+                    }
+                }
+            }
+            const bool gap = P[17] == ORB_TRAJ_LOST;
+            uint32_t* const out = a.out + (size_t)f * kBrOutWords;
+#pragma unroll
+            for (int k = 0; k < 9; k++) out[k] = __float_as_uint(R[k]);
+#pragma unroll
+            for (int k = 0; k < 3; k++) out[9 + k] = __float_as_uint(t[k]);
+            out[12] = __float_as_uint(scale);
+            out[13] = __float_as_uint(gain);
+            out[14] = root;
+            out[15] = anchor;
+            out[16] = gap ? X[13] : 0u;
+            out[17] = gap ? X[14] : 0u;
+            out[18] = gap ? X[15] : 0u;
+            out[19] = gap ? X[17] : 0u;
+            out[20] = gap ? X[19] : 0u;
+            out[21] = gap ? X[16] : (uint32_t)ORB_LOCALIZE_NOMAP;
+            out[22] = status;
+            out[23] = 0u;
+        }
+    }
+}
+
+}  // namespace orb

@@ -71,6 +71,11 @@ LANDMARK_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("flags", "
                            ("origin", "<u4"), ("tail_index", "<u4"), ("reserved", "<u4", (1,))])
 LANDMARK_ROW_DTYPE = np.dtype([("landmarks", "<u4"), ("good", "<u4"), ("longest", "<u4"), ("origin", "<u4")])
 ORB_LANDMARK_NO_ORIGIN = 0xFFFFFFFF
+# a trajectory carried across LOST frames (orb_bridge_consecutive): OrbBridgePose (96 B), its status
+BRIDGE_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4"), ("gain", "<f4"), ("root", "<u4"), ("anchor", "<u4"),
+                              ("candidates", "<u4"), ("inliers", "<u4"), ("hypothesis", "<u4"), ("shared", "<u4"), ("consistent", "<u4"),
+                              ("fix", "<u4"), ("status", "<u4"), ("reserved", "<u4", (1,))])
+ORB_BRIDGE_COPIED, ORB_BRIDGE_MOVED, ORB_BRIDGE_FIXED, ORB_BRIDGE_JOINED, ORB_BRIDGE_UNFIXED = 0, 1, 2, 3, 4
 # feature tracks and keyframes (orb_track_consecutive): the link source, OrbTrack (16 B), OrbTrackFrame (32 B)
 ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
 TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
@@ -100,6 +105,7 @@ EXPORTS = [
     "orb_trajectory_consecutive", "orb_trajectory_read", "orb_debug_pose_buffers",
     "orb_localize_consecutive", "orb_localize_read",
     "orb_landmarks_consecutive", "orb_landmarks_read",
+    "orb_bridge_consecutive", "orb_bridge_read",
 ]
 
 
@@ -176,6 +182,18 @@ class _LandmarkParams(ctypes.Structure):
 
 
 OrbLandmarkParams = _LandmarkParams
+
+
+class _BridgeParams(ctypes.Structure):
+    """OrbBridgeParams (64 bytes; fx and fy must be > 0, the other zero fields = the defaults)"""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("max_reproj_px", ctypes.c_float), ("hypotheses", ctypes.c_uint32), ("max_distance", ctypes.c_uint32),
+                ("ratio", ctypes.c_float), ("seed", ctypes.c_uint32), ("max_hops", ctypes.c_uint32), ("window", ctypes.c_uint32),
+                ("min_shared", ctypes.c_uint32), ("scale_tolerance", ctypes.c_float), ("consistent_permille", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+OrbBridgeParams = _BridgeParams
 
 
 class _TrackParams(ctypes.Structure):
@@ -272,6 +290,8 @@ def load_library(path=None):
     L.orb_localize_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_landmarks_consecutive.argtypes = [vp, u32, ctypes.POINTER(_LandmarkParams), vp]
     L.orb_landmarks_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_bridge_consecutive.argtypes = [vp, u32, ctypes.POINTER(_BridgeParams), vp]
+    L.orb_bridge_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -767,6 +787,26 @@ class OrbProgram:
         lm = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=LANDMARK_DTYPE)
         self._check(self._lib.orb_landmarks_read(self._handle(), pair, _ptr(row), _ptr(lm) if len(lm) else None, len(lm)))
         return row, lm
+
+    def bridge_consecutive(self, n_frames, fx, fy, cx, cy, max_reproj_px=0.0, hypotheses=0, max_distance=0, ratio=0.0, seed=0, max_hops=0,
+                           window=0, min_shared=0, scale_tolerance=0.0, consistent_permille=0, stream=None, reserved=(0, 0)):
+        """A trajectory carried across LOST frames (not in the reference): for every LOST frame of
+        the last trajectory_consecutive, the GOOD landmarks of the last landmarks_consecutive that end in the frame before the gap
+        are followed through the matcher's records into it and give its pose by localize_consecutive's RANSAC; a segment that
+        starts behind it is measured against the old one by the lower median of depth ratios.  Every frame gets a pose in the
+        frame and unit of its root.  Zero parameters are the defaults; asynchronous on `stream`."""
+        prm = _BridgeParams(float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
+                            float(np.float32(max_reproj_px)), hypotheses, max_distance, float(np.float32(ratio)), seed & 0xFFFFFFFF, max_hops,
+                            window, min_shared, float(np.float32(scale_tolerance)), consistent_permille, (ctypes.c_uint32 * 2)(*reserved))
+        self._check(self._lib.orb_bridge_consecutive(self._handle(), n_frames, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def bridge_read(self, frame, n=None):
+        """(record of BRIDGE_POSE_DTYPE, uint8[min(n, max_features)]: the inlier bytes of frame `frame`'s keypoint slots; n None:
+        max_features) of the last bridge_consecutive -- synchronises."""
+        rec = np.zeros((), dtype=BRIDGE_POSE_DTYPE)
+        mask = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=np.uint8)
+        self._check(self._lib.orb_bridge_read(self._handle(), frame, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
+        return rec, mask
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
