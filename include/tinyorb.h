@@ -860,6 +860,12 @@ int orb_debug_rot_table(OrbProgram *p, int16_t *dst, size_t n_entries, uint32_t 
  * on every stream a stage ran on before writing, a device synchronise after writing and before the next call.  No stage's
  * freshness state is touched: the library goes on treating the buffers as the results of its last match and pose calls. */
 int orb_debug_pose_buffers(OrbProgram *p, void **matches, void **poses, void **points);
+/* For tests: the device pointer of the frame records that orb_trajectory_consecutive writes and that orb_trajectory_read,
+ * orb_landmarks_consecutive and orb_bridge_consecutive read (frames may be NULL): frames[max_batch] OrbFramePose, 20 words each.
+ * ORB_ESTATE until an orb_trajectory_consecutive call has allocated it.  The ordering of a test's own writes is the caller's, as
+ * for orb_debug_pose_buffers, and no stage's freshness state is touched: the library goes on treating the buffer as the result
+ * of its last trajectory call. */
+int orb_debug_frame_buffer(OrbProgram *p, void **frames);
 
 /* ---- measurement ---- */
 #define ORB_KERNEL_COUNT 25

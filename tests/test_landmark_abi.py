@@ -51,6 +51,23 @@ def test_exports_and_null_arguments(tinyorb):
     assert tinyorb.ORB_KERNEL_COUNT == 25 and not any("k_lm" in n for n in names)
 
 
+def test_the_frame_buffer_accessor(tinyorb):
+    """orb_debug_frame_buffer, the tests' way to the frame records the stage reads: declared, exported, mirrored, and ORB_EINVAL for a
+    NULL program without touching the out-pointer."""
+    text = open(HEADER).read()
+    sigs = dict(re.findall(r"^int (orb_debug_(?:frame|pose)_buffers?)\(([^)]*)\);", text, re.M))
+    assert sigs == {"orb_debug_pose_buffers": "OrbProgram *p, void **matches, void **poses, void **points",
+                    "orb_debug_frame_buffer": "OrbProgram *p, void **frames"}
+    L = tinyorb.load_library()
+    assert "orb_debug_frame_buffer" in tinyorb.EXPORTS and hasattr(L, "orb_debug_frame_buffer")
+    vp = ctypes.c_void_p
+    assert L.orb_debug_frame_buffer.argtypes == [vp, ctypes.POINTER(vp)] and hasattr(tinyorb.OrbProgram, "debug_frame_buffer")
+    out = vp()
+    assert L.orb_debug_frame_buffer(None, ctypes.byref(out)) == tinyorb.ORB_EINVAL and not out.value
+    assert L.orb_debug_frame_buffer(None, None) == tinyorb.ORB_EINVAL
+    assert tinyorb.FRAME_POSE_DTYPE.itemsize == 80  # the 20 words a row of the buffer has
+
+
 def test_the_restatement_reads_the_mirror_and_the_kernels_the_same_layout():
     """The record's words as the kernel header stores them: two 16-byte halves, views in the low half of the fifth word."""
     import landmark_ref as lmr

@@ -3081,6 +3081,13 @@ int orb_debug_pose_buffers(OrbProgram* p, void** matches, void** poses, void** p
     return ORB_OK;
 }
 
+int orb_debug_frame_buffer(OrbProgram* p, void** frames) {
+    if (!p) return ORB_EINVAL;
+    if (!p->d_jframe) return fail(p, ORB_ESTATE, "debug_frame_buffer before orb_trajectory_consecutive");
+    if (frames) *frames = p->d_jframe;
+    return ORB_OK;
+}
+
 int orb_level_size(const OrbProgram* p, uint32_t level, uint32_t* width, uint32_t* height) {
     if (!p || level >= p->pyr.depth) return ORB_EINVAL;
     if (width) *width = p->pyr.w[level];

@@ -102,7 +102,7 @@ EXPORTS = [
     "orb_verify_consecutive", "orb_verify_read", "orb_match_guided", "orb_match_guided_read",
     "orb_track_consecutive", "orb_track_read", "orb_track_frames", "orb_verify_epipolar", "orb_verify_epipolar_read",
     "orb_match_epipolar", "orb_match_epipolar_read", "orb_pose_consecutive", "orb_pose_read",
-    "orb_trajectory_consecutive", "orb_trajectory_read", "orb_debug_pose_buffers",
+    "orb_trajectory_consecutive", "orb_trajectory_read", "orb_debug_pose_buffers", "orb_debug_frame_buffer",
     "orb_localize_consecutive", "orb_localize_read",
     "orb_landmarks_consecutive", "orb_landmarks_read",
     "orb_bridge_consecutive", "orb_bridge_read",
@@ -268,6 +268,7 @@ def load_library(path=None):
     L.orb_batch_device_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.orb_level_size.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.orb_debug_pose_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    L.orb_debug_frame_buffer.argtypes = [vp, ctypes.POINTER(vp)]
     L.orb_debug_read_plane.argtypes = [vp, u32, ctypes.c_int, u32, vp, sz]
     L.orb_debug_f32_to_f16.argtypes = [vp, vp, vp, sz]
     L.orb_debug_angle_code.argtypes = [vp, vp, vp, vp, sz]
@@ -847,6 +848,13 @@ class OrbProgram:
         a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._check(self._lib.orb_debug_pose_buffers(self._handle(), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
+
+    def debug_frame_buffer(self):
+        """For tests: the device address of the frame records [max_batch] FRAME_POSE_DTYPE that trajectory_consecutive writes and
+        trajectory_read, landmarks_consecutive and bridge_consecutive read.  The caller orders its own writes."""
+        a = ctypes.c_void_p()
+        self._check(self._lib.orb_debug_frame_buffer(self._handle(), ctypes.byref(a)))
+        return a.value
 
     # ---- inspection / measurement -------------------------------------------------------------
     def pipeline(self):
