@@ -435,3 +435,20 @@ def dense_cell(rng, x0, y0, extra, W=256, H=256):
     qd = flip(td[:64], 3, rng)
     qc = corners(np.clip(xs.ravel() + 1, 0, W - 1), ys.ravel(), rng=rng)  # the queries one pixel to the right (distinct within frame 0)
     return qc, qd, corners(tx, ty, rng=rng), td
+
+
+# ---- the arguments every stage's read call shares ------------------------------------------------------------------------------
+def check_read_arguments(T, prog, fn, extent, elem_bytes, head):
+    """On a stage whose last call covered `extent` rows: the C read call `fn` (with a head record before the rows when `head`)
+    rejects row `extent`, reads row extent - 1, takes NULL rows with n = 0 and not with n = 1, and clips n to max_features."""
+    h, cap = prog._handle(), prog.config.max_features
+    call = (lambda i, rows, n: fn(h, i, None, rows, n)) if head else (lambda i, rows, n: fn(h, i, rows, n))
+    more = min(100, cap)  # rows 0 and 1 of the stage's buffer hold cap + more elements, whatever the call copies
+    big = np.full((cap + more) * elem_bytes, 0xA5, dtype=np.uint8)
+    assert call(extent, big.ctypes.data, 1) == T.ORB_EINVAL
+    assert call(extent - 1, big.ctypes.data, 1) == T.ORB_OK
+    assert call(0, None, 0) == T.ORB_OK
+    assert call(0, None, 1) == T.ORB_EINVAL
+    big[:] = 0xA5
+    assert call(0, big.ctypes.data, cap + more) == T.ORB_OK
+    assert np.all(big[cap * elem_bytes:] == 0xA5)  # nothing past max_features elements was written

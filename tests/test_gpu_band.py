@@ -333,6 +333,7 @@ def test_state_arguments_and_ordering(tinyorb, oracle):
         with pytest.raises(tinyorb.OrbError) as e:
             prog.match_epipolar_read(2, cap)  # two pairs only
         assert e.value.code == tinyorb.ORB_EINVAL
+        C.check_read_arguments(tinyorb, prog, tinyorb.load_library().orb_match_epipolar_read, 2, 8, head=False)
         # the other stages' results are untouched by band calls
         prog.match_guided(4, source=tinyorb.ORB_GUIDE_VERIFIED, radius_px=3.0)
         prog.track_consecutive(4)

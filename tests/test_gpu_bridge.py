@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import bridge_cases as B
+import constructed as C
 import bridge_ref as brr
 import localize_cases as lc
 
@@ -219,6 +220,7 @@ def test_isolation_state_arguments_and_ordering(tinyorb):
         assert lib.orb_bridge_read(prog._handle(), 0, None, None, 5) == T.ORB_EINVAL  # inliers NULL with n > 0
         assert lib.orb_bridge_read(prog._handle(), 0, None, None, 0) == T.ORB_OK
         assert len(prog.bridge_read(1, cap + 100)[1]) == cap and len(prog.bridge_read(1)[1]) == cap and len(prog.bridge_read(1, 7)[1]) == 7
+        C.check_read_arguments(T, prog, lib.orb_bridge_read, n, 1, head=True)
         # isolation: the other stages' read-backs before and after bridge calls
         prog.verify_consecutive(n, inlier_px=2.0)
         prog.localize_consecutive(n, **INTR)

@@ -209,6 +209,7 @@ def test_state_and_ordering(tinyorb, oracle):
         with pytest.raises(tinyorb.OrbError) as e:
             prog.verify_epipolar_read(2, cap)  # two pairs only
         assert e.value.code == tinyorb.ORB_EINVAL
+        C.check_read_arguments(tinyorb, prog, tinyorb.load_library().orb_verify_epipolar_read, 2, 1, head=True)
         with pytest.raises(tinyorb.OrbError) as e:
             prog.verify_read(0, cap)  # the homography verifier has run nowhere
         assert e.value.code == tinyorb.ORB_ESTATE

@@ -5,6 +5,7 @@ cell size."""
 import numpy as np
 import pytest
 
+import constructed as C
 import guided_ref as gr
 
 pytestmark = pytest.mark.gpu
@@ -227,6 +228,7 @@ def test_state_and_ordering(tinyorb, oracle):
         with pytest.raises(tinyorb.OrbError) as e:
             prog.match_guided_read(2, cap)  # two pairs only
         assert e.value.code == tinyorb.ORB_EINVAL
+        C.check_read_arguments(tinyorb, prog, tinyorb.load_library().orb_match_guided_read, 2, 8, head=False)
         # the matcher's and the verifier's results are untouched by a guided call
         before = [(prog.match_read(f, cap).tobytes(), prog.verify_read(f, cap)[0].tobytes(), prog.verify_read(f, cap)[1].tobytes())
                   for f in range(2)]

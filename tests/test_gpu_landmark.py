@@ -7,6 +7,7 @@ untouched; the call's state, argument and stream rules."""
 import numpy as np
 import pytest
 
+import constructed as C
 import landmark_cases as L
 import landmark_ref as lmr
 import localize_cases as lc
@@ -204,6 +205,7 @@ def test_isolation_state_arguments_and_ordering(tinyorb):
         assert lib.orb_landmarks_read(prog._handle(), 0, None, None, 5) == T.ORB_EINVAL  # landmarks NULL with n > 0
         assert lib.orb_landmarks_read(prog._handle(), 0, None, None, 0) == T.ORB_OK
         assert len(prog.landmarks_read(1, cap + 100)[1]) == cap and len(prog.landmarks_read(1)[1]) == cap and len(prog.landmarks_read(1, 7)[1]) == 7
+        C.check_read_arguments(T, prog, lib.orb_landmarks_read, n - 1, 32, head=True)
         # isolation: the other stages' read-backs before and after landmarks calls
         prog.verify_consecutive(n, inlier_px=2.0)
         prog.localize_consecutive(n, **INTR)

@@ -6,6 +6,7 @@ results untouched; the call's state, argument and stream rules."""
 import numpy as np
 import pytest
 
+import constructed as C
 import localize_cases as lc
 import localize_ref as lr
 
@@ -195,6 +196,7 @@ def test_isolation_state_arguments_and_ordering(tinyorb):
         assert L.orb_localize_read(prog._handle(), 0, None, None, 5) == T.ORB_EINVAL  # inliers NULL with n > 0
         assert L.orb_localize_read(prog._handle(), 0, None, None, 0) == T.ORB_OK
         assert len(prog.localize_read(1, cap + 100)[1]) == cap and len(prog.localize_read(1)[1]) == cap and len(prog.localize_read(1, 7)[1]) == 7
+        C.check_read_arguments(T, prog, L.orb_localize_read, n - 1, 1, head=True)
         # isolation: the other stages' read-backs before and after localize calls
         prog.verify_consecutive(n, inlier_px=2.0)
         prog.trajectory_consecutive(n)

@@ -201,6 +201,7 @@ def test_isolation_state_arguments_and_ordering(tinyorb, oracle):
         before = others()
         inputs = _inputs(prog, n, cap)
         one = [r.tobytes() + p.tobytes() for r, p in _check(prog, n, cap, inputs, INTR1)]
+        C.check_read_arguments(tinyorb, prog, L.orb_pose_read, n - 1, 16, head=True)
         _check(prog, 2, cap, inputs, INTR1, max_reproj_px=0.5)
         assert others() == before
         # ordering: a pose call on a second stream, then an epipolar verification on the first that overwrites what it read: it waits

@@ -5,6 +5,7 @@ stream rules; and the links' correctness on views with a known motion."""
 import numpy as np
 import pytest
 
+import constructed as C
 import track_ref as tr
 
 pytestmark = pytest.mark.gpu
@@ -201,6 +202,7 @@ def test_state_and_ordering(tinyorb, oracle):
         with pytest.raises(tinyorb.OrbError) as e:
             prog.track_read(4, cap)  # four frames only
         assert e.value.code == tinyorb.ORB_EINVAL
+        C.check_read_arguments(tinyorb, prog, tinyorb.load_library().orb_track_read, 4, 16, head=False)
         assert len(prog.track_frames(10)) == 4
         # the matcher's, the verifier's and the guided call's results are untouched by a track call
         prog.match_guided(5, source=tinyorb.ORB_GUIDE_IDENTITY)

@@ -189,6 +189,7 @@ def test_isolation_state_arguments_and_ordering(tinyorb):
         assert L.orb_trajectory_read(prog._handle(), 0, None, None, 5) == T.ORB_EINVAL  # points NULL with n > 0
         assert L.orb_trajectory_read(prog._handle(), 0, None, None, 0) == T.ORB_OK
         assert len(prog.trajectory_read(0, cap + 100)[1]) == cap and len(prog.trajectory_read(0)[1]) == cap
+        C.check_read_arguments(T, prog, L.orb_trajectory_read, n, 16, head=True)
         # isolation: the other stages' read-backs before and after trajectory calls
         prog.verify_consecutive(n, inlier_px=2.0)
 

@@ -4,6 +4,7 @@ rules and its stream ordering."""
 import numpy as np
 import pytest
 
+import constructed as C
 import verify_ref as vr
 
 pytestmark = pytest.mark.gpu
@@ -202,6 +203,7 @@ def test_state_and_ordering(tinyorb, oracle):
         with pytest.raises(tinyorb.OrbError) as e:
             prog.verify_read(2, cap)  # two pairs only
         assert e.value.code == tinyorb.ORB_EINVAL
+        C.check_read_arguments(tinyorb, prog, tinyorb.load_library().orb_verify_read, 2, 1, head=True)
         # the same verification on another stream than the match's: ordered behind it, the same records
         s = torch.cuda.Stream(device=0)
         prog.match_consecutive(4)

@@ -68,21 +68,75 @@ struct ProfSpan {
 
 // The stages that run after extraction.  Each owns ONE set of buffers per program, shared by both output sets and by whatever stream
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
-// stages whose results it reads, which the entry point names; and the stages that read what it overwrites, kReadersOf[stage].
+// stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
+// which is that table transposed.
 enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_COUNT };
-const uint32_t kReadersOf[ST_COUNT] = {
-    1u << ST_VERIFY | 1u << ST_EPI | 1u << ST_TRACK | 1u << ST_POSE | 1u << ST_TRAJ | 1u << ST_LOCALIZE | 1u << ST_LANDMARK | 1u << ST_BRIDGE,  // match: d_matches (both verifiers gather from it; track links MATCHED and VERIFIED through it; pose pairs the inliers by it; trajectory pairs the points of two pairs by it; localize carries a point over two pairs by it; landmarks chains the pairs' points by it; bridge carries a landmark into a LOST frame by it)
-    1u << ST_GUIDE | 1u << ST_TRACK,                  // verify: verify.model (guided, ORB_GUIDE_VERIFIED), verify.mask (track, ORB_TRACK_VERIFIED)
-    1u << ST_BAND | 1u << ST_POSE,                    // epi: epi.model (band, ORB_BAND_VERIFIED; pose), epi.mask (pose)
-    1u << ST_TRACK,                                   // guide: d_gmatch (track, ORB_TRACK_GUIDED)
-    0u,                                               // track: read back by the host
-    0u,                                               // band: d_bmatch is read back by the host
-    1u << ST_TRAJ | 1u << ST_LOCALIZE | 1u << ST_LANDMARK | 1u << ST_BRIDGE,  // pose: d_pose, d_ppoints (trajectory, localize; landmarks and bridge read d_ppoints)
-    1u << ST_LANDMARK | 1u << ST_BRIDGE,              // trajectory: d_jframe (landmarks, bridge)
-    0u,                                               // localize: read back by the host
-    1u << ST_BRIDGE,                                  // landmarks: d_mland (bridge)
-    0u,                                               // bridge: read back by the host
+
+// A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
+struct StageInfo {
+    const char* name;
+    const char* read_name;
+    uint32_t reads;
 };
+constexpr StageInfo kStages[ST_COUNT] = {
+    {"match_consecutive", "match_read", 0u},
+    {"verify_consecutive", "verify_read",
+     1u << ST_MATCH},     // d_matches: the gather's candidates
+    {"verify_epipolar", "verify_epipolar_read",
+     1u << ST_MATCH},     // d_matches: the same gather
+    {"match_guided", "match_guided_read",
+     1u << ST_VERIFY},    // verify.model (ORB_GUIDE_VERIFIED; waited for whatever the source)
+    {"track_consecutive", "track_read",
+     1u << ST_MATCH |     // d_matches: the links of MATCHED and VERIFIED
+     1u << ST_VERIFY |    // verify.mask (ORB_TRACK_VERIFIED)
+     1u << ST_GUIDE},     // guide.match (ORB_TRACK_GUIDED)
+    {"match_epipolar", "match_epipolar_read",
+     1u << ST_EPI},       // epi.model (ORB_BAND_VERIFIED; waited for whatever the source)
+    {"pose_consecutive", "pose_read",
+     1u << ST_MATCH |     // d_matches: pairs the inliers
+     1u << ST_EPI},       // epi.model, epi.mask
+    {"trajectory_consecutive", "trajectory_read",
+     1u << ST_MATCH |     // d_matches: pairs the points of two pairs
+     1u << ST_POSE},      // d_pose, d_ppoints
+    {"localize_consecutive", "localize_read",
+     1u << ST_MATCH |     // d_matches: carries a point over two pairs
+     1u << ST_POSE},      // d_pose, d_ppoints
+    {"landmarks_consecutive", "landmarks_read",
+     1u << ST_MATCH |     // d_matches: chains the pairs' points
+     1u << ST_POSE |      // d_ppoints
+     1u << ST_TRAJ},      // d_jframe
+    {"bridge_consecutive", "bridge_read",
+     1u << ST_MATCH |     // d_matches: carries a landmark into a LOST frame
+     1u << ST_POSE |      // d_ppoints
+     1u << ST_TRAJ |      // d_jframe
+     1u << ST_LANDMARK},  // d_mland
+};
+static_assert(kStages[ST_COUNT - 1].name != nullptr, "a row of kStages for every StageId");
+
+// kReaders.of[s]: the stages that read what stage s writes (0: its results are read back by the host only)
+struct ReadersOf {
+    uint32_t of[ST_COUNT];
+};
+constexpr ReadersOf readers_of() {
+    ReadersOf r{};
+    for (int reader = 0; reader < ST_COUNT; reader++)
+        for (int s = 0; s < ST_COUNT; s++)
+            if (kStages[reader].reads >> s & 1u) r.of[s] |= 1u << reader;
+    return r;
+}
+constexpr ReadersOf kReaders = readers_of();
+
+// What the stages' kernels write as words and the reads hand out as structs of tinyorb.h; the parameter blocks
+static_assert(sizeof(OrbMatch) == sizeof(MatchRecord), "OrbMatch layout");
+static_assert(sizeof(OrbPairModel) == kVerifyModelWords * sizeof(uint32_t) && sizeof(OrbVerifyParams) == 32, "verify layouts");
+static_assert(sizeof(OrbGuideParams) == 32 && sizeof(OrbBandParams) == 32, "guided and band layouts");
+static_assert(sizeof(OrbTrack) == 16 && sizeof(OrbTrackFrame) == 32 && sizeof(OrbTrackParams) == 32, "track layouts");
+static_assert(sizeof(OrbPairPose) == kPoseWords * sizeof(uint32_t) && sizeof(OrbPoint) == sizeof(float4) && sizeof(OrbPoseParams) == 32, "pose layouts");
+static_assert(sizeof(OrbFramePose) == kTrajFrameWords * sizeof(uint32_t) && sizeof(OrbTrajectoryParams) == 32, "trajectory layouts");
+static_assert(sizeof(OrbFrameFix) == kLocFixWords * sizeof(uint32_t) && sizeof(OrbLocalizeParams) == 64, "localize layouts");
+static_assert(sizeof(OrbLandmark) == 32 && sizeof(OrbLandmarkRow) == kLmRowWords * sizeof(uint32_t) && sizeof(OrbLandmarkParams) == 32, "landmark layouts");
+static_assert(sizeof(OrbBridgePose) == kBrOutWords * sizeof(uint32_t) && sizeof(OrbBridgeParams) == 64 && kBrFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose),
+              "bridge layouts");
 
 // The last call of a stage
 struct Stage {
@@ -100,6 +154,27 @@ struct VerifierState {
     uint32_t* n = nullptr;              // [max_batch] candidates per pair
     unsigned long long* keys = nullptr; // [max_batch][kVerifyMaxHyp]
     uint32_t* model = nullptr;          // [max_batch] OrbPairModel
+    uint8_t* mask = nullptr;            // [max_batch][max_features] inlier bytes
+};
+
+// The buffers of a grid search (k_guide_bin and a search kernel), one set for the guided and one for the band call
+struct GridSearchState {
+    uint4* srec = nullptr;              // [max_batch][max_features] records in cell order (x0, y0, index, octave)
+    uint4* sdesc = nullptr;             // [max_batch][max_features][2] descriptors in cell order
+    uint32_t* cell = nullptr;           // [max_batch][kGuideMaxCells + 1] cell starts
+    MatchRecord* match = nullptr;       // [max_batch][max_features] results
+    float* d_model = nullptr;           // [max_batch][9] the caller's models (ORB_GUIDE_HOST, ORB_BAND_HOST)
+    float* h_model = nullptr;           // pinned staging of the same
+};
+
+// The buffers of LocArgs, one set for the localize and one for the bridge call
+struct PnpState {
+    uint32_t* fix = nullptr;            // [max_batch][words] the fix of every row
+    float4* reca = nullptr;             // [max_batch][max_features] candidates: the landmark in the earlier camera's frame
+    float4* recb = nullptr;             // [max_batch][max_features] candidates: the keypoint of the later frame and its ray
+    uint32_t* cand = nullptr;           // [max_batch][max_features] candidate of each slot of frame f - 1 (localize only)
+    uint32_t* n = nullptr;              // [max_batch] candidates per row
+    unsigned long long* keys = nullptr; // [max_batch][kVerifyMaxHyp]
     uint8_t* mask = nullptr;            // [max_batch][max_features] inlier bytes
 };
 
@@ -161,21 +236,9 @@ struct OrbProgram {
     int match_valu = -1;               // which matcher (0 fp4, 1 vector unit: TINYORB_MATCH_VALU=1, 2 int8: TINYORB_MATCH_I8=1); read once
     // orb_verify_consecutive (orb_kernels_verify.h) and orb_verify_epipolar (orb_kernels_epipolar.h): a set of buffers each
     VerifierState verify, epi;
-    // orb_match_guided (orb_kernels_guide.h)
-    uint4* d_gsrec = nullptr;             // [max_batch][max_features] records in cell order (x0, y0, index, octave)
-    uint4* d_gsdesc = nullptr;            // [max_batch][max_features][2] descriptors in cell order
-    uint32_t* d_gcell = nullptr;          // [max_batch][kGuideMaxCells + 1] cell starts
-    MatchRecord* d_gmatch = nullptr;      // [max_batch][max_features] results
-    float* d_gmodel = nullptr;            // [max_batch][9] the caller's models (ORB_GUIDE_HOST)
-    float* h_gmodel = nullptr;            // pinned staging of the same
+    // orb_match_guided (orb_kernels_guide.h) and orb_match_epipolar (orb_kernels_band.h): a set of buffers each, on the same grid
+    GridSearchState guide, band;
     int guide_cell = -1;                  // log2 of the grid's cell size (TINYORB_GUIDE_CELL); -1 until the first call
-    // orb_match_epipolar (orb_kernels_band.h): its own copies of the guided call's buffers, on the same grid (guide_cell)
-    uint4* d_bsrec = nullptr;
-    uint4* d_bsdesc = nullptr;
-    uint32_t* d_bcell = nullptr;
-    MatchRecord* d_bmatch = nullptr;      // [max_batch][max_features] results
-    float* d_bmodel = nullptr;            // [max_batch][9] the caller's fundamental matrices (ORB_BAND_HOST)
-    float* h_bmodel = nullptr;            // pinned staging of the same
     // orb_pose_consecutive (orb_kernels_pose.h)
     uint32_t* d_pose = nullptr;           // [max_batch][16] OrbPairPose
     float4* d_ppoints = nullptr;          // [max_batch][max_features] OrbPoint
@@ -185,26 +248,16 @@ struct OrbProgram {
     float4* d_jmap = nullptr;             // [max_batch][max_features] OrbPoint in the origin's frame and unit
     uint32_t* d_jratio = nullptr;         // [max_batch][max_features] the bits of a joint's ratios
     uint32_t* d_jjoint = nullptr;         // [max_batch][kTrajJointWords]
-    // orb_localize_consecutive (orb_kernels_localize.h)
-    uint32_t* d_lfix = nullptr;           // [max_batch][20] OrbFrameFix
-    float4* d_lreca = nullptr;            // [max_batch][max_features] candidates: the landmark in camera f's frame
-    float4* d_lrecb = nullptr;            // [max_batch][max_features] candidates: the keypoint of frame f + 1 and its ray
-    uint32_t* d_lcand = nullptr;          // [max_batch][max_features] candidate of each slot of frame f - 1
-    uint32_t* d_ln = nullptr;             // [max_batch] candidates per pair
-    unsigned long long* d_lkeys = nullptr; // [max_batch][kVerifyMaxHyp]
-    uint8_t* d_lmask = nullptr;           // [max_batch][max_features] inlier bytes
+    // orb_localize_consecutive (orb_kernels_localize.h): fix is [max_batch][20] OrbFrameFix, a row is a pair
+    PnpState loc;
     // orb_landmarks_consecutive (orb_kernels_landmark.h)
     float4* d_mland = nullptr;            // [max_batch][max_features][2] OrbLandmark
     uint32_t* d_mrow = nullptr;           // [max_batch][4] OrbLandmarkRow
     uint8_t* d_mpred = nullptr;           // [max_batch][max_features] a live slot of the pair before continues into this slot
-    // orb_bridge_consecutive (orb_kernels_bridge.h)
+    // orb_bridge_consecutive (orb_kernels_bridge.h): fix is [max_batch][kBrFixWords], the fix and join of every frame; a row is a
+    // LOST frame, a landmark in its anchor's frame with the keypoint slot; no cand
+    PnpState bridge;
     uint32_t* d_bout = nullptr;           // [max_batch][24] OrbBridgePose
-    uint32_t* d_bfix = nullptr;           // [max_batch][kBrFixWords] the fix and join of every frame
-    float4* d_breca = nullptr;            // [max_batch][max_features] candidates: the landmark in the anchor's frame, the keypoint slot
-    float4* d_brecb = nullptr;            // [max_batch][max_features] candidates: the keypoint of the LOST frame and its ray
-    uint32_t* d_bn = nullptr;             // [max_batch] candidates per frame
-    unsigned long long* d_bkeys = nullptr; // [max_batch][kVerifyMaxHyp]
-    uint8_t* d_bmask = nullptr;           // [max_batch][max_features] inlier bytes
     uint32_t* d_bratio = nullptr;         // [max_batch][max_features] the bits of a join's ratios
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
@@ -327,13 +380,25 @@ struct StageBuf {
     size_t bytes;
     bool pinned;   // host memory (hipHostMalloc); else device memory
 };
-const int kMaxStageBufs = 8;
-
-// The buffers of stage `which`, named here and nowhere else: its first call fills the slots, orb_program_destroy frees them.  Returns how many.
-int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
-    const size_t cap = p->cfg.max_features, B = p->max_batch;
+// A stage's buffers: a list of fixed capacity on the caller's stack, which says so when a stage names more than it holds
+struct StageBufs {
+    static constexpr int kMax = 10;
+    StageBuf b[kMax];
     int n = 0;
-    const auto add = [&](auto** slot, size_t bytes, bool pinned = false) { b[n++] = {(void**)slot, bytes, pinned}; };
+    bool overflow = false;
+    void add(void** slot, size_t bytes, bool pinned) {
+        if (n < kMax)
+            b[n++] = {slot, bytes, pinned};
+        else
+            overflow = true;
+    }
+};
+
+// The buffers of stage `which`, named here and nowhere else: its first call fills the slots, orb_program_destroy frees them.
+StageBufs stage_buffers(OrbProgram* p, int which) {
+    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    StageBufs l;
+    const auto add = [&](auto** slot, size_t bytes, bool pinned = false) { l.add((void**)slot, bytes, pinned); };
     switch (which) {
     case ST_MATCH:  // allocated by orb_match_consecutive itself (d_desc8 only for a matrix-core matcher, and softly); listed to be freed
         add(&p->d_matches, 0);
@@ -351,13 +416,16 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         break;
     }
     case ST_GUIDE:
-        add(&p->d_gsrec, B * cap * sizeof(uint4));
-        add(&p->d_gsdesc, B * cap * 2u * sizeof(uint4));
-        add(&p->d_gcell, B * (kGuideMaxCells + 1u) * sizeof(uint32_t));
-        add(&p->d_gmatch, B * cap * sizeof(MatchRecord));
-        add(&p->d_gmodel, B * 9u * sizeof(float));
-        add(&p->h_gmodel, B * 9u * sizeof(float), true);
+    case ST_BAND: {
+        GridSearchState& g = which == ST_GUIDE ? p->guide : p->band;
+        add(&g.srec, B * cap * sizeof(uint4));
+        add(&g.sdesc, B * cap * 2u * sizeof(uint4));
+        add(&g.cell, B * (kGuideMaxCells + 1u) * sizeof(uint32_t));
+        add(&g.match, B * cap * sizeof(MatchRecord));
+        add(&g.d_model, B * 9u * sizeof(float));
+        add(&g.h_model, B * 9u * sizeof(float), true);
         break;
+    }
     case ST_TRACK:
         add(&p->d_tkeys, B * cap * sizeof(uint32_t));
         add(&p->d_tprev, B * cap * sizeof(uint32_t));
@@ -367,14 +435,6 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         add(&p->d_tshared, B * B * sizeof(uint32_t));
         add(&p->d_tframe, B * sizeof(OrbTrackFrame));
         add(&p->d_track, B * cap * sizeof(OrbTrack));
-        break;
-    case ST_BAND:
-        add(&p->d_bsrec, B * cap * sizeof(uint4));
-        add(&p->d_bsdesc, B * cap * 2u * sizeof(uint4));
-        add(&p->d_bcell, B * (kGuideMaxCells + 1u) * sizeof(uint32_t));
-        add(&p->d_bmatch, B * cap * sizeof(MatchRecord));
-        add(&p->d_bmodel, B * 9u * sizeof(float));
-        add(&p->h_bmodel, B * 9u * sizeof(float), true);
         break;
     case ST_POSE:
         add(&p->d_pose, B * sizeof(OrbPairPose));
@@ -388,56 +448,52 @@ int stage_buffers(OrbProgram* p, int which, StageBuf* b) {
         add(&p->d_jjoint, B * kTrajJointWords * sizeof(uint32_t));
         break;
     case ST_LOCALIZE:
-        add(&p->d_lfix, B * sizeof(OrbFrameFix));
-        add(&p->d_lreca, B * cap * sizeof(float4));
-        add(&p->d_lrecb, B * cap * sizeof(float4));
-        add(&p->d_lcand, B * cap * sizeof(uint32_t));
-        add(&p->d_ln, B * sizeof(uint32_t));
-        add(&p->d_lkeys, B * kVerifyMaxHyp * sizeof(unsigned long long));
-        add(&p->d_lmask, B * cap);
+    case ST_BRIDGE: {
+        const bool br = which == ST_BRIDGE;
+        PnpState& l = br ? p->bridge : p->loc;
+        if (br) add(&p->d_bout, B * sizeof(OrbBridgePose));
+        add(&l.fix, B * (br ? kBrFixWords : kLocFixWords) * sizeof(uint32_t));
+        add(&l.reca, B * cap * sizeof(float4));
+        add(&l.recb, B * cap * sizeof(float4));
+        if (!br) add(&l.cand, B * cap * sizeof(uint32_t));  // k_br_gather keeps none, and k_loc_score reads none
+        add(&l.n, B * sizeof(uint32_t));
+        add(&l.keys, B * kVerifyMaxHyp * sizeof(unsigned long long));
+        add(&l.mask, B * cap);
+        if (br) add(&p->d_bratio, B * cap * sizeof(uint32_t));
         break;
+    }
     case ST_LANDMARK:
         add(&p->d_mland, B * cap * sizeof(OrbLandmark));
         add(&p->d_mrow, B * sizeof(OrbLandmarkRow));
         add(&p->d_mpred, B * cap);
         break;
-    case ST_BRIDGE:
-        add(&p->d_bout, B * sizeof(OrbBridgePose));
-        add(&p->d_bfix, B * kBrFixWords * sizeof(uint32_t));
-        add(&p->d_breca, B * cap * sizeof(float4));
-        add(&p->d_brecb, B * cap * sizeof(float4));
-        add(&p->d_bn, B * sizeof(uint32_t));
-        add(&p->d_bkeys, B * kVerifyMaxHyp * sizeof(unsigned long long));
-        add(&p->d_bmask, B * cap);
-        add(&p->d_bratio, B * cap * sizeof(uint32_t));
-        break;
     }
-    return n;
+    return l;
 }
 
 void free_stage_buffers(OrbProgram* p, int which) {
-    StageBuf b[kMaxStageBufs];
-    const int n = stage_buffers(p, which, b);
-    for (int i = 0; i < n; i++) {
-        if (*b[i].slot) (void)(b[i].pinned ? hipHostFree(*b[i].slot) : hipFree(*b[i].slot));
-        *b[i].slot = nullptr;
+    const StageBufs l = stage_buffers(p, which);
+    for (int i = 0; i < l.n; i++) {
+        if (*l.b[i].slot) (void)(l.b[i].pinned ? hipHostFree(*l.b[i].slot) : hipFree(*l.b[i].slot));
+        *l.b[i].slot = nullptr;
     }
 }
 
 // A stage's buffers on its first call, all or none: a failure frees the earlier ones and leaves every slot null, so the next call
 // allocates again.
 int alloc_all_or_none(OrbProgram* p, int which, const char* who) {
-    StageBuf b[kMaxStageBufs];
-    const int n = stage_buffers(p, which, b);
-    if (*b[0].slot) return ORB_OK;
-    for (int i = 0; i < n; i++) {
-        const hipError_t e = b[i].pinned ? hipHostMalloc(b[i].slot, b[i].bytes, hipHostMallocDefault) : hipMalloc(b[i].slot, b[i].bytes);
+    const StageBufs l = stage_buffers(p, which);
+    if (l.overflow) return fail(p, ORB_ESTATE, "%s: internal: the stage names more than %d buffers", who, StageBufs::kMax);
+    if (*l.b[0].slot) return ORB_OK;
+    for (int i = 0; i < l.n; i++) {
+        const StageBuf& b = l.b[i];
+        const hipError_t e = b.pinned ? hipHostMalloc(b.slot, b.bytes, hipHostMallocDefault) : hipMalloc(b.slot, b.bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            *b[i].slot = nullptr;
+            *b.slot = nullptr;
             free_stage_buffers(p, which);
-            if (b[i].pinned) return fail(p, ORB_EHIP, "%s: hipHostMalloc failed: %s", who, hipGetErrorString(e));
-            return fail(p, ORB_EHIP, "%s: hipMalloc of %zu bytes failed: %s", who, b[i].bytes, hipGetErrorString(e));
+            if (b.pinned) return fail(p, ORB_EHIP, "%s: hipHostMalloc failed: %s", who, hipGetErrorString(e));
+            return fail(p, ORB_EHIP, "%s: hipMalloc of %zu bytes failed: %s", who, b.bytes, hipGetErrorString(e));
         }
     }
     return ORB_OK;
@@ -446,19 +502,40 @@ int alloc_all_or_none(OrbProgram* p, int which, const char* who) {
 // "The last call of this stage is of the current batch and output set": what a later stage asks before it reads the stage's results.
 bool stage_fresh(const OrbProgram* p, const Stage& st) { return st.extent && st.seq == p->batch_seq && st.set == p->cur_set; }
 
+// The same of every stage in `need` (bits 1 << StageId), for a call of stage `which`: ORB_OK, or ORB_ESTATE with their names
+int stages_fresh(OrbProgram* p, int which, uint32_t need) {
+    uint32_t stale = 0;
+    for (int i = 0; i < ST_COUNT; i++)
+        if ((need >> i & 1u) && !stage_fresh(p, p->stage[i])) stale |= 1u << i;
+    if (!stale) return ORB_OK;
+    std::string names;
+    for (int i = 0; i < ST_COUNT; i++)
+        if (need >> i & 1u) names += std::string(names.empty() ? "orb_" : ", orb_") + kStages[i].name;
+    return fail(p, ORB_ESTATE, "%s: needs %s of the current batch and output set", kStages[which].name, names.c_str());
+}
+
 // Opens a call of stage `which`: its stream, its event on first use, and the waits behind the stage itself, the stages in `reads` (bits
-// 1 << StageId) and the readers of what it overwrites -- those that have run, and on another stream.
+// 1 << StageId, of the stage's row of kStages) and the readers of what it overwrites -- those that have run, and on another stream.
 int stage_begin(OrbProgram* p, int which, void* stream, uint32_t reads, hipStream_t* s_out) {
+    if (reads & ~kStages[which].reads)
+        return fail(p, ORB_ESTATE, "%s: internal: reads stages 0x%x, kStages says 0x%x", kStages[which].name, reads, kStages[which].reads);
     const hipStream_t s = call_stream(p, stream);
     Stage& self = p->stage[which];
     if (!self.done) HIP_TRY(p, hipEventCreateWithFlags(&self.done, hipEventDisableTiming));
-    const uint32_t behind = 1u << which | reads | kReadersOf[which];
+    const uint32_t behind = 1u << which | reads | kReaders.of[which];
     for (int i = 0; i < ST_COUNT; i++) {
         const Stage& o = p->stage[i];
         if ((behind >> i & 1u) && o.stream && o.stream != s) HIP_TRY(p, hipStreamWaitEvent(s, o.done, 0));
     }
     *s_out = s;
     return ORB_OK;
+}
+
+// The same with what comes before it in every stage but the matcher: the device, and the stage's buffers on its first call
+int stage_open(OrbProgram* p, int which, void* stream, uint32_t reads, hipStream_t* s_out) {
+    HIP_TRY(p, hipSetDevice(p->device));
+    if (int rc = alloc_all_or_none(p, which, kStages[which].name)) return rc;
+    return stage_begin(p, which, stream, reads, s_out);
 }
 
 // Closes it after the launches.  p->last_stream is the entry point's business: only the matcher and the verifiers move it.
@@ -2300,7 +2377,6 @@ int orb_match_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
     if (int rc = orb_batch_sync(p)) return rc;  // the batch's stream (the matcher moved it to its own), not the matcher's event
     const size_t cap = p->cfg.max_features;
     if (n > cap) n = cap;
-    static_assert(sizeof(OrbMatch) == sizeof(MatchRecord), "OrbMatch layout");
     HIP_TRY(p, hipMemcpy(dst, p->d_matches + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
@@ -2311,40 +2387,64 @@ namespace {
 
 // What orb_verify_consecutive and orb_verify_epipolar differ in
 struct VerifierKind {
-    const char* name;             // in messages
-    const char* read_name;
     uint32_t seed_salt;           // the draw stream's seed is lowbias32(seed ^ seed_salt)
     void (*score)(VerifyArgs);
     void (*refine)(VerifyArgs);
     StageId stage;
     bool profiled;                // launches under LaunchScope (KID_VERIFY_*)
 };
-const VerifierKind kHomography = {"verify_consecutive", "verify_read", 0u, k_verify_score, k_verify_refine, ST_VERIFY, true};
-const VerifierKind kEpipolar = {"verify_epipolar", "verify_epipolar_read", kEpiSeedSalt, k_epi_score, k_epi_refine, ST_EPI, false};
+const VerifierKind kHomography = {0u, k_verify_score, k_verify_refine, ST_VERIFY, true};
+const VerifierKind kEpipolar = {kEpiSeedSalt, k_epi_score, k_epi_refine, ST_EPI, false};
+
+// A RANSAC call's hypotheses, max_distance and ratio (the verifiers, localize, bridge): ORB_EINVAL out of range, else 0 becomes the default
+int ransac_params(OrbProgram* p, int which, uint32_t* hypotheses, uint32_t* max_distance, float* ratio) {
+    if (*hypotheses > kVerifyMaxHyp || *max_distance > 256u || !(std::isfinite(*ratio) && *ratio >= 0.0f))
+        return fail(p, ORB_EINVAL, "%s: hypotheses must be 0..%u, max_distance 0..256, ratio finite and >= 0", kStages[which].name, kVerifyMaxHyp);
+    if (!*hypotheses) *hypotheses = 512u;
+    if (!*max_distance) *max_distance = 64u;
+    if (*ratio == 0.0f) *ratio = 0.8f;
+    return ORB_OK;
+}
+
+// The intrinsics of a pose, localize, landmarks or bridge call
+int check_intrinsics(OrbProgram* p, int which, float fx, float fy, float cx, float cy) {
+    if (!(std::isfinite(fx) && fx > 0.0f) || !(std::isfinite(fy) && fy > 0.0f) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail(p, ORB_EINVAL, "%s: fx and fy must be finite and > 0, cx and cy finite", kStages[which].name);
+    return ORB_OK;
+}
+
+// A read call of stage `which`: the head record of row `index` (head NULL: not asked for) and the first n elements of that row of
+// max_features.  Waits for the stage's event on the host.
+int read_stage(OrbProgram* p, int which, uint32_t index, void* head, const void* d_head, size_t head_bytes, void* rows, const void* d_rows,
+               size_t elem_bytes, size_t n) {
+    const Stage& last = p->stage[which];
+    const StageInfo& k = kStages[which];
+    if (!last.extent) return fail(p, ORB_ESTATE, "%s before %s", k.read_name, k.name);
+    if (index >= last.extent || (!rows && n))
+        return fail(p, ORB_EINVAL, "%s: index %u of %u, or the destination of %zu elements is NULL", k.read_name, index, last.extent, n);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    const size_t cap = p->cfg.max_features;
+    if (n > cap) n = cap;
+    if (head) HIP_TRY(p, hipMemcpy(head, (const char*)d_head + (size_t)index * head_bytes, head_bytes, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(p, hipMemcpy(rows, (const char*)d_rows + (size_t)index * cap * elem_bytes, n * elem_bytes, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
 
 int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
+    const char* const name = kStages[kind.stage].name;
     OrbVerifyParams v{};
     if (params) v = *params;
-    if (v.reserved[0] || v.reserved[1] || v.reserved[2]) return fail(p, ORB_EINVAL, "%s: reserved words must be 0", kind.name);
-    if (v.hypotheses > kVerifyMaxHyp || v.max_distance > 256u)
-        return fail(p, ORB_EINVAL, "%s: hypotheses must be 0..%u and max_distance 0..256", kind.name, kVerifyMaxHyp);
-    if (!(std::isfinite(v.ratio) && v.ratio >= 0.0f) || !(std::isfinite(v.inlier_px) && v.inlier_px >= 0.0f))
-        return fail(p, ORB_EINVAL, "%s: ratio and inlier_px must be finite and >= 0", kind.name);
+    if (v.reserved[0] || v.reserved[1] || v.reserved[2]) return fail(p, ORB_EINVAL, "%s: reserved words must be 0", name);
+    if (int rc = ransac_params(p, kind.stage, &v.hypotheses, &v.max_distance, &v.ratio)) return rc;
+    if (!(std::isfinite(v.inlier_px) && v.inlier_px >= 0.0f)) return fail(p, ORB_EINVAL, "%s: inlier_px must be finite and >= 0", name);
+    if (int rc = stages_fresh(p, kind.stage, kStages[kind.stage].reads)) return rc;
     const Stage& m = p->stage[ST_MATCH];
-    if (!stage_fresh(p, m))  // said in two ways: the batch first, then the output set
-        return fail(p, ORB_ESTATE, !m.extent || m.seq != p->batch_seq ? "%s: no orb_match_consecutive since the last batch"
-                                                                      : "%s: the output set changed since orb_match_consecutive", kind.name);
-    if (n_frames < 2u || n_frames > m.extent)
-        return fail(p, ORB_EINVAL, "%s: need 2..%u frames (the matched ones)", kind.name, m.extent);
-    if (!v.hypotheses) v.hypotheses = 512u;
-    if (!v.max_distance) v.max_distance = 64u;
-    if (v.ratio == 0.0f) v.ratio = 0.8f;
+    if (n_frames < 2u || n_frames > m.extent) return fail(p, ORB_EINVAL, "%s: need 2..%u frames (the matched ones)", name, m.extent);
     if (v.inlier_px == 0.0f) v.inlier_px = 3.0f;
-    HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
-    if (int rc = alloc_all_or_none(p, kind.stage, kind.name)) return rc;
     hipStream_t s;
-    if (int rc = stage_begin(p, kind.stage, stream, 1u << ST_MATCH, &s)) return rc;  // the matches come from the matcher's stream
+    if (int rc = stage_open(p, kind.stage, stream, kStages[kind.stage].reads, &s)) return rc;  // the matches come from the matcher's stream
     // GV-2: coordinates centred on the level-0 image and scaled by 2 / max(W, H)
     const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
     VerifyArgs a{};
@@ -2384,20 +2484,58 @@ int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uin
     return ORB_OK;
 }
 
-int read_verifier(OrbProgram* p, const VerifierKind& kind, const VerifierState& st, uint32_t pair, OrbPairModel* model, uint8_t* inlier,
-                     size_t n) {
-    const Stage& last = p->stage[kind.stage];
-    if (!last.extent) return fail(p, ORB_ESTATE, "%s before %s", kind.read_name, kind.name);
-    if (pair >= last.extent || (!inlier && n))
-        return fail(p, ORB_EINVAL, "%s: pair %u of %u, or inlier is NULL", kind.read_name, pair, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    static_assert(sizeof(OrbPairModel) == kVerifyModelWords * sizeof(uint32_t) && sizeof(OrbVerifyParams) == 32, "verify layouts");
-    if (model) HIP_TRY(p, hipMemcpy(model, st.model + (size_t)pair * kVerifyModelWords, sizeof(OrbPairModel), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(p, hipMemcpy(inlier, st.mask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
+// k_guide_bin's part of GuideArgs, for the guided and the band call: the frame's records into the cells of the program's grid
+GuideArgs guide_bin_args(const OrbProgram* p, const GridSearchState& g) {
+    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    GuideArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.desc = p->d_desc;
+    a.cap = p->cfg.max_features;
+    a.shift = (uint32_t)p->guide_cell;
+    a.gw = (W + (1u << a.shift) - 1u) >> a.shift;
+    a.gh = (H + (1u << a.shift) - 1u) >> a.shift;
+    a.srec = g.srec;
+    a.sdesc = g.sdesc;
+    a.cell_start = g.cell;
+    return a;
+}
+
+// The caller's models, 9 floats a pair, through the stage's pinned staging buffer, once the previous call's copy out of it is done
+int stage_host_models(OrbProgram* p, int which, const GridSearchState& g, const float* models_host, uint32_t pairs, hipStream_t s) {
+    if (p->stage[which].stream) HIP_TRY(p, hipEventSynchronize(p->stage[which].done));
+    memcpy(g.h_model, models_host, (size_t)pairs * 9u * sizeof(float));
+    HIP_TRY(p, hipMemcpyAsync(g.d_model, g.h_model, (size_t)pairs * 9u * sizeof(float), hipMemcpyHostToDevice, s));
     return ORB_OK;
+}
+
+// LocArgs on a set of buffers, from the fields OrbLocalizeParams and OrbBridgeParams share (defaults applied)
+template <class Params>
+LocArgs loc_args(const OrbProgram* p, const PnpState& l, const Params& g, uint32_t seed_salt) {
+    LocArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.matches = p->d_matches;
+    a.cap = p->cfg.max_features;
+    a.poses = p->d_pose;
+    a.points = p->d_ppoints;
+    a.hyps = g.hypotheses;
+    a.max_distance = g.max_distance;
+    a.ratio = g.ratio;
+    a.fx = g.fx;
+    a.fy = g.fy;
+    a.cx = g.cx;
+    a.cy = g.cy;
+    a.r2 = g.max_reproj_px * g.max_reproj_px;
+    a.seed_mix = lowbias32(g.seed ^ seed_salt);
+    a.reca = l.reca;
+    a.recb = l.recb;
+    a.cand_of = l.cand;  // bridge: NULL, k_loc_score reads none
+    a.n_cand = l.n;
+    a.keys = l.keys;
+    a.fix = l.fix;
+    a.mask = l.mask;
+    return a;
 }
 
 // The grid of the guided and the band search, fixed by the program's first such call: the smallest cell (8, or TINYORB_GUIDE_CELL: a
@@ -2423,7 +2561,7 @@ int orb_verify_consecutive(OrbProgram* p, uint32_t n_frames, const OrbVerifyPara
 }
 
 int orb_verify_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
-    return p ? read_verifier(p, kHomography, p->verify, pair, model, inlier, n) : ORB_EINVAL;
+    return p ? read_stage(p, ST_VERIFY, pair, model, p->verify.model, sizeof(OrbPairModel), inlier, p->verify.mask, 1, n) : ORB_EINVAL;
 }
 
 int orb_verify_epipolar(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
@@ -2431,7 +2569,7 @@ int orb_verify_epipolar(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams*
 }
 
 int orb_verify_epipolar_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
-    return p ? read_verifier(p, kEpipolar, p->epi, pair, model, inlier, n) : ORB_EINVAL;
+    return p ? read_stage(p, ST_EPI, pair, model, p->epi.model, sizeof(OrbPairModel), inlier, p->epi.mask, 1, n) : ORB_EINVAL;
 }
 
 int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {
@@ -2448,45 +2586,28 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
     if ((g.source == ORB_GUIDE_HOST) != (models_host != nullptr))
         return fail(p, ORB_EINVAL, "match_guided: models_host is required with ORB_GUIDE_HOST and only then");
     if (g.source == ORB_GUIDE_VERIFIED) {
-        const Stage& v = p->stage[ST_VERIFY];
-        if (!stage_fresh(p, v)) return fail(p, ORB_ESTATE, "match_guided: no orb_verify_consecutive of the current batch and output set");
-        if (n_frames - 1u > v.extent)
-            return fail(p, ORB_EINVAL, "match_guided: %u pairs, the last verification has %u", n_frames - 1u, v.extent);
+        if (int rc = stages_fresh(p, ST_GUIDE, kStages[ST_GUIDE].reads)) return rc;
+        const uint32_t verified = p->stage[ST_VERIFY].extent;
+        if (n_frames - 1u > verified) return fail(p, ORB_EINVAL, "match_guided: %u pairs, the last verification has %u", n_frames - 1u, verified);
     }
     if (g.radius_px == 0.0f) g.radius_px = 16.0f;
-    HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
-    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
     guide_grid(p);
-    if (int rc = alloc_all_or_none(p, ST_GUIDE, "match_guided")) return rc;
     hipStream_t s;
     // the models come from the last verification (waited for whatever the source is)
-    if (int rc = stage_begin(p, ST_GUIDE, stream, 1u << ST_VERIFY, &s)) return rc;
+    if (int rc = stage_open(p, ST_GUIDE, stream, kStages[ST_GUIDE].reads, &s)) return rc;
     const uint32_t pairs = n_frames - 1u;
-    if (g.source == ORB_GUIDE_HOST) {  // through the pinned staging buffer, once the previous call's copy out of it is done
-        if (p->stage[ST_GUIDE].stream) HIP_TRY(p, hipEventSynchronize(p->stage[ST_GUIDE].done));
-        memcpy(p->h_gmodel, models_host, (size_t)pairs * 9u * sizeof(float));
-        HIP_TRY(p, hipMemcpyAsync(p->d_gmodel, p->h_gmodel, (size_t)pairs * 9u * sizeof(float), hipMemcpyHostToDevice, s));
-    }
-    GuideArgs a{};
-    a.counts = p->d_counts;
-    a.corners = p->d_corners;
-    a.desc = p->d_desc;
-    a.cap = (uint32_t)cap;
-    a.shift = (uint32_t)p->guide_cell;
-    a.gw = (W + (1u << a.shift) - 1u) >> a.shift;
-    a.gh = (H + (1u << a.shift) - 1u) >> a.shift;
-    a.srec = p->d_gsrec;
-    a.sdesc = p->d_gsdesc;
-    a.cell_start = p->d_gcell;
+    if (g.source == ORB_GUIDE_HOST)
+        if (int rc = stage_host_models(p, ST_GUIDE, p->guide, models_host, pairs, s)) return rc;
+    GuideArgs a = guide_bin_args(p, p->guide);
     a.pairs = pairs;
     a.source = g.source;
     a.vmodel = p->verify.model;
-    a.hmodel = p->d_gmodel;
+    a.hmodel = p->guide.d_model;
     a.radius = g.radius_px;
     a.octave_window = g.octave_window;
     a.scale_radius = (g.flags & ORB_GUIDE_SCALE_RADIUS) ? 1u : 0u;
-    a.out = p->d_gmatch;
+    a.out = p->guide.match;
     hipLaunchKernelGGL(k_guide_bin, dim3(n_frames), dim3(kGuideBinThreads), 0, s, a);
     hipLaunchKernelGGL(k_guide_search, dim3(pairs * (unsigned)((cap + kGuideSearchThreads - 1u) / kGuideSearchThreads)),
                        dim3(kGuideSearchThreads), 0, s, a);
@@ -2494,17 +2615,7 @@ int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* par
 }
 
 int orb_match_guided_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
-    if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_GUIDE];
-    if (!last.extent) return fail(p, ORB_ESTATE, "match_guided_read before match_guided");
-    if (frame >= last.extent || (!dst && n)) return fail(p, ORB_EINVAL, "match_guided_read: frame %u of %u, or dst is NULL", frame, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    static_assert(sizeof(OrbGuideParams) == 32, "OrbGuideParams layout");
-    if (n) HIP_TRY(p, hipMemcpy(dst, p->d_gmatch + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_stage(p, ST_GUIDE, frame, nullptr, nullptr, 0, dst, p->guide.match, sizeof(OrbMatch), n) : ORB_EINVAL;
 }
 
 int orb_match_epipolar(OrbProgram* p, uint32_t n_frames, const OrbBandParams* params, const float* models_host, void* stream) {
@@ -2522,57 +2633,41 @@ int orb_match_epipolar(OrbProgram* p, uint32_t n_frames, const OrbBandParams* pa
     if ((g.source == ORB_BAND_HOST) != (models_host != nullptr))
         return fail(p, ORB_EINVAL, "match_epipolar: models_host is required with ORB_BAND_HOST and only then");
     if (g.source == ORB_BAND_VERIFIED) {
-        const Stage& v = p->stage[ST_EPI];
-        if (!stage_fresh(p, v)) return fail(p, ORB_ESTATE, "match_epipolar: no orb_verify_epipolar of the current batch and output set");
-        if (n_frames - 1u > v.extent)
-            return fail(p, ORB_EINVAL, "match_epipolar: %u pairs, the last epipolar verification has %u", n_frames - 1u, v.extent);
+        if (int rc = stages_fresh(p, ST_BAND, kStages[ST_BAND].reads)) return rc;
+        const uint32_t verified = p->stage[ST_EPI].extent;
+        if (n_frames - 1u > verified)
+            return fail(p, ORB_EINVAL, "match_epipolar: %u pairs, the last epipolar verification has %u", n_frames - 1u, verified);
     }
     if (g.band_px == 0.0f) g.band_px = 2.0f;
-    HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
-    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
     guide_grid(p);
-    if (int rc = alloc_all_or_none(p, ST_BAND, "match_epipolar")) return rc;
     hipStream_t s;
     // the models come from the last epipolar verification (waited for whatever the source is, as the guided call does)
-    if (int rc = stage_begin(p, ST_BAND, stream, 1u << ST_EPI, &s)) return rc;
+    if (int rc = stage_open(p, ST_BAND, stream, kStages[ST_BAND].reads, &s)) return rc;
     const uint32_t pairs = n_frames - 1u;
-    if (g.source == ORB_BAND_HOST) {  // through the pinned staging buffer, once the previous call's copy out of it is done
-        if (p->stage[ST_BAND].stream) HIP_TRY(p, hipEventSynchronize(p->stage[ST_BAND].done));
-        memcpy(p->h_bmodel, models_host, (size_t)pairs * 9u * sizeof(float));
-        HIP_TRY(p, hipMemcpyAsync(p->d_bmodel, p->h_bmodel, (size_t)pairs * 9u * sizeof(float), hipMemcpyHostToDevice, s));
-    }
-    GuideArgs bin{};  // k_guide_bin as it is, on this stage's buffers
-    bin.counts = p->d_counts;
-    bin.corners = p->d_corners;
-    bin.desc = p->d_desc;
-    bin.cap = (uint32_t)cap;
-    bin.shift = (uint32_t)p->guide_cell;
-    bin.gw = (W + (1u << bin.shift) - 1u) >> bin.shift;
-    bin.gh = (H + (1u << bin.shift) - 1u) >> bin.shift;
-    bin.srec = p->d_bsrec;
-    bin.sdesc = p->d_bsdesc;
-    bin.cell_start = p->d_bcell;
+    if (g.source == ORB_BAND_HOST)
+        if (int rc = stage_host_models(p, ST_BAND, p->band, models_host, pairs, s)) return rc;
+    const GuideArgs bin = guide_bin_args(p, p->band);  // k_guide_bin as it is, on this stage's buffers
     BandArgs a{};
-    a.counts = p->d_counts;
-    a.cap = (uint32_t)cap;
+    a.counts = bin.counts;
+    a.cap = bin.cap;
     a.gw = bin.gw;
     a.gh = bin.gh;
     a.shift = bin.shift;
-    a.fw = (float)W;
-    a.fh = (float)H;
-    a.srec = p->d_bsrec;
-    a.sdesc = p->d_bsdesc;
-    a.cell_start = p->d_bcell;
+    a.fw = (float)p->pyr.w[0];
+    a.fh = (float)p->pyr.h[0];
+    a.srec = bin.srec;
+    a.sdesc = bin.sdesc;
+    a.cell_start = bin.cell_start;
     a.pairs = pairs;
     a.source = g.source;
     a.vmodel = p->epi.model;
-    a.hmodel = p->d_bmodel;
+    a.hmodel = p->band.d_model;
     a.band = g.band_px;
     a.radius = g.radius_px;
     a.octave_window = g.octave_window;
     a.scale = (g.flags & ORB_BAND_SCALE) ? 1u : 0u;
-    a.out = p->d_bmatch;
+    a.out = p->band.match;
     hipLaunchKernelGGL(k_guide_bin, dim3(n_frames), dim3(kGuideBinThreads), 0, s, bin);
     hipLaunchKernelGGL(k_band_search, dim3(pairs * (unsigned)((cap + kGuideSearchThreads - 1u) / kGuideSearchThreads)),
                        dim3(kGuideSearchThreads), 0, s, a);
@@ -2580,41 +2675,27 @@ int orb_match_epipolar(OrbProgram* p, uint32_t n_frames, const OrbBandParams* pa
 }
 
 int orb_match_epipolar_read(OrbProgram* p, uint32_t frame, OrbMatch* dst, size_t n) {
-    if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_BAND];
-    if (!last.extent) return fail(p, ORB_ESTATE, "match_epipolar_read before match_epipolar");
-    if (frame >= last.extent || (!dst && n)) return fail(p, ORB_EINVAL, "match_epipolar_read: frame %u of %u, or dst is NULL", frame, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    static_assert(sizeof(OrbBandParams) == 32, "OrbBandParams layout");
-    if (n) HIP_TRY(p, hipMemcpy(dst, p->d_bmatch + (size_t)frame * cap, n * sizeof(OrbMatch), hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_stage(p, ST_BAND, frame, nullptr, nullptr, 0, dst, p->band.match, sizeof(OrbMatch), n) : ORB_EINVAL;
 }
 
 int orb_pose_consecutive(OrbProgram* p, uint32_t n_frames, const OrbPoseParams* params, void* stream) {
     if (!p || !params) return p ? fail(p, ORB_EINVAL, "pose_consecutive: params is NULL") : ORB_EINVAL;
     OrbPoseParams g = *params;
-    if (!(std::isfinite(g.fx) && g.fx > 0.0f) || !(std::isfinite(g.fy) && g.fy > 0.0f) || !std::isfinite(g.cx) || !std::isfinite(g.cy))
-        return fail(p, ORB_EINVAL, "pose_consecutive: fx and fy must be finite and > 0, cx and cy finite");
+    if (int rc = check_intrinsics(p, ST_POSE, g.fx, g.fy, g.cx, g.cy)) return rc;
     if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f) || !(g.max_cos_parallax >= 0.0f && g.max_cos_parallax <= 1.0f) ||
         g.ambiguity_permille > 1000u)
         return fail(p, ORB_EINVAL, "pose_consecutive: max_reproj_px must be finite and >= 0, max_cos_parallax in (0, 1] (0: the default), ambiguity_permille 0..1000");
-    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_EPI];
-    if (!stage_fresh(p, m) || !stage_fresh(p, v))
-        return fail(p, ORB_ESTATE, "pose_consecutive: no orb_match_consecutive and orb_verify_epipolar of the current batch and output set");
-    if (n_frames < 2u || n_frames - 1u > v.extent)
-        return fail(p, ORB_EINVAL, "pose_consecutive: need 2..%u frames (the last epipolar verification's pairs + 1)", v.extent + 1u);
+    if (int rc = stages_fresh(p, ST_POSE, kStages[ST_POSE].reads)) return rc;
+    const uint32_t verified = p->stage[ST_EPI].extent;
+    if (n_frames < 2u || n_frames - 1u > verified)
+        return fail(p, ORB_EINVAL, "pose_consecutive: need 2..%u frames (the last epipolar verification's pairs + 1)", verified + 1u);
     if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
     if (g.max_cos_parallax == 0.0f) g.max_cos_parallax = 0.99998f;
     if (!g.min_good) g.min_good = 8u;
     if (!g.ambiguity_permille) g.ambiguity_permille = 700u;
-    HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
-    if (int rc = alloc_all_or_none(p, ST_POSE, "pose_consecutive")) return rc;
     hipStream_t s;
-    if (int rc = stage_begin(p, ST_POSE, stream, 1u << ST_MATCH | 1u << ST_EPI, &s)) return rc;
+    if (int rc = stage_open(p, ST_POSE, stream, kStages[ST_POSE].reads, &s)) return rc;
     const uint32_t pairs = n_frames - 1u;
     PoseArgs a{};
     a.counts = p->d_counts;
@@ -2634,8 +2715,6 @@ int orb_pose_consecutive(OrbProgram* p, uint32_t n_frames, const OrbPoseParams* 
     a.counters = p->d_pcount;
     a.poses = p->d_pose;
     a.points = p->d_ppoints;
-    static_assert(sizeof(OrbPairPose) == kPoseWords * sizeof(uint32_t) && sizeof(OrbPoint) == sizeof(float4) && sizeof(OrbPoseParams) == 32,
-                  "pose layouts");
     const dim3 grid(pairs, (unsigned)((cap + kPoseThreads - 1u) / kPoseThreads));
     HIP_TRY(p, hipMemsetAsync(p->d_pcount, 0, (size_t)pairs * kPoseCounters * sizeof(uint32_t), s));
     hipLaunchKernelGGL(k_pose_count, grid, dim3(kPoseThreads), 0, s, a);
@@ -2644,17 +2723,7 @@ int orb_pose_consecutive(OrbProgram* p, uint32_t n_frames, const OrbPoseParams* 
 }
 
 int orb_pose_read(OrbProgram* p, uint32_t pair, OrbPairPose* pose, OrbPoint* points, size_t n) {
-    if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_POSE];
-    if (!last.extent) return fail(p, ORB_ESTATE, "pose_read before pose_consecutive");
-    if (pair >= last.extent || (!points && n)) return fail(p, ORB_EINVAL, "pose_read: pair %u of %u, or points is NULL", pair, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    if (pose) HIP_TRY(p, hipMemcpy(pose, p->d_pose + (size_t)pair * kPoseWords, sizeof(OrbPairPose), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(p, hipMemcpy(points, p->d_ppoints + (size_t)pair * cap, n * sizeof(OrbPoint), hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_stage(p, ST_POSE, pair, pose, p->d_pose, sizeof(OrbPairPose), points, p->d_ppoints, sizeof(OrbPoint), n) : ORB_EINVAL;
 }
 
 int orb_trajectory_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrajectoryParams* params, void* stream) {
@@ -2667,18 +2736,14 @@ int orb_trajectory_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrajec
         return fail(p, ORB_EINVAL, "trajectory_consecutive: scale_tolerance must be finite and >= 0, consistent_permille 0..1000");
     const size_t cap = p->cfg.max_features;
     if (cap > (1u << 23)) return fail(p, ORB_EINVAL, "trajectory_consecutive: max_features above 2^23");
-    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_POSE];
-    if (!stage_fresh(p, m) || !stage_fresh(p, v))
-        return fail(p, ORB_ESTATE, "trajectory_consecutive: no orb_match_consecutive and orb_pose_consecutive of the current batch and output set");
-    const uint32_t most = std::min(4096u, v.extent + 1u);
+    if (int rc = stages_fresh(p, ST_TRAJ, kStages[ST_TRAJ].reads)) return rc;
+    const uint32_t most = std::min(4096u, p->stage[ST_POSE].extent + 1u);
     if (n_frames < 2u || n_frames > most) return fail(p, ORB_EINVAL, "trajectory_consecutive: need 2..%u frames (the last pose call's pairs + 1, at most 4096)", most);
     if (!g.min_shared) g.min_shared = 8u;
     if (g.scale_tolerance == 0.0f) g.scale_tolerance = 0.1f;
     if (!g.consistent_permille) g.consistent_permille = 500u;
-    HIP_TRY(p, hipSetDevice(p->device));
-    if (int rc = alloc_all_or_none(p, ST_TRAJ, "trajectory_consecutive")) return rc;
     hipStream_t s;
-    if (int rc = stage_begin(p, ST_TRAJ, stream, 1u << ST_MATCH | 1u << ST_POSE, &s)) return rc;
+    if (int rc = stage_open(p, ST_TRAJ, stream, kStages[ST_TRAJ].reads, &s)) return rc;
     TrajArgs a{};
     a.counts = p->d_counts;
     a.matches = p->d_matches;
@@ -2694,7 +2759,6 @@ int orb_trajectory_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrajec
     a.joints = p->d_jjoint;
     a.frames = p->d_jframe;
     a.map = p->d_jmap;
-    static_assert(sizeof(OrbFramePose) == kTrajFrameWords * sizeof(uint32_t) && sizeof(OrbTrajectoryParams) == 32, "trajectory layouts");
     if (n_frames > 2u) hipLaunchKernelGGL(k_traj_joint, dim3(n_frames - 2u), dim3(kTrajThreads), 0, s, a);
     hipLaunchKernelGGL(k_traj_chain, dim3(1), dim3(64), 0, s, a);
     hipLaunchKernelGGL(k_traj_map, dim3(n_frames - 1u, (unsigned)((cap + kTrajThreads - 1u) / kTrajThreads)), dim3(kTrajThreads), 0, s, a);
@@ -2703,17 +2767,7 @@ int orb_trajectory_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrajec
 }
 
 int orb_trajectory_read(OrbProgram* p, uint32_t frame, OrbFramePose* pose, OrbPoint* points, size_t n) {
-    if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_TRAJ];
-    if (!last.extent) return fail(p, ORB_ESTATE, "trajectory_read before trajectory_consecutive");
-    if (frame >= last.extent || (!points && n)) return fail(p, ORB_EINVAL, "trajectory_read: frame %u of %u, or points is NULL", frame, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    if (pose) HIP_TRY(p, hipMemcpy(pose, p->d_jframe + (size_t)frame * kTrajFrameWords, sizeof(OrbFramePose), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(p, hipMemcpy(points, p->d_jmap + (size_t)frame * cap, n * sizeof(OrbPoint), hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_stage(p, ST_TRAJ, frame, pose, p->d_jframe, sizeof(OrbFramePose), points, p->d_jmap, sizeof(OrbPoint), n) : ORB_EINVAL;
 }
 
 int orb_localize_consecutive(OrbProgram* p, uint32_t n_frames, const OrbLocalizeParams* params, void* stream) {
@@ -2721,52 +2775,19 @@ int orb_localize_consecutive(OrbProgram* p, uint32_t n_frames, const OrbLocalize
     OrbLocalizeParams g = *params;
     for (uint32_t w : g.reserved)
         if (w) return fail(p, ORB_EINVAL, "localize_consecutive: reserved words must be 0");
-    if (!(std::isfinite(g.fx) && g.fx > 0.0f) || !(std::isfinite(g.fy) && g.fy > 0.0f) || !std::isfinite(g.cx) || !std::isfinite(g.cy))
-        return fail(p, ORB_EINVAL, "localize_consecutive: fx and fy must be finite and > 0, cx and cy finite");
-    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f) || !(std::isfinite(g.ratio) && g.ratio >= 0.0f))
-        return fail(p, ORB_EINVAL, "localize_consecutive: max_reproj_px and ratio must be finite and >= 0");
-    if (g.hypotheses > kVerifyMaxHyp || g.max_distance > 256u)
-        return fail(p, ORB_EINVAL, "localize_consecutive: hypotheses must be 0..%u and max_distance 0..256", kVerifyMaxHyp);
-    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_POSE];
-    if (!stage_fresh(p, m) || !stage_fresh(p, v))
-        return fail(p, ORB_ESTATE, "localize_consecutive: no orb_match_consecutive and orb_pose_consecutive of the current batch and output set");
-    const uint32_t most = std::min(m.extent, v.extent + 1u);  // pair f reads the matches of frame f and the pose of pair f - 1
+    if (int rc = check_intrinsics(p, ST_LOCALIZE, g.fx, g.fy, g.cx, g.cy)) return rc;
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f)) return fail(p, ORB_EINVAL, "localize_consecutive: max_reproj_px must be finite and >= 0");
+    if (int rc = ransac_params(p, ST_LOCALIZE, &g.hypotheses, &g.max_distance, &g.ratio)) return rc;
+    if (int rc = stages_fresh(p, ST_LOCALIZE, kStages[ST_LOCALIZE].reads)) return rc;
+    // pair f reads the matches of frame f and the pose of pair f - 1
+    const uint32_t most = std::min(p->stage[ST_MATCH].extent, p->stage[ST_POSE].extent + 1u);
     if (n_frames < 3u || n_frames > most)
         return fail(p, ORB_EINVAL, "localize_consecutive: need 3..%u frames (the last pose call's pairs + 1)", most);
     if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
-    if (!g.hypotheses) g.hypotheses = 512u;
-    if (!g.max_distance) g.max_distance = 64u;
-    if (g.ratio == 0.0f) g.ratio = 0.8f;
-    HIP_TRY(p, hipSetDevice(p->device));
-    const size_t cap = p->cfg.max_features;
-    if (int rc = alloc_all_or_none(p, ST_LOCALIZE, "localize_consecutive")) return rc;
     hipStream_t s;
-    if (int rc = stage_begin(p, ST_LOCALIZE, stream, 1u << ST_MATCH | 1u << ST_POSE, &s)) return rc;
+    if (int rc = stage_open(p, ST_LOCALIZE, stream, kStages[ST_LOCALIZE].reads, &s)) return rc;
     const uint32_t pairs = n_frames - 1u;
-    LocArgs a{};
-    a.counts = p->d_counts;
-    a.corners = p->d_corners;
-    a.matches = p->d_matches;
-    a.cap = (uint32_t)cap;
-    a.poses = p->d_pose;
-    a.points = p->d_ppoints;
-    a.hyps = g.hypotheses;
-    a.max_distance = g.max_distance;
-    a.ratio = g.ratio;
-    a.fx = g.fx;
-    a.fy = g.fy;
-    a.cx = g.cx;
-    a.cy = g.cy;
-    a.r2 = g.max_reproj_px * g.max_reproj_px;
-    a.seed_mix = lowbias32(g.seed ^ kLocSeedSalt);
-    a.reca = p->d_lreca;
-    a.recb = p->d_lrecb;
-    a.cand_of = p->d_lcand;
-    a.n_cand = p->d_ln;
-    a.keys = p->d_lkeys;
-    a.fix = p->d_lfix;
-    a.mask = p->d_lmask;
-    static_assert(sizeof(OrbFrameFix) == kLocFixWords * sizeof(uint32_t) && sizeof(OrbLocalizeParams) == 64, "localize layouts");
+    const LocArgs a = loc_args(p, p->loc, g, kLocSeedSalt);
     hipLaunchKernelGGL(k_loc_gather, dim3(pairs), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_loc_score, dim3(pairs, (g.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_loc_refine, dim3(pairs), dim3(256), 0, s, a);
@@ -2774,38 +2795,24 @@ int orb_localize_consecutive(OrbProgram* p, uint32_t n_frames, const OrbLocalize
 }
 
 int orb_localize_read(OrbProgram* p, uint32_t pair, OrbFrameFix* fix, uint8_t* inliers, size_t n) {
-    if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_LOCALIZE];
-    if (!last.extent) return fail(p, ORB_ESTATE, "localize_read before localize_consecutive");
-    if (pair >= last.extent || (!inliers && n)) return fail(p, ORB_EINVAL, "localize_read: pair %u of %u, or inliers is NULL", pair, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    if (fix) HIP_TRY(p, hipMemcpy(fix, p->d_lfix + (size_t)pair * kLocFixWords, sizeof(OrbFrameFix), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(p, hipMemcpy(inliers, p->d_lmask + (size_t)pair * cap, n, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_stage(p, ST_LOCALIZE, pair, fix, p->loc.fix, sizeof(OrbFrameFix), inliers, p->loc.mask, 1, n) : ORB_EINVAL;
 }
 
 int orb_landmarks_consecutive(OrbProgram* p, uint32_t n_frames, const OrbLandmarkParams* params, void* stream) {
     if (!p || !params) return p ? fail(p, ORB_EINVAL, "landmarks_consecutive: params is NULL") : ORB_EINVAL;
     OrbLandmarkParams g = *params;
     if (g.reserved[0] | g.reserved[1]) return fail(p, ORB_EINVAL, "landmarks_consecutive: reserved words must be 0");
-    if (!(std::isfinite(g.fx) && g.fx > 0.0f) || !(std::isfinite(g.fy) && g.fy > 0.0f) || !std::isfinite(g.cx) || !std::isfinite(g.cy))
-        return fail(p, ORB_EINVAL, "landmarks_consecutive: fx and fy must be finite and > 0, cx and cy finite");
+    if (int rc = check_intrinsics(p, ST_LANDMARK, g.fx, g.fy, g.cx, g.cy)) return rc;
     if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f)) return fail(p, ORB_EINVAL, "landmarks_consecutive: max_reproj_px must be finite and >= 0");
-    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_POSE], &t = p->stage[ST_TRAJ];
-    if (!stage_fresh(p, m) || !stage_fresh(p, v) || !stage_fresh(p, t))
-        return fail(p, ORB_ESTATE, "landmarks_consecutive: no orb_match_consecutive, orb_pose_consecutive and orb_trajectory_consecutive of the current batch and output set");
-    const uint32_t most = std::min(std::min(m.extent, v.extent + 1u), t.extent);  // pair p reads the matches of frame p, the points of pair p, the records of frames p and p + 1
+    if (int rc = stages_fresh(p, ST_LANDMARK, kStages[ST_LANDMARK].reads)) return rc;
+    // pair p reads the matches of frame p, the points of pair p, the records of frames p and p + 1
+    const uint32_t most = std::min(std::min(p->stage[ST_MATCH].extent, p->stage[ST_POSE].extent + 1u), p->stage[ST_TRAJ].extent);
     if (n_frames < 2u || n_frames > most) return fail(p, ORB_EINVAL, "landmarks_consecutive: need 2..%u frames (the last trajectory call's frames)", most);
     if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
     if (!g.min_views) g.min_views = 2u;
-    HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
-    if (int rc = alloc_all_or_none(p, ST_LANDMARK, "landmarks_consecutive")) return rc;
     hipStream_t s;
-    if (int rc = stage_begin(p, ST_LANDMARK, stream, 1u << ST_MATCH | 1u << ST_POSE | 1u << ST_TRAJ, &s)) return rc;
+    if (int rc = stage_open(p, ST_LANDMARK, stream, kStages[ST_LANDMARK].reads, &s)) return rc;
     const uint32_t pairs = n_frames - 1u;
     LmArgs a{};
     a.counts = p->d_counts;
@@ -2824,7 +2831,6 @@ int orb_landmarks_consecutive(OrbProgram* p, uint32_t n_frames, const OrbLandmar
     a.pred = p->d_mpred;
     a.rows = p->d_mrow;
     a.out = p->d_mland;
-    static_assert(sizeof(OrbLandmark) == 32 && sizeof(OrbLandmarkRow) == kLmRowWords * sizeof(uint32_t) && sizeof(OrbLandmarkParams) == 32, "landmark layouts");
     const dim3 grid(pairs, (unsigned)((cap + kLmThreads - 1u) / kLmThreads));
     HIP_TRY(p, hipMemsetAsync(p->d_mpred, 0, (size_t)pairs * cap, s));
     hipLaunchKernelGGL(k_lm_mark, grid, dim3(kLmThreads), 0, s, a);
@@ -2833,73 +2839,35 @@ int orb_landmarks_consecutive(OrbProgram* p, uint32_t n_frames, const OrbLandmar
 }
 
 int orb_landmarks_read(OrbProgram* p, uint32_t pair, OrbLandmarkRow* row, OrbLandmark* landmarks, size_t n) {
-    if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_LANDMARK];
-    if (!last.extent) return fail(p, ORB_ESTATE, "landmarks_read before landmarks_consecutive");
-    if (pair >= last.extent || (!landmarks && n)) return fail(p, ORB_EINVAL, "landmarks_read: pair %u of %u, or landmarks is NULL", pair, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    if (row) HIP_TRY(p, hipMemcpy(row, p->d_mrow + (size_t)pair * kLmRowWords, sizeof(OrbLandmarkRow), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(p, hipMemcpy(landmarks, p->d_mland + (size_t)pair * cap * 2u, n * sizeof(OrbLandmark), hipMemcpyDeviceToHost));
-    return ORB_OK;
+    // an OrbLandmark is two float4 of d_mland
+    return p ? read_stage(p, ST_LANDMARK, pair, row, p->d_mrow, sizeof(OrbLandmarkRow), landmarks, p->d_mland, sizeof(OrbLandmark), n) : ORB_EINVAL;
 }
 
 int orb_bridge_consecutive(OrbProgram* p, uint32_t n_frames, const OrbBridgeParams* params, void* stream) {
     if (!p || !params) return p ? fail(p, ORB_EINVAL, "bridge_consecutive: params is NULL") : ORB_EINVAL;
     OrbBridgeParams g = *params;
     if (g.reserved[0] | g.reserved[1]) return fail(p, ORB_EINVAL, "bridge_consecutive: reserved words must be 0");
-    if (!(std::isfinite(g.fx) && g.fx > 0.0f) || !(std::isfinite(g.fy) && g.fy > 0.0f) || !std::isfinite(g.cx) || !std::isfinite(g.cy))
-        return fail(p, ORB_EINVAL, "bridge_consecutive: fx and fy must be finite and > 0, cx and cy finite");
-    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f) || !(std::isfinite(g.ratio) && g.ratio >= 0.0f) ||
-        !(std::isfinite(g.scale_tolerance) && g.scale_tolerance >= 0.0f))
-        return fail(p, ORB_EINVAL, "bridge_consecutive: max_reproj_px, ratio and scale_tolerance must be finite and >= 0");
-    if (g.hypotheses > kVerifyMaxHyp || g.max_distance > 256u || g.max_hops > kBrMaxHops || g.window > 4095u || g.consistent_permille > 1000u)
-        return fail(p, ORB_EINVAL, "bridge_consecutive: hypotheses must be 0..%u, max_distance 0..256, max_hops 0..%u, window 0..4095, consistent_permille 0..1000",
-                    kVerifyMaxHyp, kBrMaxHops);
-    const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_POSE], &t = p->stage[ST_TRAJ], &l = p->stage[ST_LANDMARK];
-    if (!stage_fresh(p, m) || !stage_fresh(p, v) || !stage_fresh(p, t) || !stage_fresh(p, l))
-        return fail(p, ORB_ESTATE, "bridge_consecutive: no orb_match_consecutive, orb_pose_consecutive, orb_trajectory_consecutive and orb_landmarks_consecutive of the current batch and output set");
-    const uint32_t most = std::min(std::min(m.extent, v.extent + 1u), std::min(t.extent, l.extent + 1u));
+    if (int rc = check_intrinsics(p, ST_BRIDGE, g.fx, g.fy, g.cx, g.cy)) return rc;
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f) || !(std::isfinite(g.scale_tolerance) && g.scale_tolerance >= 0.0f))
+        return fail(p, ORB_EINVAL, "bridge_consecutive: max_reproj_px and scale_tolerance must be finite and >= 0");
+    if (int rc = ransac_params(p, ST_BRIDGE, &g.hypotheses, &g.max_distance, &g.ratio)) return rc;
+    if (g.max_hops > kBrMaxHops || g.window > 4095u || g.consistent_permille > 1000u)
+        return fail(p, ORB_EINVAL, "bridge_consecutive: max_hops must be 0..%u, window 0..4095, consistent_permille 0..1000", kBrMaxHops);
+    if (int rc = stages_fresh(p, ST_BRIDGE, kStages[ST_BRIDGE].reads)) return rc;
+    const Stage* const st = p->stage;
+    const uint32_t most = std::min(std::min(st[ST_MATCH].extent, st[ST_POSE].extent + 1u), std::min(st[ST_TRAJ].extent, st[ST_LANDMARK].extent + 1u));
     if (n_frames < 2u || n_frames > most) return fail(p, ORB_EINVAL, "bridge_consecutive: need 2..%u frames (the last landmarks call's frames)", most);
     if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
-    if (!g.hypotheses) g.hypotheses = 512u;
-    if (!g.max_distance) g.max_distance = 64u;
-    if (g.ratio == 0.0f) g.ratio = 0.8f;
     if (!g.max_hops) g.max_hops = 4u;
     if (!g.window) g.window = 32u;
     if (!g.min_shared) g.min_shared = 8u;
     if (g.scale_tolerance == 0.0f) g.scale_tolerance = 0.1f;
     if (!g.consistent_permille) g.consistent_permille = 500u;
-    HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
-    if (int rc = alloc_all_or_none(p, ST_BRIDGE, "bridge_consecutive")) return rc;
     hipStream_t s;
-    if (int rc = stage_begin(p, ST_BRIDGE, stream, 1u << ST_MATCH | 1u << ST_POSE | 1u << ST_TRAJ | 1u << ST_LANDMARK, &s)) return rc;
+    if (int rc = stage_open(p, ST_BRIDGE, stream, kStages[ST_BRIDGE].reads, &s)) return rc;
     BrArgs a{};
-    a.loc.counts = p->d_counts;
-    a.loc.corners = p->d_corners;
-    a.loc.matches = p->d_matches;
-    a.loc.cap = (uint32_t)cap;
-    a.loc.poses = p->d_pose;
-    a.loc.points = p->d_ppoints;
-    a.loc.hyps = g.hypotheses;
-    a.loc.max_distance = g.max_distance;
-    a.loc.ratio = g.ratio;
-    a.loc.fx = g.fx;
-    a.loc.fy = g.fy;
-    a.loc.cx = g.cx;
-    a.loc.cy = g.cy;
-    a.loc.r2 = g.max_reproj_px * g.max_reproj_px;
-    a.loc.seed_mix = lowbias32(g.seed ^ kBrSeedSalt);
-    a.loc.reca = p->d_breca;
-    a.loc.recb = p->d_brecb;
-    a.loc.cand_of = nullptr;  // k_loc_score reads none
-    a.loc.n_cand = p->d_bn;
-    a.loc.keys = p->d_bkeys;
-    a.loc.fix = p->d_bfix;
-    a.loc.mask = p->d_bmask;
+    a.loc = loc_args(p, p->bridge, g, kBrSeedSalt);
     a.frames = p->d_jframe;
     a.lms = p->d_mland;
     a.n_frames = n_frames;
@@ -2910,9 +2878,7 @@ int orb_bridge_consecutive(OrbProgram* p, uint32_t n_frames, const OrbBridgePara
     a.permille = g.consistent_permille;
     a.ratios = p->d_bratio;
     a.out = p->d_bout;
-    static_assert(sizeof(OrbBridgePose) == kBrOutWords * sizeof(uint32_t) && sizeof(OrbBridgeParams) == 64 && kBrFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose),
-                  "bridge layouts");
-    HIP_TRY(p, hipMemsetAsync(p->d_bmask, 0, (size_t)n_frames * cap, s));
+    HIP_TRY(p, hipMemsetAsync(p->bridge.mask, 0, (size_t)n_frames * cap, s));
     hipLaunchKernelGGL(k_br_gather, dim3(n_frames), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_loc_score, dim3(n_frames, (g.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a.loc);
     hipLaunchKernelGGL(k_br_refine, dim3(n_frames), dim3(256), 0, s, a);
@@ -2921,17 +2887,7 @@ int orb_bridge_consecutive(OrbProgram* p, uint32_t n_frames, const OrbBridgePara
 }
 
 int orb_bridge_read(OrbProgram* p, uint32_t frame, OrbBridgePose* pose, uint8_t* inliers, size_t n) {
-    if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_BRIDGE];
-    if (!last.extent) return fail(p, ORB_ESTATE, "bridge_read before bridge_consecutive");
-    if (frame >= last.extent || (!inliers && n)) return fail(p, ORB_EINVAL, "bridge_read: frame %u of %u, or inliers is NULL", frame, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    if (pose) HIP_TRY(p, hipMemcpy(pose, p->d_bout + (size_t)frame * kBrOutWords, sizeof(OrbBridgePose), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(p, hipMemcpy(inliers, p->d_bmask + (size_t)frame * cap, n, hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_stage(p, ST_BRIDGE, frame, pose, p->d_bout, sizeof(OrbBridgePose), inliers, p->bridge.mask, 1, n) : ORB_EINVAL;
 }
 
 int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams* params, void* stream) {
@@ -2953,16 +2909,16 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
     const Stage &m = p->stage[ST_MATCH], &v = p->stage[ST_VERIFY], &gd = p->stage[ST_GUIDE];
     uint32_t pairs_avail = 0, reads = 0;  // reads: the stages whose results the links come from
     if (t.source == ORB_TRACK_VERIFIED) {  // the inlier bytes and the matches they mark, which must be the ones the verification read
-        if (!stage_fresh(p, v) || m.seq != v.seq || m.set != v.set)
-            return fail(p, ORB_ESTATE, "track_consecutive: no orb_verify_consecutive of the current batch, output set and matches");
+        if (int rc = stages_fresh(p, ST_TRACK, 1u << ST_VERIFY)) return rc;
+        if (m.seq != v.seq || m.set != v.set) return fail(p, ORB_ESTATE, "track_consecutive: orb_match_consecutive ran again since orb_verify_consecutive");
         pairs_avail = v.extent;
         reads = 1u << ST_MATCH | 1u << ST_VERIFY;
     } else if (t.source == ORB_TRACK_GUIDED) {
-        if (!stage_fresh(p, gd)) return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_guided of the current batch and output set");
+        if (int rc = stages_fresh(p, ST_TRACK, 1u << ST_GUIDE)) return rc;
         pairs_avail = gd.extent;
         reads = 1u << ST_GUIDE;
     } else {
-        if (!stage_fresh(p, m)) return fail(p, ORB_ESTATE, "track_consecutive: no orb_match_consecutive of the current batch and output set");
+        if (int rc = stages_fresh(p, ST_TRACK, 1u << ST_MATCH)) return rc;
         pairs_avail = m.extent - 1u;
         reads = 1u << ST_MATCH;
     }
@@ -2972,22 +2928,20 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
         if (!t.max_distance) t.max_distance = 64u;
         if (t.ratio == 0.0f) t.ratio = 0.8f;
     }
-    HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features, B = p->max_batch;
     if (p->track_global_keys < 0) {
         const char* e = getenv("TINYORB_TRACK_GLOBAL_KEYS");
         p->track_global_keys = (e && atoi(e) != 0) ? 1 : 0;
     }
-    if (int rc = alloc_all_or_none(p, ST_TRACK, "track_consecutive")) return rc;
     hipStream_t s;
-    if (int rc = stage_begin(p, ST_TRACK, stream, reads, &s)) return rc;
+    if (int rc = stage_open(p, ST_TRACK, stream, reads, &s)) return rc;
     TrackArgs a{};
     a.counts = p->d_counts;
     a.cap = (uint32_t)cap;
     a.frames = n_frames;
     a.stride = (uint32_t)B;
     a.source = t.source;
-    a.rec = t.source == ORB_TRACK_GUIDED ? p->d_gmatch : p->d_matches;
+    a.rec = t.source == ORB_TRACK_GUIDED ? p->guide.match : p->d_matches;
     a.mask = p->verify.mask;
     a.max_distance = t.max_distance;
     a.ratio = t.ratio;
@@ -3027,17 +2981,7 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
 }
 
 int orb_track_read(OrbProgram* p, uint32_t frame, OrbTrack* dst, size_t n) {
-    if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_TRACK];
-    if (!last.extent) return fail(p, ORB_ESTATE, "track_read before track_consecutive");
-    if (frame >= last.extent || (!dst && n)) return fail(p, ORB_EINVAL, "track_read: frame %u of %u, or dst is NULL", frame, last.extent);
-    HIP_TRY(p, hipSetDevice(p->device));
-    HIP_TRY(p, hipEventSynchronize(last.done));
-    const size_t cap = p->cfg.max_features;
-    if (n > cap) n = cap;
-    static_assert(sizeof(OrbTrack) == 16 && sizeof(OrbTrackFrame) == 32 && sizeof(OrbTrackParams) == 32, "track layouts");
-    if (n) HIP_TRY(p, hipMemcpy(dst, p->d_track + (size_t)frame * cap, n * sizeof(OrbTrack), hipMemcpyDeviceToHost));
-    return ORB_OK;
+    return p ? read_stage(p, ST_TRACK, frame, nullptr, nullptr, 0, dst, p->d_track, sizeof(OrbTrack), n) : ORB_EINVAL;
 }
 
 int orb_track_frames(OrbProgram* p, OrbTrackFrame* dst, size_t n) {
