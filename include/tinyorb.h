@@ -774,6 +774,55 @@ int orb_bridge_consecutive(OrbProgram *p, uint32_t n_frames, const OrbBridgePara
  * inliers NULL with n > 0. */
 int orb_bridge_read(OrbProgram *p, uint32_t frame, OrbBridgePose *pose, uint8_t *inliers, size_t n);
 
+/* ---- poses and landmarks refined by reprojection (NOT in the reference; definition BA-1..BA-7 in DESIGN.md section 24) ----
+ * Every OrbFramePose is a product of two-view poses, and orb_landmarks_consecutive places its points under those poses without
+ * moving one.  Here the two are alternated (resection-intersection: bundle adjustment by block coordinate descent).  A frame is
+ * free iff its trajectory status is CHAINED; every other frame is held, so the first two cameras of a segment never move and
+ * the result stays in the trajectory's frame and unit.  The GOOD landmarks whose views all lie inside the call's frames take
+ * part; keypoint k of a free frame g belongs to the landmark of g's segment with the smallest pair * capacity + slot among
+ * those that see it.  A round is one Gauss-Newton step of orb_localize_consecutive's refit on every free frame over the
+ * keypoints that have an owner (all from the points of the round before), then orb_landmarks_consecutive's point nearest to all
+ * rays for every landmark under the new poses; an unsolved landmark keeps its point.  No step is damped or rejected: the
+ * record reports the cost (the sum of squared pixel residuals over the frame's owned keypoints) before the first step and
+ * after the last.  Binary32 arithmetic in a fixed order, no fused operations: a CPU restatement gives the same bits.  Nothing
+ * is fed back into another stage. */
+typedef struct {            /* zero-initialised is NOT valid: fx, fy must be > 0 */
+    float fx, fy, cx, cy;   /* the intrinsics given to orb_pose_consecutive */
+    float max_reproj_px;    /* closing check: reprojection error a view may have (0: 2.0); finite, >= 0 */
+    uint32_t rounds;        /* alternations, 1..16 (0: 4) */
+    uint32_t reserved[2];   /* must be 0 (ORB_EINVAL otherwise) */
+} OrbAdjustParams;          /* 32 bytes */
+
+#define ORB_ADJUST_HELD 0u    /* not CHAINED: r and t are the trajectory's bits, the other words 0 */
+#define ORB_ADJUST_REFINED 1u /* every round's step was taken */
+#define ORB_ADJUST_FEW 2u     /* fewer than 6 owned keypoints: the trajectory's pose, observations, costs 0 */
+#define ORB_ADJUST_FAILED 3u  /* a step failed: the last pose kept and both costs; or the trajectory's record is not finite: all 0 but observations */
+
+typedef struct {
+    float r[9];             /* row-major R, X_f = R X_origin + t, as OrbFramePose */
+    float t[3];
+    float cost_before;      /* sum of squared pixel residuals over the owned keypoints, under the trajectory's pose and the landmark stage's points */
+    float cost_after;       /* the same under the poses and points written (a cost that is not finite reads FLT_MAX) */
+    uint32_t observations;  /* keypoints of this frame that have an owner */
+    uint32_t status;        /* ORB_ADJUST_* */
+} OrbAdjustedPose;          /* 64 bytes */
+
+/* Refined poses of frames 0 .. n_frames - 1 of the last batch and refined landmarks of its pairs.  ORB_EINVAL for a NULL program
+ * or params, fx or fy not finite or not > 0, cx or cy not finite, max_reproj_px not finite or < 0, rounds above 16, a reserved
+ * word that is not 0, n_frames not in 2 .. the last orb_landmarks_consecutive's frames, or n_frames * max_features >= 2^32 - 1;
+ * ORB_ESTATE unless the last orb_match_consecutive, orb_trajectory_consecutive and orb_landmarks_consecutive are all of the
+ * current batch and output set.  Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not change it),
+ * ordered behind those three stages' last calls and the last call of its own when they ran on another stream; the three wait for
+ * such a call on another stream before they overwrite what it reads.  Result buffers of its own (allocated by the first call):
+ * no other stage's results are ever written. */
+int orb_adjust_consecutive(OrbProgram *p, uint32_t n_frames, const OrbAdjustParams *params, void *stream);
+/* Copy the record of frame `frame` of the last orb_adjust_consecutive call (pose may be NULL) and the first n landmark records of
+ * the pair (frame, frame + 1) -- indexed and laid out as orb_landmarks_read's: a landmark that took part with its refined point,
+ * inliers recounted and GOOD iff every view is one, every other record as the landmark stage wrote it; zeros for the last
+ * frame -- to the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a frame outside its frames or landmarks NULL
+ * with n > 0. */
+int orb_adjust_read(OrbProgram *p, uint32_t frame, OrbAdjustedPose *pose, OrbLandmark *landmarks, size_t n);
+
 /* ---- feature tracks and keyframes (NOT in the reference; definition TK-1..TK-5 in DESIGN.md section 15) ----
  * Over the pairs (f, f+1), f in [0, n_frames - 1), of the last batch: query i of frame f links to target j of frame f+1 by the
  * source's record (VERIFIED: the matcher's record where the last verification's inlier byte is 1; GUIDED / MATCHED: the last

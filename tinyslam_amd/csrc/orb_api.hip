@@ -35,6 +35,7 @@
 #include "orb_kernels_localize.h"
 #include "orb_kernels_landmark.h"
 #include "orb_kernels_bridge.h"
+#include "orb_kernels_adjust.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -70,7 +71,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -110,6 +111,10 @@ constexpr StageInfo kStages[ST_COUNT] = {
      1u << ST_POSE |      // d_ppoints
      1u << ST_TRAJ |      // d_jframe
      1u << ST_LANDMARK},  // d_mland
+    {"adjust_consecutive", "adjust_read",
+     1u << ST_MATCH |     // d_matches: the views of a landmark
+     1u << ST_TRAJ |      // d_jframe
+     1u << ST_LANDMARK},  // d_mland
 };
 static_assert(kStages[ST_COUNT - 1].name != nullptr, "a row of kStages for every StageId");
 
@@ -137,6 +142,8 @@ static_assert(sizeof(OrbFrameFix) == kLocFixWords * sizeof(uint32_t) && sizeof(O
 static_assert(sizeof(OrbLandmark) == 32 && sizeof(OrbLandmarkRow) == kLmRowWords * sizeof(uint32_t) && sizeof(OrbLandmarkParams) == 32, "landmark layouts");
 static_assert(sizeof(OrbBridgePose) == kBrOutWords * sizeof(uint32_t) && sizeof(OrbBridgeParams) == 64 && kBrFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose),
               "bridge layouts");
+static_assert(sizeof(OrbAdjustedPose) == kBaPoseWords * sizeof(uint32_t) && sizeof(OrbAdjustParams) == 32 && kBaFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose),
+              "adjust layouts");
 
 // The last call of a stage
 struct Stage {
@@ -259,6 +266,11 @@ struct OrbProgram {
     PnpState bridge;
     uint32_t* d_bout = nullptr;           // [max_batch][24] OrbBridgePose
     uint32_t* d_bratio = nullptr;         // [max_batch][max_features] the bits of a join's ratios
+    // orb_adjust_consecutive (orb_kernels_adjust.h)
+    uint32_t* d_apose = nullptr;          // [max_batch][16] OrbAdjustedPose: the current poses during a call
+    float4* d_ax = nullptr;               // [max_batch][max_features] the current point of every landmark slot
+    uint32_t* d_aowner = nullptr;         // [max_batch][max_features] the owner of every keypoint slot
+    float4* d_aland = nullptr;            // [max_batch][max_features][2] OrbLandmark
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -466,6 +478,12 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&p->d_mland, B * cap * sizeof(OrbLandmark));
         add(&p->d_mrow, B * sizeof(OrbLandmarkRow));
         add(&p->d_mpred, B * cap);
+        break;
+    case ST_ADJUST:
+        add(&p->d_apose, B * sizeof(OrbAdjustedPose));
+        add(&p->d_ax, B * cap * sizeof(float4));
+        add(&p->d_aowner, B * cap * sizeof(uint32_t));
+        add(&p->d_aland, B * cap * sizeof(OrbLandmark));
         break;
     }
     return l;
@@ -2888,6 +2906,59 @@ int orb_bridge_consecutive(OrbProgram* p, uint32_t n_frames, const OrbBridgePara
 
 int orb_bridge_read(OrbProgram* p, uint32_t frame, OrbBridgePose* pose, uint8_t* inliers, size_t n) {
     return p ? read_stage(p, ST_BRIDGE, frame, pose, p->d_bout, sizeof(OrbBridgePose), inliers, p->bridge.mask, 1, n) : ORB_EINVAL;
+}
+
+int orb_adjust_consecutive(OrbProgram* p, uint32_t n_frames, const OrbAdjustParams* params, void* stream) {
+    if (!p || !params) return p ? fail(p, ORB_EINVAL, "adjust_consecutive: params is NULL") : ORB_EINVAL;
+    OrbAdjustParams g = *params;
+    if (g.reserved[0] | g.reserved[1]) return fail(p, ORB_EINVAL, "adjust_consecutive: reserved words must be 0");
+    if (int rc = check_intrinsics(p, ST_ADJUST, g.fx, g.fy, g.cx, g.cy)) return rc;
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f) || g.rounds > 16u)
+        return fail(p, ORB_EINVAL, "adjust_consecutive: max_reproj_px must be finite and >= 0, rounds 0..16");
+    if (int rc = stages_fresh(p, ST_ADJUST, kStages[ST_ADJUST].reads)) return rc;
+    // frame g reads the matches, the frame record and the landmarks of index g (the last frame only its frame record)
+    const Stage* const st = p->stage;
+    const uint32_t most = std::min(st[ST_MATCH].extent, std::min(st[ST_TRAJ].extent, st[ST_LANDMARK].extent + 1u));
+    if (n_frames < 2u || n_frames > most) return fail(p, ORB_EINVAL, "adjust_consecutive: need 2..%u frames (the last landmarks call's frames)", most);
+    const size_t cap = p->cfg.max_features;
+    if ((unsigned long long)n_frames * cap >= 0xffffffffull)  // BA-3: a key p * cap + i below the "no owner" word
+        return fail(p, ORB_EINVAL, "adjust_consecutive: n_frames * max_features must be below 2^32 - 1");
+    if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
+    if (!g.rounds) g.rounds = 4u;
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_ADJUST, stream, kStages[ST_ADJUST].reads, &s)) return rc;
+    BaArgs a{};
+    a.counts = p->d_counts;
+    a.corners = p->d_corners;
+    a.matches = p->d_matches;
+    a.cap = (uint32_t)cap;
+    a.n_frames = n_frames;
+    a.frames = p->d_jframe;
+    a.lms = p->d_mland;
+    a.fx = g.fx;
+    a.fy = g.fy;
+    a.cx = g.cx;
+    a.cy = g.cy;
+    a.r2 = g.max_reproj_px * g.max_reproj_px;
+    a.owner = p->d_aowner;
+    a.X = p->d_ax;
+    a.pose = p->d_apose;
+    a.out = p->d_aland;
+    const unsigned blocks = (unsigned)((cap + kBaThreads - 1u) / kBaThreads);
+    const dim3 by_frame(n_frames, blocks), by_pair(n_frames - 1u, blocks);
+    HIP_TRY(p, hipMemsetAsync(p->d_aowner, 0xff, (size_t)n_frames * cap * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_ba_index, by_frame, dim3(kBaThreads), 0, s, a);
+    for (uint32_t r = 0; r < g.rounds; r++) {  // BA-6
+        hipLaunchKernelGGL(k_ba_motion, dim3(n_frames), dim3(kBaThreads), 0, s, a, r ? kBaStep : kBaFirst);
+        hipLaunchKernelGGL(k_ba_structure, by_pair, dim3(kBaThreads), 0, s, a);
+    }
+    hipLaunchKernelGGL(k_ba_motion, dim3(n_frames), dim3(kBaThreads), 0, s, a, kBaClose);
+    hipLaunchKernelGGL(k_ba_check, by_frame, dim3(kBaThreads), 0, s, a);
+    return stage_end(p, ST_ADJUST, s, n_frames);  // p->last_stream stays, as after a guided call
+}
+
+int orb_adjust_read(OrbProgram* p, uint32_t frame, OrbAdjustedPose* pose, OrbLandmark* landmarks, size_t n) {
+    return p ? read_stage(p, ST_ADJUST, frame, pose, p->d_apose, sizeof(OrbAdjustedPose), landmarks, p->d_aland, sizeof(OrbLandmark), n) : ORB_EINVAL;
 }
 
 int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams* params, void* stream) {

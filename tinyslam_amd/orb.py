@@ -76,6 +76,10 @@ BRIDGE_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", 
                               ("candidates", "<u4"), ("inliers", "<u4"), ("hypothesis", "<u4"), ("shared", "<u4"), ("consistent", "<u4"),
                               ("fix", "<u4"), ("status", "<u4"), ("reserved", "<u4", (1,))])
 ORB_BRIDGE_COPIED, ORB_BRIDGE_MOVED, ORB_BRIDGE_FIXED, ORB_BRIDGE_JOINED, ORB_BRIDGE_UNFIXED = 0, 1, 2, 3, 4
+# poses and landmarks refined by reprojection (orb_adjust_consecutive): OrbAdjustedPose (64 B), its status
+ADJUSTED_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("cost_before", "<f4"), ("cost_after", "<f4"),
+                                ("observations", "<u4"), ("status", "<u4")])
+ORB_ADJUST_HELD, ORB_ADJUST_REFINED, ORB_ADJUST_FEW, ORB_ADJUST_FAILED = 0, 1, 2, 3
 # feature tracks and keyframes (orb_track_consecutive): the link source, OrbTrack (16 B), OrbTrackFrame (32 B)
 ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
 TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
@@ -106,6 +110,7 @@ EXPORTS = [
     "orb_localize_consecutive", "orb_localize_read",
     "orb_landmarks_consecutive", "orb_landmarks_read",
     "orb_bridge_consecutive", "orb_bridge_read",
+    "orb_adjust_consecutive", "orb_adjust_read",
 ]
 
 
@@ -194,6 +199,15 @@ class _BridgeParams(ctypes.Structure):
 
 
 OrbBridgeParams = _BridgeParams
+
+
+class _AdjustParams(ctypes.Structure):
+    """OrbAdjustParams (32 bytes; fx and fy must be > 0, the other zero fields = the defaults)"""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("max_reproj_px", ctypes.c_float), ("rounds", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+OrbAdjustParams = _AdjustParams
 
 
 class _TrackParams(ctypes.Structure):
@@ -293,6 +307,8 @@ def load_library(path=None):
     L.orb_landmarks_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_bridge_consecutive.argtypes = [vp, u32, ctypes.POINTER(_BridgeParams), vp]
     L.orb_bridge_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_adjust_consecutive.argtypes = [vp, u32, ctypes.POINTER(_AdjustParams), vp]
+    L.orb_adjust_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -808,6 +824,24 @@ class OrbProgram:
         mask = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=np.uint8)
         self._check(self._lib.orb_bridge_read(self._handle(), frame, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
         return rec, mask
+
+    def adjust_consecutive(self, n_frames, fx, fy, cx, cy, max_reproj_px=0.0, rounds=0, stream=None, reserved=(0, 0)):
+        """Poses and landmarks refined by reprojection (not in the reference; DESIGN.md section 24, BA-1..BA-7): `rounds` (0: 4;
+        1..16) alternations of a Gauss-Newton step on every CHAINED frame of the last trajectory_consecutive over the keypoints
+        that GOOD landmarks of the last landmarks_consecutive own, and the point nearest to all rays for every such landmark
+        under the new poses; every other frame is held.  A closing pass checks every landmark's views within max_reproj_px
+        (0: 2.0).  The intrinsics are those given to pose_consecutive.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        prm = _AdjustParams(float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
+                            float(np.float32(max_reproj_px)), rounds, (ctypes.c_uint32 * 2)(*reserved))
+        self._check(self._lib.orb_adjust_consecutive(self._handle(), n_frames, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def adjust_read(self, frame, n=None):
+        """(record of ADJUSTED_POSE_DTYPE, LANDMARK_DTYPE[min(n, max_features)]: the refined records at pair `frame`'s slots, zeros
+        for the last frame; n None: max_features) of the last adjust_consecutive -- synchronises."""
+        rec = np.zeros((), dtype=ADJUSTED_POSE_DTYPE)
+        lm = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=LANDMARK_DTYPE)
+        self._check(self._lib.orb_adjust_read(self._handle(), frame, _ptr(rec), _ptr(lm) if len(lm) else None, len(lm)))
+        return rec, lm
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
