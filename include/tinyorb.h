@@ -902,6 +902,14 @@ int orb_debug_angle_code(OrbProgram *p, const float *cy, const float *cx, uint32
  * stored [code][lane 0..63][test lane + 64 e, e = 0..3][a, b].  Writes min(n_entries, codes * 512) values; *codes and *pitch
  * (either may be NULL) say what the table was built for. */
 int orb_debug_rot_table(OrbProgram *p, int16_t *dst, size_t n_entries, uint32_t *codes, uint32_t *pitch);
+/* For tests: the blur column table that the program built at creation for the bands of `level` (the fused pipeline's level 0 on
+ * full-width bands), one 24-byte entry per column blur_q .. width - 1: uint16 a0, a1, b0, b1, float fa, fb, f2, uint32 0 -- pass 2
+ * at the column lerps pass 1 at two columns with fraction f2; pass 1 at the first (second) of them lerps the grey texels a0, a1
+ * (b0, b1) with fraction fa (fb), and a0 (b0) == 0xffff says that pass-1 column lies where pass 1 is one value per row.  Writes
+ * min(n_entries, *n_var) entries; *n_var is 0 for a level whose bands build the table themselves; *blur_p and *blur_q are the
+ * level's constant stretches of pass 1 and of the final blur.  dst may be NULL with n_entries 0, and so may each of the three. */
+int orb_debug_blur_col_table(OrbProgram *p, uint32_t level, void *dst, size_t n_entries, uint32_t *n_var, uint32_t *blur_p,
+                             uint32_t *blur_q);
 /* For tests: device pointers of what orb_trajectory_consecutive reads besides the raw counters (any of the three may be NULL):
  * matches[max_batch][max_features] OrbMatch (row f: the queries of frame f), poses[max_batch] OrbPairPose and
  * points[max_batch][max_features] OrbPoint (row f: pair (f, f + 1)).  ORB_ESTATE until an orb_match_consecutive and an

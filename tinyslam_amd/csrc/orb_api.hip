@@ -333,6 +333,7 @@ struct OrbProgram {
     float* d_cos = nullptr;
     float* d_sin = nullptr;
     uint4* d_rot = nullptr;  // the pattern rotated by every angle code (k_rot_table), for k_brief_nf or k_brief_i
+    uint4* d_blur_tab = nullptr;  // the plain fused path: k_front's BlurCol table of level 0 (k_blur_col_table), in 16-byte pieces; null when level 0 runs on column tiles
     unsigned long long* d_stamps = nullptr;  // TINYORB_STAMPS=1: phase cycle sums of k_front (2 x 16 slots)
 
     // host staging of the single-frame API (orb.rs:216-218 staging buffers)
@@ -877,6 +878,11 @@ int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_
     return ORB_OK;
 }
 
+// The program's ready-made blur column table for a launch of geometry g (FrontGeom::blur_tab): level 0 on full-width bands has one.
+const BlurCol* front_blur_tab(const OrbProgram* p, const FrontGeom& g) {
+    return (g.lvl == 0u && !g.tiled) ? reinterpret_cast<const BlurCol*>(p->d_blur_tab) : nullptr;
+}
+
 // The geometry of level `lvl` of the plain fused pipeline for a batch of n frames; gw, gh: the octave's FAST dispatch domain (orb.rs:501-519).
 FrontGeom fused_level_geometry(const OrbProgram* p, uint32_t lvl, uint32_t gw, uint32_t gh, uint32_t n) {
     const Pyramid& pyr = p->pyr;
@@ -892,6 +898,7 @@ FrontGeom fused_level_geometry(const OrbProgram* p, uint32_t lvl, uint32_t gw, u
     g.oob = p->oob;
     g.wq = p->wq;
     g.fp = p->opt.fp_contract;
+    g.blur_tab = front_blur_tab(p, g);
     g.store_grey = (lvl == 0 && pyr.depth > 1 && !(pyr.w[0] == 2u * pyr.w[1] && pyr.h[0] == 2u * pyr.h[1])) ? 1u : 0u;
     return g;
 }
@@ -1648,6 +1655,21 @@ int orb_program_create(const OrbConfig* config, const OrbOptions* options, OrbPr
         CREATE_TRY(hipGetLastError());
         CREATE_TRY(hipStreamSynchronize(p->stream));
     }
+    if (p->fused && !p->tile_w_lvl[0]) {
+        // k_front's blur column table of level 0: a function of the level's width (and the sampler's weight bits) alone, so built here
+        // once, with the band's own arithmetic (blur_col_entry), instead of by every band of every frame.  A level 0 on column tiles
+        // and the levels above keep building theirs in the band (orb_front_body.inc).
+        const FrontGeom g = front_geometry(p->pyr, 0, 8u, 8u, 1, p->band_rows_lvl[0]);  // blur_p, blur_q, n_var: of the width alone
+        const uint32_t pieces = blur_col_pieces(g.n_var);
+        if (pieces) {
+            CREATE_TRY(hipMalloc(&p->d_blur_tab, (size_t)pieces * sizeof(uint4)));
+            CREATE_TRY(hipMemsetAsync(p->d_blur_tab, 0, (size_t)pieces * sizeof(uint4), p->stream));  // an odd n_var ends in the middle of a piece
+            hipLaunchKernelGGL(k_blur_col_table<>, dim3((g.n_var + 63u) / 64u), dim3(64), 0, p->stream, p->pyr.w[0], g.blur_p, g.blur_q, g.n_var, p->wq,
+                               reinterpret_cast<BlurCol*>(p->d_blur_tab));
+            CREATE_TRY(hipGetLastError());
+            CREATE_TRY(hipStreamSynchronize(p->stream));
+        }
+    }
     if (p->fused && getenv("TINYORB_STAMPS")) {  // diagnostic builds only (tools/stamps.py)
         CREATE_TRY(hipMalloc(&p->d_stamps, 32 * sizeof(unsigned long long)));
         CREATE_TRY(hipMemset(p->d_stamps, 0, 32 * sizeof(unsigned long long)));
@@ -1716,6 +1738,7 @@ void orb_program_destroy(OrbProgram* p) {
     (void)hipFree(p->d_cos);
     (void)hipFree(p->d_sin);
     if (p->d_rot) (void)hipFree(p->d_rot);
+    (void)hipFree(p->d_blur_tab);
     (void)hipFree(p->d_stamps);
     for (int st = 0; st < ST_COUNT; st++) {
         free_stage_buffers(p, st);
@@ -1878,6 +1901,7 @@ int orb_extract_corners(OrbProgram* p, uint32_t* corner_count) {
                 g[lvl].xcd_swizzle = 0u;
                 g[lvl].wq = p->wq;
                 g[lvl].fp = p->opt.fp_contract;
+                g[lvl].blur_tab = front_blur_tab(p, g[lvl]);
                 if (p->env.phase_mask >= 0) g[lvl].phase_mask = (uint32_t)p->env.phase_mask;
                 lds = std::max(lds, front_lds_bytes(g[lvl]));
             }
@@ -3186,6 +3210,22 @@ int orb_debug_rot_table(OrbProgram* p, int16_t* dst, size_t n_entries, uint32_t*
     if (n && !dst) return fail(p, ORB_EINVAL, "dst is NULL");
     HIP_TRY(p, hipSetDevice(p->device));
     if (n) HIP_TRY(p, hipMemcpy(dst, p->d_rot, n * sizeof(int16_t), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+// The program's ready-made BlurCol table of one level, as k_blur_col_table wrote it (tinyorb.h).
+int orb_debug_blur_col_table(OrbProgram* p, uint32_t level, void* dst, size_t n_entries, uint32_t* n_var, uint32_t* blur_p, uint32_t* blur_q) {
+    if (!p) return ORB_EINVAL;
+    if (level >= p->pyr.depth) return fail(p, ORB_EINVAL, "level %u of %u", level, p->pyr.depth);
+    FrontGeom g = front_geometry(p->pyr, level, 8u, 8u, 1, p->band_rows_lvl[level] ? p->band_rows_lvl[level] : (uint32_t)kFrontRows, p->tile_w_lvl[level]);
+    const BlurCol* tab = front_blur_tab(p, g);
+    if (n_var) *n_var = tab ? g.n_var : 0u;
+    if (blur_p) *blur_p = g.blur_p;
+    if (blur_q) *blur_q = g.blur_q;
+    const size_t n = tab ? std::min<size_t>(n_entries, g.n_var) : 0;
+    if (n && !dst) return fail(p, ORB_EINVAL, "dst is NULL");
+    HIP_TRY(p, hipSetDevice(p->device));
+    if (n) HIP_TRY(p, hipMemcpy(dst, tab, n * sizeof(BlurCol), hipMemcpyDeviceToHost));
     return ORB_OK;
 }
 

@@ -37,9 +37,9 @@
     // two bit sets over the band's pre-test items (geo.ovf_words words each): the items whose survivors did not fit queue A in
     // this round of the detector / in the one before
     uint32_t* const ovf_sets = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(blur_k2 + R) + (TILED ? 8 * R : 0));
-    // per column >= blur_q: tap positions.  Used by phase C only, which runs before the detector: it borrows the storage of
-    // queues B and C, which are first written in stage S1 -- behind the barrier that ends the pre-test, which every wave
-    // reaches after its share of phase C.
+    // per column >= blur_q: tap positions -- written during phase A (the program's ready-made table, copied) or straight behind it
+    // (built by the band).  Used by phase C only, which runs before the detector: it borrows the storage of queues B and C, which
+    // are first written in stage S1 -- behind the barrier that ends the pre-test, which every wave reaches after its share of phase C.
     BlurCol* const blur_cols = reinterpret_cast<BlurCol*>(tmp);
 
     // ---- which band (tile) of which frame: keep all bands of a frame on one XCD so halo rows hit its L2
@@ -87,6 +87,20 @@
 #endif
     if (tid < 6) qa_count[tid] = tid == 5 ? ~0u : 0u;
     for (int i = tid; i < 2 * (int)geo.ovf_words; i += NT) ovf_sets[i] = 0u;
+
+    // ---- level 0 on full-width bands: the blur column table, ready-made (geo.blur_tab, k_blur_col_table), copied into blur_cols as
+    // part of phase A, in 16-byte pieces dealt to the workgroup's last threads -- the lanes that stage no row, or one row fewer: thread
+    // tab_t0 + k takes piece k (so the test, the load's offset and the store's address are all built on the thread index, and nothing
+    // of the copy is held across the phase).
+    // TILED: the band builds the table (below) -- its tile 0 shares that storage by other rules (geo.tmp_halfs) and does the blur alone.
+    // Levels >= 1 build it in the band as well: there the build runs beside the row-constant chain, which is the longer of the two, and
+    // a ready-made table measured slower (NOTEBOOK.md) -- for them nothing of this is compiled.
+    const bool tab_ready = L0 && !TILED && geo.blur_tab != nullptr && (geo.phase_mask & 8u);
+    const int n_pieces = (int)blur_col_pieces(geo.n_var), tab_t0 = max(NT - n_pieces, 0);
+    const bool has_piece = tab_ready && tid >= tab_t0;
+    const uint4* const tab_src = reinterpret_cast<const uint4*>(geo.blur_tab);
+    uint4* const tab_dst = reinterpret_cast<uint4*>(blur_cols);
+    bool tab_first = false;  // uniform: phase A's own code has copied the table (all n_pieces <= NT pieces)
 
     // =========================== A: stage grey rows [y0-3, y0+R+3) ===========================
     if (!L0 && SRC) {
@@ -197,6 +211,23 @@
         int dst_w = __mul24(ty, LS) + kLdsPad + (it0 + tx) * 4 - x0;                   // its LDS offset (halfs): LDS column kLdsPad <-> image column x0
         const uint32_t off_step = (uint32_t)(rpp * w * bpp);
         const int dst_step = rpp * LS;
+        // The ready-made blur column table rides in the last of a thread's load slots, so it holds no register of its own across the
+        // phase (a uint4 of its own raised the 720p instance from 48 to 52 VGPRs: this phase, with eight loads in flight, is where the
+        // kernel's count peaks): where every thread with a piece has fewer than U rows to stage and all threads run the first round
+        // (uniform; 720p: the 233 pieces go to threads 791..1023, rows to slot U - 1 of threads 0..319 only), the piece takes slot
+        // U - 1 of that round.  Any other shape copies the table behind the staging (below).
+        const int busy_to = max(R + 6 - (U - 1) * rpp, 0) * per_row;  // the threads below it stage a row through slot U - 1 of the first round
+        // ... decided per wave: all lanes of a wave that holds a piece are free in that slot (the first such wave may hold threads
+        // below tab_t0, hence the rounding), and the choice between the table's load and the row's is a scalar branch -- as a lane
+        // mask the two loads would follow each other in the instruction stream, into the same registers, and the compiler would
+        // make the second wait for every load in flight.  Not in the general variant (UA): it stores its rows to HBM as well and has no
+        // register to spare in this phase -- with the riding piece its instances went from 52..54 VGPRs to 64 and scratch.
+        const bool ride = L0 && !UA && !TILED && n_pieces <= NT && busy_to <= (tab_t0 & ~63) && NT <= (R + 6) * per_row;
+        const bool wave_rides = ride && tab_ready && __builtin_amdgcn_readfirstlane((int)((tid | 63) >= tab_t0)) != 0;
+        const bool rides = wave_rides && has_piece;
+        // the table as a buffer that thread t reads at 16 t: it starts tab_t0 pieces in front of the table (no thread reads those)
+        const __amdgpu_buffer_rsrc_t tab_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+            reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(tab_src) - (uintptr_t)tab_t0 * 16u), 0, (tab_t0 + n_pieces) * 16, kBufferWord3Raw);
         for (int lyb = ty, ly_base = 0; lyb < R + 6; lyb += rpp * U, ly_base += rpp * U) {
             uint4 v[U];
             int dst[U];
@@ -204,12 +235,19 @@
             // TILED: passes of this round that still reach rows of the tile (uniform: a narrow tile stages many rows per
             // pass, and a load for a row past the tile would be real traffic for nothing)
             const int n_u = TILED ? min(U, (R + 6 - ly_base + rpp - 1) / rpp) : U;
+            // the table's piece first, into the slot the wave has no row for: the oldest request of the round, consumed last
+            const bool round_rides = !TILED && ly_base == 0 && wave_rides;  // scalar
+            if (!TILED) {
+                v[U - 1] = make_uint4(0u, 0u, 0u, 0u);
+                if (round_rides && has_piece) v[U - 1] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(tab_rsrc, tid * 16, 0, 0));
+            }
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int ly = lyb + u * rpp;
                 const int gy = y0 - 3 + ly;
                 const bool in_band = lane_ok && ly < R + 6;
-                v[u] = make_uint4(0u, 0u, 0u, 0u);
+                const bool slot_rides = u == U - 1 && round_rides;  // scalar: no lane of the wave has a row in this slot (see ride)
+                if (TILED || u != U - 1) v[u] = make_uint4(0u, 0u, 0u, 0u);
                 if (TILED) {
                     live[u] = false;
                     dst[u] = 0;
@@ -232,16 +270,18 @@
                     // any other lane without an item reads something valid that is never stored.  Buffer loads also only
                     // ask for dword alignment, which is what the general variant's rows have.
                     const int off = (int)off_w;
-                    if (Y8 && UA) {  // rows start on any byte; the last group of a row may be partial
-                        const uint8_t* q = src0 + (size_t)(ok ? off_w : 0u);
-                        const int left = ok ? w - (it0 + tx) * 4 : 4;
-                        v[u].x = (uint32_t)q[0] | ((uint32_t)q[left > 1 ? 1 : 0] << 8) | ((uint32_t)q[left > 2 ? 2 : 0] << 16) |
-                                 ((uint32_t)q[left > 3 ? 3 : 0] << 24);
-                    } else if (Y8) {  // four texels = four bytes, converted on the way in (rows are 4-byte aligned here)
-                        v[u] = __builtin_bit_cast(uint4, buffer_load_format_xyzw(frame_unorm, off, 0, 0));
-                    } else {  // RGBA quad; in the general variant (UA) the last quad of a row may run into the next row: those
-                              // texels land in columns >= w, which nothing ever uses
-                        v[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(frame_rsrc, off, 0, 0));
+                    if (!slot_rides) {  // (a riding slot holds the table's piece)
+                        if (Y8 && UA) {  // rows start on any byte; the last group of a row may be partial
+                            const uint8_t* q = src0 + (size_t)(ok ? off_w : 0u);
+                            const int left = ok ? w - (it0 + tx) * 4 : 4;
+                            v[u].x = (uint32_t)q[0] | ((uint32_t)q[left > 1 ? 1 : 0] << 8) | ((uint32_t)q[left > 2 ? 2 : 0] << 16) |
+                                     ((uint32_t)q[left > 3 ? 3 : 0] << 24);
+                        } else if (Y8) {  // four texels = four bytes, converted on the way in (rows are 4-byte aligned here)
+                            v[u] = __builtin_bit_cast(uint4, buffer_load_format_xyzw(frame_unorm, off, 0, 0));
+                        } else {  // RGBA quad; in the general variant (UA) the last quad of a row may run into the next row: those
+                                  // texels land in columns >= w, which nothing ever uses
+                            v[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(frame_rsrc, off, 0, 0));
+                        }
                     }
                     gy_w += rpp;
                     off_w -= off_step;
@@ -319,8 +359,13 @@
                     }
                 }
             }
+            if (!TILED && ly_base == 0 && rides) tab_dst[tid - tab_t0] = v[U - 1];  // the thread has no row past this round
         }
+        tab_first = ride;
     }
+    // a shape without a free slot (a level so narrow that not every thread stages a row in the first round): the whole table, behind the staging
+    if (tab_ready && !tab_first)
+        for (int k = tid; k < n_pieces; k += NT) tab_dst[k] = tab_src[k];
     // TILED: tile 0 of several does the band's blur, whose row constants read three grey texels per row that lie beyond its
     // own columns: the row's last one and the two that pass 1 lerps at the last column (SURVEY.md Q11).  Same conversion
     // as the staged rows (CRD-1..3); rows outside the level are never used.
@@ -393,28 +438,11 @@
         blur_k2[tid] = make_float4(base2, b2, b3, finish(base2, c1, b2, b3));
     }
 
-    // ---- blur column table (the last threads of the workgroup, so that wave 0 is not doing both) ----
-    if ((geo.phase_mask & 8u) && blur_tile)
-    for (int c = NT - 1 - tid; c < (int)geo.n_var; c += NT) {  // one entry per thread while n_var <= NT (it is about 0.12 w)
-        const int x = (int)geo.blur_q + c, P = (int)geo.blur_p;
-        const BlurTap t2 = blur_tap((uint32_t)x, (uint32_t)w, kBlurOff[1], geo.wq);
-        BlurCol e;
-        e.f2 = t2.f;
-        e.pad = 0u;
-        if (t2.i0 < P) {
-            e.a0 = 0xffffu, e.a1 = 0u, e.fa = 0.0f;
-        } else {
-            const BlurTap t = blur_tap((uint32_t)t2.i0, (uint32_t)w, kBlurOff[1], geo.wq);
-            e.a0 = (uint16_t)t.i0, e.a1 = (uint16_t)t.i1, e.fa = t.f;
-        }
-        if (t2.i1 < P) {
-            e.b0 = 0xffffu, e.b1 = 0u, e.fb = 0.0f;
-        } else {
-            const BlurTap t = blur_tap((uint32_t)t2.i1, (uint32_t)w, kBlurOff[1], geo.wq);
-            e.b0 = (uint16_t)t.i0, e.b1 = (uint16_t)t.i1, e.fb = t.f;
-        }
-        blur_cols[c] = e;
-    }
+    // ---- blur column table, where phase A brought none: a tiled level, a launch without geo.blur_tab (the last threads of the
+    // workgroup, so that wave 0 is not doing both) ----
+    if ((geo.phase_mask & 8u) && blur_tile && !tab_ready)
+    for (int c = NT - 1 - tid; c < (int)geo.n_var; c += NT)  // one entry per thread while n_var <= NT (it is about 0.12 w)
+        blur_cols[c] = blur_col_entry((int)geo.blur_q + c, w, (int)geo.blur_p, geo.wq);
 
     // Phases B (FAST) and C (mip + blur) only share the read-only grey rows.
     auto phase_B = [&](auto first_round, const uint32_t round) {

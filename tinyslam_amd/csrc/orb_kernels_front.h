@@ -52,6 +52,7 @@ constexpr int kFrontMaxWidthTiled = 16384;  // widest level 0 of the fused liter
 constexpr int kFrontTileW = 1280;           // preferred tile width there: the shape the kernel is tuned on (16 rows x 1280 columns)
 constexpr int kLdsPad = 8;           // halfs of padding left of column 0
 
+struct BlurCol;  // below
 struct FrontGeom {
     uint32_t lvl;       // pyramid level handled by this launch
     uint32_t rows;      // band height (one of kFrontBandHeights)
@@ -88,6 +89,10 @@ struct FrontGeom {
     uint32_t oob;         // OrbOptions::oob_policy (kOobZero / kOobClamp / kOobUmin); phase A of the levels >= 1 follows it through OOBK
     float wq;             // OrbOptions::sampler_weight_bits as 2^bits (0: exact lerp weights), for blur_tap()
     uint32_t fp;          // OrbOptions::fp_contract (kFp*), for the record: the luminance's form and the blur's are the template parameter FPF
+    const BlurCol* blur_tab;  // level 0: its BlurCol table, built once per program (k_blur_col_table): blur_col_pieces(n_var) pieces of 16
+                              // bytes that a band copies into LDS during phase A.  Null: the band builds the table itself (a tiled level,
+                              // whose tile 0 shares that storage by other rules; the levels above 0, which do not read it; launches that
+                              // bring none).  Not a shape field
 };
 
 // Tap positions of one column x >= blur_q of the literal blur (phase C): pass 2 at x lerps pass 1 at columns j0, j1
@@ -100,6 +105,39 @@ struct __attribute__((aligned(8))) BlurCol {
     uint32_t pad;
 };
 static_assert(sizeof(BlurCol) == 24, "BlurCol layout");
+
+// The table entry of column x (>= blur_q) of a level w wide; P = blur_p.  The one text of the entries: k_blur_col_table evaluates it
+// once per program for level 0 on full-width bands, a band of any other level (and of any launch without a table) per band.
+__device__ __forceinline__ BlurCol blur_col_entry(int x, int w, int P, float wq) {
+    const BlurTap t2 = blur_tap((uint32_t)x, (uint32_t)w, kBlurOff[1], wq);
+    BlurCol e;
+    e.f2 = t2.f;
+    e.pad = 0u;
+    if (t2.i0 < P) {
+        e.a0 = 0xffffu, e.a1 = 0u, e.fa = 0.0f;
+    } else {
+        const BlurTap t = blur_tap((uint32_t)t2.i0, (uint32_t)w, kBlurOff[1], wq);
+        e.a0 = (uint16_t)t.i0, e.a1 = (uint16_t)t.i1, e.fa = t.f;
+    }
+    if (t2.i1 < P) {
+        e.b0 = 0xffffu, e.b1 = 0u, e.fb = 0.0f;
+    } else {
+        const BlurTap t = blur_tap((uint32_t)t2.i1, (uint32_t)w, kBlurOff[1], wq);
+        e.b0 = (uint16_t)t.i0, e.b1 = (uint16_t)t.i1, e.fb = t.f;
+    }
+    return e;
+}
+// The table is copied into LDS in 16-byte pieces (orb_front_body.inc, phase A): the program's buffer holds a whole number of
+// pieces (the host zeroes what an odd count leaves of the last one).
+__host__ __device__ constexpr uint32_t blur_col_pieces(uint32_t n_var) { return (n_var * (uint32_t)sizeof(BlurCol) + 15u) / 16u; }
+// One level's table, once per program (orb_program_create, beside k_rot_table): out[c] = the entry of column blur_q + c, c < n_var.
+// (A template so that only the unit that launches it, orb_api.hip, emits it: every unit that instantiates k_front includes this header.)
+template <int = 0>
+__global__ __launch_bounds__(64) void k_blur_col_table(uint32_t w, uint32_t blur_p, uint32_t blur_q, uint32_t n_var, float wq,
+                                                              BlurCol* __restrict__ out) {
+    const uint32_t c = blockIdx.x * 64u + threadIdx.x;
+    if (c < n_var) out[c] = blur_col_entry((int)(blur_q + c), (int)w, (int)blur_p, wq);
+}
 
 // ---- compile-time geometry (k_front's last template parameter) ----
 // Every workgroup of a level recomputes what depends on the level's shape alone -- item-index reciprocals, the BlurCol table's divisions

@@ -40,6 +40,8 @@ CORNER_DTYPE = np.dtype([("x", "<u4"), ("y", "<u4"), ("angle", "<u4"), ("octave"
 MATCH_DTYPE = np.dtype([("index", "<u4"), ("distance", "<u2"), ("second", "<u2")])
 ORB_MATCH_NONE = 0xFFFFFFFF
 DESCRIPTOR_DTYPE = np.dtype([("bits", "u1", (32,))])
+# csrc/orb_kernels_front.h BlurCol, the fractions as bit patterns (OrbProgram.blur_col_table)
+BLUR_COL_DTYPE = np.dtype([("a0", "<u2"), ("a1", "<u2"), ("b0", "<u2"), ("b1", "<u2"), ("fa", "<u4"), ("fb", "<u4"), ("f2", "<u4"), ("pad", "<u4")])
 # geometric verification (orb_verify_consecutive): OrbPairModel (64 B) and its status codes
 VERIFY_MODEL_DTYPE = np.dtype([("h", "<f4", (9,)), ("candidates", "<u4"), ("inliers", "<u4"), ("hypothesis", "<u4"),
                                ("status", "<u4"), ("reserved", "<u4", (3,))])
@@ -92,7 +94,7 @@ EXPORTS = [
     "orb_write_input_image", "orb_set_threshold", "orb_extract_corners", "orb_read_corners",
     "orb_read_descriptors", "orb_extract_batch_device", "orb_extract_batch_host", "orb_batch_sync",
     "orb_batch_counts", "orb_batch_read", "orb_batch_select_output", "orb_batch_device_buffers", "orb_level_size",
-    "orb_debug_read_plane", "orb_debug_f32_to_f16", "orb_debug_angle_code", "orb_debug_rot_table", "orb_profile_enable",
+    "orb_debug_read_plane", "orb_debug_f32_to_f16", "orb_debug_angle_code", "orb_debug_rot_table", "orb_debug_blur_col_table", "orb_profile_enable",
     "orb_profile_reset", "orb_profile_get", "orb_synth_frames_device", "orb_copy_to_host", "orb_debug_stamps",
     "orb_match_consecutive", "orb_match_read", "orb_corner_level0_xy",
     "orb_batch_read_all", "orb_batch_compact_device", "orb_host_alloc", "orb_host_free", "orb_stream_sync",
@@ -287,6 +289,7 @@ def load_library(path=None):
     L.orb_debug_f32_to_f16.argtypes = [vp, vp, vp, sz]
     L.orb_debug_angle_code.argtypes = [vp, vp, vp, vp, sz]
     L.orb_debug_rot_table.argtypes = [vp, vp, sz, vp, vp]
+    L.orb_debug_blur_col_table.argtypes = [vp, u32, vp, sz, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.orb_match_consecutive.argtypes = [vp, u32, vp]
     L.orb_match_read.argtypes = [vp, u32, vp, ctypes.c_size_t]
     L.orb_verify_consecutive.argtypes = [vp, u32, ctypes.POINTER(_VerifyParams), vp]
@@ -929,6 +932,17 @@ class OrbProgram:
         out = np.zeros((codes.value, 64, 4, 2), dtype=np.int16)
         self._check(self._lib.orb_debug_rot_table(self._handle(), _ptr(out), out.size, None, None))
         return out, pitch.value
+
+    def blur_col_table(self, level):
+        """k_front's ready-made blur column table of one level, as the device built it -> (entries (BLUR_COL_DTYPE; empty: the level's
+        bands build their own), blur_p, blur_q)."""
+        fn = self._lib.orb_debug_blur_col_table
+        n, p, q = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(fn(self._handle(), level, None, 0, ctypes.byref(n), ctypes.byref(p), ctypes.byref(q)))
+        out = np.zeros(n.value, dtype=BLUR_COL_DTYPE)
+        if n.value:
+            self._check(fn(self._handle(), level, _ptr(out), out.size, None, None, None))
+        return out, p.value, q.value
 
     def profile_enable(self, on=True):
         self._check(self._lib.orb_profile_enable(self._handle(), 1 if on else 0))
