@@ -68,3 +68,16 @@ with orb.OrbProgram(cfg) as prog:  # == OrbProgram { config, .. }.init() in the 
               % (int(frame1["origin"]), int(frame1["status"]), float(frame1["scale"]), int(((world["flags"] & orb.ORB_POINT_GOOD) != 0).sum())))
     else:
         print("frame 0 -> 1: no fundamental matrix (status %d), no band search and no pose" % int(fmodel["status"]))
+
+    # --- place recognition across batches (meant for the intended mode) -----------------------------------
+    # batch A: keep the signatures of the frames worth remembering (here both; a SLAM front-end keeps its keyframes') ...
+    prog.place_frames(2, min_gap=1)
+    kept = np.stack([prog.place_signature(f) for f in range(2)])        # uint8 (2, 65536) at the default 16 bits x 8 tables
+    # ... batch B, later: the same two scenes in the other order, with the kept signatures as the database
+    prog.extract_batch_host(frames[::-1].copy())
+    prog.place_frames(2, db=kept, min_gap=1)
+    for f, row in enumerate(prog.place_read(0, 2)):
+        best, who = row["best"][0], int(row["best"][0]["frame"])
+        where = ("entry %d of the database" % (who & 0x7FFFFFFF) if who & orb.ORB_PLACE_DB
+                 else "frame %d of this batch" % who) if row["n"] else "nothing"
+        print("batch B frame %d: %d of its %d signature bits are shared with %s" % (f, int(best["score"]), int(row["bits_set"]), where))

@@ -881,6 +881,68 @@ int orb_track_read(OrbProgram *p, uint32_t frame, OrbTrack *dst, size_t n);
  * any call. */
 int orb_track_frames(OrbProgram *p, OrbTrackFrame *dst, size_t n);
 
+/* ---- loop candidates by descriptor-signature overlap (NOT in the reference; definition PL-1..PL-6 in DESIGN.md section 25) ----
+ * Place recognition: which earlier frames, of this batch or of a database kept from earlier batches, show what frame f shows.
+ * A descriptor is 16 little-endian 16-bit halves; table t < tables gives a record the key (half t) & (2^bits - 1).  A frame's
+ * signature is `tables` bitmaps of 2^bits bits -- bit `key` of bitmap t (bit key & 7 of byte t * 2^bits / 8 + (key >> 3)) is set
+ * iff one of the frame's stored records, the first min(count, max_features), has that key in table t --, sig_bytes =
+ * tables * 2^bits / 8 bytes in all, and score(a, b) the number of bits two signatures share.  Ids: database entry e is e, batch
+ * frame g is n_db + g.  For query f every database entry is eligible, and batch frame g iff g + min_gap <= f (with
+ * ORB_PLACE_KEYFRAMES: and g is a keyframe of the last orb_track_consecutive).  An eligible id is a candidate iff score >=
+ * max(min_score, 1) and 1000 score >= min_permille bits_set(f); the row lists the min(candidates, top) candidates with the
+ * greatest (score << 32) | (0xffffffff - id), greatest first, so equal scores go to the smaller id.  Integer arithmetic only: a
+ * CPU restatement gives the same bytes.  The descriptors of the literal mode change under translation (README, the verifier's
+ * paragraph) and recognise nothing here: like the verifier, the stage is meant for ORB_FLAG_INTENDED programs.  Nothing is fed
+ * back into another stage. */
+typedef struct {            /* zero-initialised = the defaults */
+    uint32_t bits;          /* key width, 8..16 (0: 16) */
+    uint32_t tables;        /* 1..16 (0: 8); tables << bits must not exceed 8 * ORB_PLACE_SIG_BYTES_MAX */
+    uint32_t min_gap;       /* >= 1 (0: 32) */
+    uint32_t top;           /* 1..8 (0: 4) */
+    uint32_t min_score;     /* 0: 1 */
+    uint32_t min_permille;  /* 0..1000 */
+    uint32_t flags;         /* ORB_PLACE_KEYFRAMES (1) or 0 */
+    uint32_t reserved;      /* must be 0 */
+} OrbPlaceParams;           /* 32 bytes */
+
+#define ORB_PLACE_KEYFRAMES 1u           /* only keyframes of the last orb_track_consecutive are eligible batch frames */
+#define ORB_PLACE_DB 0x80000000u         /* OrbPlaceCandidate::frame of database entry e is ORB_PLACE_DB | e */
+#define ORB_PLACE_SIG_BYTES_MAX 65536u
+#define ORB_PLACE_DB_MAX 1024u
+
+typedef struct { uint32_t frame; uint32_t score; } OrbPlaceCandidate;   /* 8 bytes */
+
+typedef struct {
+    uint32_t keypoints;     /* min(count, max_features) */
+    uint32_t bits_set;      /* set bits of the frame's signature */
+    uint32_t eligible;      /* eligible ids, database entries included */
+    uint32_t candidates;    /* of them candidates */
+    uint32_t n;             /* min(candidates, top) */
+    uint32_t reserved[3];   /* 0 */
+    OrbPlaceCandidate best[8];  /* the first n: a batch frame g as g, a database entry e as ORB_PLACE_DB | e; the rest ORB_MATCH_NONE, score 0 */
+} OrbPlaceRow;              /* 96 bytes */
+
+/* Signatures and candidate rows of frames 0 .. n_frames - 1 of the last batch and the current output set (params NULL: the
+ * defaults).  db_host: n_db signatures of sig_bytes each, row after row, made by earlier calls with the same bits and tables
+ * (orb_place_signature); NULL with n_db 0.  ORB_EINVAL for a NULL program, a parameter out of range, a reserved word that is
+ * not 0, unknown flags, n_db above ORB_PLACE_DB_MAX, exactly one of db_host and n_db zero, or n_frames not in 1 .. the frames of
+ * the last batch; ORB_ESTATE when the program holds no batch, and with ORB_PLACE_KEYFRAMES unless the last
+ * orb_track_consecutive is of the current batch and output set and tracked at least n_frames frames.  Asynchronous on `stream`
+ * (NULL: as orb_match_guided chooses; the call does not change it), ordered behind the last call of its own and, with
+ * ORB_PLACE_KEYFRAMES, the last orb_track_consecutive when they ran on another stream; orb_track_consecutive waits for a place
+ * call on another stream before it overwrites its frame records.  The database is copied to the device on the call's stream
+ * and the call waits on the host for that copy alone: db_host may be freed or overwritten as soon as it returns.  Result
+ * buffers of its own (allocated by the first call: max_batch + ORB_PLACE_DB_MAX signatures of ORB_PLACE_SIG_BYTES_MAX and a
+ * score matrix): no other stage's results are ever written. */
+int orb_place_frames(OrbProgram *p, uint32_t n_frames, const OrbPlaceParams *params, const uint8_t *db_host, uint32_t n_db, void *stream);
+/* Copy up to n OrbPlaceRow records, frames `frame`, frame + 1, ... of the last orb_place_frames call clipped to its frames, to
+ * the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a frame outside its frames or rows NULL with n > 0. */
+int orb_place_read(OrbProgram *p, uint32_t frame, OrbPlaceRow *rows, size_t n);
+/* Copy the first min(n_bytes, sig_bytes) bytes of the signature of frame `frame` as the last orb_place_frames call built it
+ * (synchronises): what a caller keeps, for a keyframe say, and hands back as a row of db_host in a later batch.  ORB_ESTATE
+ * before any call, ORB_EINVAL for a frame outside its frames or dst NULL with n_bytes > 0. */
+int orb_place_signature(OrbProgram *p, uint32_t frame, uint8_t *dst, size_t n_bytes);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

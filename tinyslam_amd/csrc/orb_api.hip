@@ -36,6 +36,7 @@
 #include "orb_kernels_landmark.h"
 #include "orb_kernels_bridge.h"
 #include "orb_kernels_adjust.h"
+#include "orb_kernels_place.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -71,7 +72,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_PLACE, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -115,6 +116,8 @@ constexpr StageInfo kStages[ST_COUNT] = {
      1u << ST_MATCH |     // d_matches: the views of a landmark
      1u << ST_TRAJ |      // d_jframe
      1u << ST_LANDMARK},  // d_mland
+    {"place_frames", "place_read",
+     1u << ST_TRACK},     // d_tframe: the keyframe column (ORB_PLACE_KEYFRAMES)
 };
 static_assert(kStages[ST_COUNT - 1].name != nullptr, "a row of kStages for every StageId");
 
@@ -144,6 +147,9 @@ static_assert(sizeof(OrbBridgePose) == kBrOutWords * sizeof(uint32_t) && sizeof(
               "bridge layouts");
 static_assert(sizeof(OrbAdjustedPose) == kBaPoseWords * sizeof(uint32_t) && sizeof(OrbAdjustParams) == 32 && kBaFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose),
               "adjust layouts");
+static_assert(sizeof(OrbPlaceRow) == kPlaceRowWords * sizeof(uint32_t) && sizeof(OrbPlaceParams) == 32 && sizeof(OrbPlaceCandidate) == 8 &&
+                  sizeof(OrbTrackFrame) == kPlaceFrameWords * sizeof(uint32_t) && offsetof(OrbTrackFrame, keyframe) == kPlaceKeyframeWord * sizeof(uint32_t),
+              "place layouts");
 
 // The last call of a stage
 struct Stage {
@@ -271,6 +277,14 @@ struct OrbProgram {
     float4* d_ax = nullptr;               // [max_batch][max_features] the current point of every landmark slot
     uint32_t* d_aowner = nullptr;         // [max_batch][max_features] the owner of every keypoint slot
     float4* d_aland = nullptr;            // [max_batch][max_features][2] OrbLandmark
+    // orb_place_frames (orb_kernels_place.h)
+    uint32_t* d_psig = nullptr;           // [max_batch][sig_bytes of the last call / 4] signatures (room for ORB_PLACE_SIG_BYTES_MAX each)
+    uint32_t* d_pdb = nullptr;            // [n_db][the same] the caller's database (room for ORB_PLACE_DB_MAX of ORB_PLACE_SIG_BYTES_MAX)
+    uint32_t* d_ptbits = nullptr;         // [max_batch][16] set bits per table
+    uint32_t* d_pscore = nullptr;         // [slices][n_frames][n_db + n_frames] partial scores (room for max_batch x (ORB_PLACE_DB_MAX + max_batch))
+    uint32_t* d_prow = nullptr;           // [max_batch] OrbPlaceRow
+    hipEvent_t place_copied = nullptr;    // behind the database's copy of the last call
+    uint32_t place_sig_bytes = 0;         // of the last call
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -485,6 +499,13 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&p->d_ax, B * cap * sizeof(float4));
         add(&p->d_aowner, B * cap * sizeof(uint32_t));
         add(&p->d_aland, B * cap * sizeof(OrbLandmark));
+        break;
+    case ST_PLACE:
+        add(&p->d_psig, B * (size_t)ORB_PLACE_SIG_BYTES_MAX);
+        add(&p->d_pdb, (size_t)ORB_PLACE_DB_MAX * ORB_PLACE_SIG_BYTES_MAX);
+        add(&p->d_ptbits, B * kPlaceMaxTables * sizeof(uint32_t));
+        add(&p->d_pscore, B * (ORB_PLACE_DB_MAX + B) * sizeof(uint32_t));
+        add(&p->d_prow, B * sizeof(OrbPlaceRow));
         break;
     }
     return l;
@@ -1745,6 +1766,7 @@ void orb_program_destroy(OrbProgram* p) {
         if (p->stage[st].done) (void)hipEventDestroy(p->stage[st].done);
     }
     if (p->single_done_ev) (void)hipEventDestroy(p->single_done_ev);
+    if (p->place_copied) (void)hipEventDestroy(p->place_copied);
     if (p->h_count) (void)hipHostFree(p->h_count);
     if (p->d_single_done) (void)hipFree(p->d_single_done);
     if (p->h_corners) (void)hipHostFree(p->h_corners);
@@ -2983,6 +3005,111 @@ int orb_adjust_consecutive(OrbProgram* p, uint32_t n_frames, const OrbAdjustPara
 
 int orb_adjust_read(OrbProgram* p, uint32_t frame, OrbAdjustedPose* pose, OrbLandmark* landmarks, size_t n) {
     return p ? read_stage(p, ST_ADJUST, frame, pose, p->d_apose, sizeof(OrbAdjustedPose), landmarks, p->d_aland, sizeof(OrbLandmark), n) : ORB_EINVAL;
+}
+
+int orb_place_frames(OrbProgram* p, uint32_t n_frames, const OrbPlaceParams* params, const uint8_t* db_host, uint32_t n_db, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbPlaceParams g{};
+    if (params) g = *params;
+    if (g.reserved || (g.flags & ~ORB_PLACE_KEYFRAMES)) return fail(p, ORB_EINVAL, "place_frames: reserved word must be 0, flags ORB_PLACE_KEYFRAMES or 0");
+    if (!g.bits) g.bits = 16u;
+    if (!g.tables) g.tables = 8u;
+    if (!g.min_gap) g.min_gap = 32u;
+    if (!g.top) g.top = 4u;
+    if (!g.min_score) g.min_score = 1u;
+    if (g.bits < 8u || g.bits > 16u || g.tables > 16u || g.top > 8u || g.min_permille > 1000u)
+        return fail(p, ORB_EINVAL, "place_frames: bits must be 8..16, tables 1..16, top 1..8, min_permille 0..1000");
+    if (((size_t)g.tables << g.bits) > 8u * (size_t)ORB_PLACE_SIG_BYTES_MAX)
+        return fail(p, ORB_EINVAL, "place_frames: tables << bits must not exceed %u bits", 8u * ORB_PLACE_SIG_BYTES_MAX);
+    if (n_db > ORB_PLACE_DB_MAX || (db_host != nullptr) != (n_db != 0u))
+        return fail(p, ORB_EINVAL, "place_frames: n_db must be 0..%u, and db_host NULL exactly when it is 0", ORB_PLACE_DB_MAX);
+    if (!p->last_batch) return fail(p, ORB_ESTATE, "place_frames before a batch");
+    if (n_frames < 1u || n_frames > p->last_batch) return fail(p, ORB_EINVAL, "place_frames: need 1..%u frames of the last batch", p->last_batch);
+    const bool keyed = (g.flags & ORB_PLACE_KEYFRAMES) != 0u;
+    const uint32_t reads = keyed ? 1u << ST_TRACK : 0u;  // the track stage is waited for only when its keyframes are read
+    if (keyed) {
+        if (int rc = stages_fresh(p, ST_PLACE, reads)) return rc;
+        if (p->stage[ST_TRACK].extent < n_frames)
+            return fail(p, ORB_ESTATE, "place_frames: %u frames, the last orb_track_consecutive tracked %u", n_frames, p->stage[ST_TRACK].extent);
+    }
+    const size_t sig_bytes = ((size_t)g.tables << g.bits) / 8u;
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_PLACE, stream, reads, &s)) return rc;
+    if (n_db) {  // the caller's rows are the caller's again when this returns: the copy alone is waited for
+        if (!p->place_copied) HIP_TRY(p, hipEventCreateWithFlags(&p->place_copied, hipEventDisableTiming));
+        HIP_TRY(p, hipMemcpyAsync(p->d_pdb, db_host, (size_t)n_db * sig_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(p, hipEventRecord(p->place_copied, s));
+    }
+    PlaceArgs a{};
+    a.counts = p->d_counts;
+    a.desc = p->d_desc;
+    a.cap = p->cfg.max_features;
+    a.n_frames = n_frames;
+    a.bits = g.bits;
+    a.tables = g.tables;
+    a.words = (uint32_t)(sig_bytes / 4u);
+    a.n_db = n_db;
+    a.min_gap = g.min_gap;
+    a.top = g.top;
+    a.min_score = g.min_score;
+    a.min_permille = g.min_permille;
+    a.keyframe = keyed ? p->d_tframe : nullptr;
+    a.sig = p->d_psig;
+    a.db = p->d_pdb;
+    a.tbits = p->d_ptbits;
+    a.score = p->d_pscore;
+    a.rows = p->d_prow;
+    const uint32_t n_ids = n_db + n_frames;
+    // slices of a signature's words (orb_kernels_place.h): whole chunks, as many as the score buffer has room for beside each other
+    const dim3 tiles((n_ids + kPlaceTile - 1u) / kPlaceTile, (n_frames + kPlaceTile - 1u) / kPlaceTile);
+    const size_t room = (size_t)p->max_batch * (ORB_PLACE_DB_MAX + p->max_batch) / ((size_t)n_frames * n_ids);
+    const uint32_t chunks = (a.words + kPlaceChunk - 1u) / kPlaceChunk;
+    const uint32_t wanted = std::max(1u, kPlaceWantedGroups / (tiles.x * tiles.y));
+    const uint32_t most = (uint32_t)std::min<size_t>(std::min<size_t>(kPlaceMaxSlices, room), std::min(chunks, wanted));
+    const uint32_t per = (chunks + most - 1u) / most;
+    a.slice_words = per * kPlaceChunk;
+    a.slices = (chunks + per - 1u) / per;
+    hipLaunchKernelGGL(k_place_sign, dim3(g.tables, n_frames), dim3(kPlaceSignThreads), 0, s, a);
+    hipLaunchKernelGGL(k_place_score, dim3(tiles.x, tiles.y, a.slices), dim3(kPlaceScoreThreads), 0, s, a);
+    hipLaunchKernelGGL(k_place_select, dim3(n_frames), dim3(kPlaceSelectThreads), 0, s, a);
+    if (int rc = stage_end(p, ST_PLACE, s, n_frames)) return rc;  // p->last_stream stays, as after a guided call
+    p->place_sig_bytes = (uint32_t)sig_bytes;
+    if (n_db) HIP_TRY(p, hipEventSynchronize(p->place_copied));
+    return ORB_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// What orb_place_read and orb_place_signature share: the state and argument rules, and the wait for the stage's event
+int place_read_open(OrbProgram* p, const char* who, uint32_t frame, const void* dst, size_t n) {
+    const Stage& last = p->stage[ST_PLACE];
+    if (!last.extent) return fail(p, ORB_ESTATE, "%s before place_frames", who);
+    if (frame >= last.extent || (!dst && n)) return fail(p, ORB_EINVAL, "%s: frame %u of %u, or the destination of %zu elements is NULL", who, frame, last.extent, n);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    return ORB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orb_place_read(OrbProgram* p, uint32_t frame, OrbPlaceRow* rows, size_t n) {
+    if (!p) return ORB_EINVAL;
+    if (int rc = place_read_open(p, "place_read", frame, rows, n)) return rc;
+    n = std::min<size_t>(n, p->stage[ST_PLACE].extent - frame);
+    if (n) HIP_TRY(p, hipMemcpy(rows, p->d_prow + (size_t)frame * kPlaceRowWords, n * sizeof(OrbPlaceRow), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_place_signature(OrbProgram* p, uint32_t frame, uint8_t* dst, size_t n_bytes) {
+    if (!p) return ORB_EINVAL;
+    if (int rc = place_read_open(p, "place_signature", frame, dst, n_bytes)) return rc;
+    n_bytes = std::min<size_t>(n_bytes, p->place_sig_bytes);
+    if (n_bytes) HIP_TRY(p, hipMemcpy(dst, (const uint8_t*)p->d_psig + (size_t)frame * p->place_sig_bytes, n_bytes, hipMemcpyDeviceToHost));
+    return ORB_OK;
 }
 
 int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams* params, void* stream) {

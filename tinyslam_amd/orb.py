@@ -87,6 +87,15 @@ ORB_TRACK_VERIFIED, ORB_TRACK_GUIDED, ORB_TRACK_MATCHED = 0, 1, 2
 TRACK_DTYPE = np.dtype([("prev", "<u4"), ("next", "<u4"), ("head_index", "<u4"), ("head_frame", "<u2"), ("tail_frame", "<u2")])
 TRACK_FRAME_DTYPE = np.dtype([("keypoints", "<u4"), ("links_in", "<u4"), ("links_out", "<u4"), ("keyframe", "<u4"),
                               ("ref_keyframe", "<u4"), ("shared", "<u4"), ("reserved", "<u4", (2,))])
+# loop candidates by descriptor-signature overlap (orb_place_frames): OrbPlaceCandidate (8 B), OrbPlaceRow (96 B),
+# the flag of OrbPlaceParams, the mark of a database entry in a row, and the two capacities
+PLACE_CANDIDATE_DTYPE = np.dtype([("frame", "<u4"), ("score", "<u4")])
+PLACE_ROW_DTYPE = np.dtype([("keypoints", "<u4"), ("bits_set", "<u4"), ("eligible", "<u4"), ("candidates", "<u4"), ("n", "<u4"),
+                            ("reserved", "<u4", (3,)), ("best", PLACE_CANDIDATE_DTYPE, (8,))])
+ORB_PLACE_KEYFRAMES = 1
+ORB_PLACE_DB = 0x80000000
+ORB_PLACE_SIG_BYTES_MAX = 65536
+ORB_PLACE_DB_MAX = 1024
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -113,6 +122,7 @@ EXPORTS = [
     "orb_landmarks_consecutive", "orb_landmarks_read",
     "orb_bridge_consecutive", "orb_bridge_read",
     "orb_adjust_consecutive", "orb_adjust_read",
+    "orb_place_frames", "orb_place_read", "orb_place_signature",
 ]
 
 
@@ -210,6 +220,16 @@ class _AdjustParams(ctypes.Structure):
 
 
 OrbAdjustParams = _AdjustParams
+
+
+class _PlaceParams(ctypes.Structure):
+    """OrbPlaceParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("bits", ctypes.c_uint32), ("tables", ctypes.c_uint32), ("min_gap", ctypes.c_uint32), ("top", ctypes.c_uint32),
+                ("min_score", ctypes.c_uint32), ("min_permille", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+OrbPlaceParams = _PlaceParams
 
 
 class _TrackParams(ctypes.Structure):
@@ -312,6 +332,9 @@ def load_library(path=None):
     L.orb_bridge_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_adjust_consecutive.argtypes = [vp, u32, ctypes.POINTER(_AdjustParams), vp]
     L.orb_adjust_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_place_frames.argtypes = [vp, u32, ctypes.POINTER(_PlaceParams), vp, u32, vp]
+    L.orb_place_read.argtypes = [vp, u32, vp, sz]
+    L.orb_place_signature.argtypes = [vp, u32, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -845,6 +868,40 @@ class OrbProgram:
         lm = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=LANDMARK_DTYPE)
         self._check(self._lib.orb_adjust_read(self._handle(), frame, _ptr(rec), _ptr(lm) if len(lm) else None, len(lm)))
         return rec, lm
+
+    def place_frames(self, n_frames, db=None, stream=None, bits=0, tables=0, min_gap=0, top=0, min_score=0, min_permille=0, flags=0,
+                     reserved=0):
+        """Loop candidates of frames 0 .. n_frames - 1 of the last batch (not in the reference):
+        a frame's signature is `tables` (0: 8) bitmaps of 2^bits (0: 16) bits over the low bits of its descriptors' 16-bit
+        halves, a score the bits two signatures share, and frame f's candidates the entries of `db` (uint8 (n_db, sig_bytes):
+        signatures kept from earlier calls with the same bits and tables; None: no database) and the frames g <= f - min_gap
+        (0: 32) -- keyframes of the last track_consecutive only with ORB_PLACE_KEYFRAMES -- with score >= min_score (0: 1) and
+        1000 score >= min_permille bits_set; the best `top` (0: 4; at most 8) are kept.  Meant for ORB_FLAG_INTENDED programs.
+        Asynchronous on `stream` (None: as match_guided chooses); `db` may be reused as soon as the call returns."""
+        prm = _PlaceParams(bits, tables, min_gap, top, min_score, min_permille, flags, reserved)
+        n_db = 0
+        if db is not None:
+            db = np.ascontiguousarray(db, dtype=np.uint8)
+            if db.ndim != 2:
+                raise OrbError(ORB_EINVAL, "place_frames: db must be a (n_db, sig_bytes) array")
+            n_db = db.shape[0]
+        self._check(self._lib.orb_place_frames(self._handle(), n_frames, ctypes.byref(prm), _ptr(db) if n_db else None, n_db,
+                                               ctypes.c_void_p(stream) if stream else None))
+        self._place = (n_frames, ((tables or 8) << (bits or 16)) // 8)
+
+    def place_read(self, first, n):
+        """PLACE_ROW_DTYPE records of frames first .. first + n - 1 of the last place_frames (clipped to its frames) --
+        synchronises."""
+        out = np.zeros(max(min(n, getattr(self, "_place", (first + n, 0))[0] - first), 0), dtype=PLACE_ROW_DTYPE)
+        self._check(self._lib.orb_place_read(self._handle(), first, _ptr(out) if len(out) else None, len(out)))
+        return out
+
+    def place_signature(self, frame):
+        """The signature of `frame` as the last place_frames built it, uint8 (sig_bytes,): what a caller keeps and hands back
+        as a row of `db` in a later batch -- synchronises."""
+        out = np.zeros(getattr(self, "_place", (0, ORB_PLACE_SIG_BYTES_MAX))[1], dtype=np.uint8)
+        self._check(self._lib.orb_place_signature(self._handle(), frame, _ptr(out), len(out)))
+        return out
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
