@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "../../include/tinyorb.h"
-#include "orb_front_launch.h"
+#include "orb_plan.h"
 #include "orb_kernels_fused.h"
 #include "orb_kernels_brief.h"
 #include "orb_kernels_intended.h"
@@ -209,38 +209,21 @@ struct OrbProgram {
     hipEvent_t pack_event[2] = {nullptr, nullptr};
     uint32_t pack_n[2] = {0u, 0u};
     uint32_t cur_set = 0;
-    Pyramid pyr{};
-    size_t frame_bytes = 0;
-    uint32_t max_batch = 1;
+    ProgramPlan plan;  // which pipeline and its geometry (orb_plan.h): written once by orb_program_create, only read afterwards
+    PlanEnv env;       // the create-time environment switches, read once (read_plan_env)
     float threshold = 0.f;
-    uint32_t arc = 12;  // FAST arc length (opt-in extension, 9..16)
-    uint32_t oob = kOobZero;  // OrbOptions::oob_policy
-    float wq = 0.0f;          // OrbOptions::sampler_weight_bits as 2^bits (0: exact weights)
     // opt-in NMS (staged pipeline): provisional detections + score planes
-    uint32_t cap_prov = 0;
     uint32_t* d_prov_counts = nullptr;
     CornerData* d_prov = nullptr;
     float* d_prov_scores = nullptr;
     float* d_score_planes = nullptr;
-    ScoreLayout score_layout{};
-    // "intended" mode: survivors of the NMS with their scores, input of the top-K cut
-    bool intended = false;
-    bool input_y8 = false;  // ORB_FLAG_INPUT_Y8: frames are one byte per pixel
-    // fused "intended" pipeline (orb_kernels_intended.h): tile slots, their segments (record + score), the cut
-    bool fused_i = false;
-    bool igauss_fused = false;  // fused_i: k_front_i blurs its own tile (phase G); false: k_gauss over the stored grey plane (TINYORB_I_GAUSS_KERNEL=1)
-    bool igrey_stored = false;  // fused_i: k_front_i<true> stores the level-0 grey plane (k_gauss or k_mip reads it)
-    bool fused_x = false;  // the reference's algorithm with the opt-in arc / NMS on the tile kernels
+    // fused "intended" and arc / NMS pipelines: the tile slots' segments (record + score), the cut
     uint32_t* d_xband_counts = nullptr;  // band-slot counters written by the blur-only k_front launches (unused)
-    RowsGeom xrows{};
-    uint32_t xband_slots = 0;  // 16-row bands per frame over all levels (grid of the blur-only launches)
-    IBriefGeom itiles{};
     CornerData* d_iseg = nullptr;
     float* d_iseg_scores = nullptr;
     uint32_t* d_iseg_counts = nullptr;
     uint32_t* d_iseg_before = nullptr;
     unsigned long long* d_thr_key = nullptr;
-    uint32_t ibrief_lds = 0;
     uint64_t batch_seq = 0;    // batched calls so far (every call that sets last_batch); a stage records which one it read
     Stage stage[ST_COUNT];     // the last call of each stage after extraction
     // orb_match_consecutive (orb_kernels_match.h)
@@ -308,21 +291,13 @@ struct OrbProgram {
     uint32_t in_queue[2] = {0u, 0u};      // their slabs, oldest first
     hipEvent_t in_uploaded[2] = {nullptr, nullptr};  // behind the asynchronous upload into the slab
     bool in_async[2] = {false, false};    // the slab's image came through the copy stream: extract_corners orders its kernels behind in_uploaded
-    // environment switches (experiments and cross-checks), read once when the program is created
-    struct {
-        bool single_memcpy = false, single_split = false, single_serial = false, single_sync = false, single_block = false;
-        bool no_swizzle = false, quiet = false;
-        bool front_generic = false, front_trace = false;  // TINYORB_FRONT_GENERIC: no instance of k_front with a compile-time geometry; TINYORB_FRONT_TRACE: say which
-        int phase_mask = -1, brief_i_mask = -1, lds_pad = 0;
-    } env;
     // device-visible addresses of the pinned single-frame staging arrays (resolved once)
     uint32_t* dv_count = nullptr;
     CornerData* dv_corners = nullptr;
     CornerDescriptor* dv_desc = nullptr;
     uint16_t* d_gray = nullptr;  // max_batch x pyr.stride
     uint16_t* d_blur = nullptr;
-    uint16_t* d_blur_rowc = nullptr;  // fused path: [max_batch][row_stride] blur row constants (columns < qa)
-    uint32_t blur_qa[kMaxLevels] = {0};  // fused path: per level, columns [0, qa) of the blur plane live in d_blur_rowc
+    uint16_t* d_blur_rowc = nullptr;  // fused path: [max_batch][row_stride] blur row constants (columns < plan.blur_qa)
     uint32_t* d_counts = nullptr;  // currently selected output set (orb_batch_select_output)
     CornerData* d_corners = nullptr;
     CornerDescriptor* d_desc = nullptr;
@@ -335,14 +310,6 @@ struct OrbProgram {
     // [max_batch][brief_mask_words(max_features)] per output set, like the final lists it describes: bit i of word c of a frame = keypoint
     // 64 c + i of the final list is not flat.  k_brief_t writes every word of the frames it runs on, k_brief_nf starts from them.
     uint64_t* d_nf_mask[2] = {nullptr, nullptr};
-    BandGeom bands{};
-    RowsGeom rows{};
-    BriefTGeom brieft{};       // thread-per-keypoint BRIEF of the fused literal pipelines (plain and arc/NMS)
-    bool use_brief_t = false;
-    uint32_t band_rows_lvl[kMaxLevels] = {0};  // band height of the plain fused path per level: kFrontRows or kFrontRowsWide (chosen at create)
-    uint32_t ln_threads[kMaxLevels] = {0};     // levels >= 1: threads of a band's workgroup, kFrontThreadsLN or kFrontThreadsLNBig (chosen at create)
-    uint32_t tile_w_lvl[kMaxLevels] = {0};     // 0: full-width bands; else the level runs on column tiles of this width (k_front<..., TILED>)
-    uint32_t seg_classes = 1;  // lists per band slot of the plain fused path: 2 with k_brief_t (angle code 0 / the rest)
     uint32_t* d_pattern = nullptr;
     float* d_cos = nullptr;
     float* d_sin = nullptr;
@@ -362,7 +329,6 @@ struct OrbProgram {
     uint32_t last_batch = 0;  // frames of the last batched call
     hipStream_t last_stream = nullptr;
     bool planes_valid = false;
-    bool fused = false;
     uint32_t max_lds = 0;
     uint32_t n_cus = 256;
 
@@ -372,7 +338,6 @@ struct OrbProgram {
     double prof_ms[ORB_KERNEL_COUNT] = {0};
     uint64_t prof_n[ORB_KERNEL_COUNT] = {0};
 
-    std::string pipeline_note;  // why the staged kernels were chosen when nobody asked for them (else empty)
     std::string err;
 };
 
@@ -402,30 +367,43 @@ hipStream_t call_stream(const OrbProgram* p, void* stream) {
     return stream ? (hipStream_t)stream : (p->last_stream ? p->last_stream : p->stream);
 }
 
-struct StageBuf {
-    void** slot;   // where the stage keeps the buffer's address
+struct Buf {
+    void** slot;   // where the program keeps the buffer's address
     size_t bytes;
     bool pinned;   // host memory (hipHostMalloc); else device memory
+    bool cleared = false;        // a create-time buffer that is zeroed before any launch
+    const char* name = nullptr;  // a create-time buffer's, for the message of a failed allocation
 };
-// A stage's buffers: a list of fixed capacity on the caller's stack, which says so when a stage names more than it holds
-struct StageBufs {
-    static constexpr int kMax = 10;
-    StageBuf b[kMax];
+// A list of buffers of fixed capacity on the caller's stack, which says so when more are named than it holds
+template <int N>
+struct BufList {
+    static constexpr int kMax = N;
+    Buf b[N];
     int n = 0;
     bool overflow = false;
-    void add(void** slot, size_t bytes, bool pinned) {
-        if (n < kMax)
-            b[n++] = {slot, bytes, pinned};
+    void add(const Buf& x) {
+        if (n < N)
+            b[n++] = x;
         else
             overflow = true;
     }
 };
+using StageBufs = BufList<10>;    // a stage's (stage_buffers)
+using ProgramBufs = BufList<48>;  // orb_program_create's (program_buffers)
+
+template <int N>
+void free_bufs(const BufList<N>& l) {
+    for (int i = 0; i < l.n; i++) {
+        if (*l.b[i].slot) (void)(l.b[i].pinned ? hipHostFree(*l.b[i].slot) : hipFree(*l.b[i].slot));
+        *l.b[i].slot = nullptr;
+    }
+}
 
 // The buffers of stage `which`, named here and nowhere else: its first call fills the slots, orb_program_destroy frees them.
 StageBufs stage_buffers(OrbProgram* p, int which) {
-    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    const size_t cap = p->cfg.max_features, B = p->plan.max_batch;
     StageBufs l;
-    const auto add = [&](auto** slot, size_t bytes, bool pinned = false) { l.add((void**)slot, bytes, pinned); };
+    const auto add = [&](auto** slot, size_t bytes, bool pinned = false) { l.add(Buf{(void**)slot, bytes, pinned}); };
     switch (which) {
     case ST_MATCH:  // allocated by orb_match_consecutive itself (d_desc8 only for a matrix-core matcher, and softly); listed to be freed
         add(&p->d_matches, 0);
@@ -511,13 +489,7 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
     return l;
 }
 
-void free_stage_buffers(OrbProgram* p, int which) {
-    const StageBufs l = stage_buffers(p, which);
-    for (int i = 0; i < l.n; i++) {
-        if (*l.b[i].slot) (void)(l.b[i].pinned ? hipHostFree(*l.b[i].slot) : hipFree(*l.b[i].slot));
-        *l.b[i].slot = nullptr;
-    }
-}
+void free_stage_buffers(OrbProgram* p, int which) { free_bufs(stage_buffers(p, which)); }
 
 // A stage's buffers on its first call, all or none: a failure frees the earlier ones and leaves every slot null, so the next call
 // allocates again.
@@ -526,7 +498,7 @@ int alloc_all_or_none(OrbProgram* p, int which, const char* who) {
     if (l.overflow) return fail(p, ORB_ESTATE, "%s: internal: the stage names more than %d buffers", who, StageBufs::kMax);
     if (*l.b[0].slot) return ORB_OK;
     for (int i = 0; i < l.n; i++) {
-        const StageBuf& b = l.b[i];
+        const Buf& b = l.b[i];
         const hipError_t e = b.pinned ? hipHostMalloc(b.slot, b.bytes, hipHostMallocDefault) : hipMalloc(b.slot, b.bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
@@ -631,65 +603,44 @@ int drain_profile(OrbProgram* p) {
     return ORB_OK;
 }
 
-void layout_pyramid(uint32_t W, uint32_t H, uint32_t depth, Pyramid* pyr) {
-    memset(pyr, 0, sizeof *pyr);
-    pyr->depth = depth;
-    uint32_t off = 0;
-    for (uint32_t m = 0; m < depth; m++) {
-        uint32_t w = W >> m, h = H >> m;  // wgpu mip chain: max(1, dim >> m)
-        pyr->w[m] = w ? w : 1u;
-        pyr->h[m] = h ? h : 1u;
-        pyr->off[m] = off;
-        off += pyr->w[m] * pyr->h[m];
-        off = (off + 7u) & ~7u;  // keep every level 16-byte aligned
-    }
-    pyr->stride = (off + 63u) & ~63u;
-    uint32_t rows = 0;
-    for (uint32_t m = 0; m < depth; m++) {
-        pyr->row_off[m] = rows;
-        rows += pyr->h[m];
-    }
-    pyr->row_stride = (rows + 7u) & ~7u;
-}
-
 // The staged pipeline for `n` frames starting at device pointer `frames` (orb.rs:469-534).
 int run_staged(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s) {
-    const Pyramid& pyr = p->pyr;
+    const Pyramid& pyr = p->plan.pyr;
     const uint32_t W = pyr.w[0], H = pyr.h[0], D = pyr.depth, cap = p->cfg.max_features;
     HIP_TRY(p, hipMemsetAsync(p->d_counts, 0, sizeof(uint32_t) * n, s));  // orb.rs:475 clear_buffer(counter)
     {
         LaunchScope ls(p, s, KID_GRAY);
         dim3 grid((W + 1023u) / 1024u, H, n);
-        if (p->input_y8)
-            hipLaunchKernelGGL(k_grayscale_y8, grid, dim3(256), 0, s, frames, p->frame_bytes, p->d_gray, pyr);
-        else if (p->intended)
-            hipLaunchKernelGGL(k_grayscale<true>, grid, dim3(256), 0, s, frames, p->frame_bytes, p->d_gray, pyr);
+        if (p->plan.input_y8)
+            hipLaunchKernelGGL(k_grayscale_y8, grid, dim3(256), 0, s, frames, p->plan.frame_bytes, p->d_gray, pyr);
+        else if (p->plan.intended)
+            hipLaunchKernelGGL(k_grayscale<true>, grid, dim3(256), 0, s, frames, p->plan.frame_bytes, p->d_gray, pyr);
         else
-            hipLaunchKernelGGL(k_grayscale<false>, grid, dim3(256), 0, s, frames, p->frame_bytes, p->d_gray, pyr, p->opt.fp_contract);
+            hipLaunchKernelGGL(k_grayscale<false>, grid, dim3(256), 0, s, frames, p->plan.frame_bytes, p->d_gray, pyr, p->opt.fp_contract);
     }
     for (uint32_t m = 1; m < D; m++) {  // orb.rs:413-429
         LaunchScope ls(p, s, KID_MIP);
         dim3 grid((pyr.w[m] + 63u) / 64u, (pyr.h[m] + 4u * kMipRows - 1u) / (4u * kMipRows), n);
-        hipLaunchKernelGGL(k_mip, grid, dim3(64, 4), 0, s, p->d_gray, pyr, m, (float)pyr.w[m - 1] / (float)pyr.w[m], (float)pyr.h[m - 1] / (float)pyr.h[m], p->wq);
+        hipLaunchKernelGGL(k_mip, grid, dim3(64, 4), 0, s, p->d_gray, pyr, m, (float)pyr.w[m - 1] / (float)pyr.w[m], (float)pyr.h[m - 1] / (float)pyr.h[m], p->plan.wq);
     }
     for (uint32_t m = 0; m < D; m++) {  // orb.rs:432-466 (both passes)
         LaunchScope ls(p, s, KID_BLUR);
-        if (p->intended) {
+        if (p->plan.intended) {
             hipLaunchKernelGGL(k_gauss, dim3((pyr.w[m] + kGaussTW - 1u) / kGaussTW, (pyr.h[m] + kGaussTH - 1u) / kGaussTH, n), dim3(256), 0, s,
                                p->d_gray, p->d_blur, pyr, m);
             continue;
         }
         dim3 grid(pyr.h[m], 1, n);
         size_t lds = (size_t)pyr.w[m] * 2u * sizeof(uint16_t);
-        hipLaunchKernelGGL(k_blur_rows, grid, dim3(256), lds, s, p->d_gray, p->d_blur, pyr, m, p->wq, p->opt.fp_contract);
+        hipLaunchKernelGGL(k_blur_rows, grid, dim3(256), lds, s, p->d_gray, p->d_blur, pyr, m, p->plan.wq, p->opt.fp_contract);
     }
     const bool nms = (p->opt.flags & ORB_FLAG_NMS) != 0u;
-    const uint32_t im = p->intended ? 1u : 0u;
-    const bool prov = nms || p->intended;  // the detector writes the provisional list
+    const uint32_t im = p->plan.intended ? 1u : 0u;
+    const bool prov = nms || p->plan.intended;  // the detector writes the provisional list
     if (prov) HIP_TRY(p, hipMemsetAsync(p->d_prov_counts, 0, sizeof(uint32_t) * n, s));
-    if (nms && p->intended) HIP_TRY(p, hipMemsetAsync(p->d_prov2_counts, 0, sizeof(uint32_t) * n, s));
+    if (nms && p->plan.intended) HIP_TRY(p, hipMemsetAsync(p->d_prov2_counts, 0, sizeof(uint32_t) * n, s));
     if (nms) {
-        HIP_TRY(p, hipMemsetAsync(p->d_score_planes, 0, sizeof(float) * (size_t)p->score_layout.stride * n, s));
+        HIP_TRY(p, hipMemsetAsync(p->d_score_planes, 0, sizeof(float) * (size_t)p->plan.score_layout.stride * n, s));
     }
     uint32_t width = W, height = H;  // orb.rs:501-519
     for (uint32_t oct = 0; oct < D; oct++) {
@@ -698,31 +649,31 @@ int run_staged(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s) 
             LaunchScope ls(p, s, KID_FAST);
             dim3 grid((gw + 15u) / 16u, (gh + 15u) / 16u, n);
             if (prov)
-                hipLaunchKernelGGL(k_fast, grid, dim3(16, 16), 0, s, p->d_gray, pyr, oct, gw, gh, p->threshold, p->arc, im,
-                                   p->d_prov_counts, p->d_prov, p->cap_prov, p->d_prov_scores,
-                                   nms ? p->d_score_planes : (float*)nullptr, p->score_layout);
+                hipLaunchKernelGGL(k_fast, grid, dim3(16, 16), 0, s, p->d_gray, pyr, oct, gw, gh, p->threshold, p->plan.arc, im,
+                                   p->d_prov_counts, p->d_prov, p->plan.cap_prov, p->d_prov_scores,
+                                   nms ? p->d_score_planes : (float*)nullptr, p->plan.score_layout);
             else
-                hipLaunchKernelGGL(k_fast, grid, dim3(16, 16), 0, s, p->d_gray, pyr, oct, gw, gh, p->threshold, p->arc, im,
-                                   p->d_counts, p->d_corners, cap, (float*)nullptr, (float*)nullptr, p->score_layout, p->oob);
+                hipLaunchKernelGGL(k_fast, grid, dim3(16, 16), 0, s, p->d_gray, pyr, oct, gw, gh, p->threshold, p->plan.arc, im,
+                                   p->d_counts, p->d_corners, cap, (float*)nullptr, (float*)nullptr, p->plan.score_layout, p->plan.oob);
         }
         width /= 2u;
         height /= 2u;
     }
-    const uint32_t nms_blocks = std::min<uint32_t>((p->cap_prov + 255u) / 256u, 64u);
-    if (nms && !p->intended) {
+    const uint32_t nms_blocks = std::min<uint32_t>((p->plan.cap_prov + 255u) / 256u, 64u);
+    if (nms && !p->plan.intended) {
         LaunchScope ls(p, s, KID_FAST);
         hipLaunchKernelGGL(k_nms, dim3(nms_blocks, 1, n), dim3(256), 0, s, p->d_prov_counts, p->d_prov,
-                           p->d_prov_scores, p->cap_prov, p->d_score_planes, p->score_layout, p->d_counts, p->d_corners,
+                           p->d_prov_scores, p->plan.cap_prov, p->d_score_planes, p->plan.score_layout, p->d_counts, p->d_corners,
                            cap, (float*)nullptr);
     }
-    if (p->intended) {  // [NMS ->] top-K cut -> final list (IM-7, IM-8)
+    if (p->plan.intended) {  // [NMS ->] top-K cut -> final list (IM-7, IM-8)
         LaunchScope ls(p, s, KID_FAST);
         if (nms)
             hipLaunchKernelGGL(k_nms, dim3(nms_blocks, 1, n), dim3(256), 0, s, p->d_prov_counts,
-                               p->d_prov, p->d_prov_scores, p->cap_prov, p->d_score_planes, p->score_layout,
-                               p->d_prov2_counts, p->d_prov2, p->cap_prov, p->d_prov2_scores);
+                               p->d_prov, p->d_prov_scores, p->plan.cap_prov, p->d_score_planes, p->plan.score_layout,
+                               p->d_prov2_counts, p->d_prov2, p->plan.cap_prov, p->d_prov2_scores);
         hipLaunchKernelGGL(k_topk, dim3(n), dim3(1024), 0, s, nms ? p->d_prov2_counts : p->d_prov_counts,
-                           nms ? p->d_prov2 : p->d_prov, nms ? p->d_prov2_scores : p->d_prov_scores, p->cap_prov,
+                           nms ? p->d_prov2 : p->d_prov, nms ? p->d_prov2_scores : p->d_prov_scores, p->plan.cap_prov,
                            p->d_counts, p->d_corners, cap);
     }
     {  // orb.rs:523-534
@@ -732,116 +683,11 @@ int run_staged(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s) 
         if (bx > 64u) bx = 64u;
         if (bx < 1u) bx = 1u;
         hipLaunchKernelGGL(k_brief, dim3(bx, 1, n), dim3(256), 0, s, p->d_blur, pyr, p->d_counts, p->d_corners, cap,
-                           p->d_desc, tab, im, p->oob, p->opt.fp_contract, p->opt.angle_bins);
+                           p->d_desc, tab, im, p->plan.oob, p->opt.fp_contract, p->opt.angle_bins);
     }
     HIP_TRY(p, hipGetLastError());
     p->planes_valid = true;
     return ORB_OK;
-}
-
-// Can the fused per-level kernels handle this configuration?  (Otherwise: staged pipeline.)
-bool fused_eligible(const OrbProgram* p) {
-    if (p->opt.flags & (ORB_FLAG_STAGED | ORB_FLAG_NMS | ORB_FLAG_INTENDED)) return false;
-    if (p->arc != 12u) return false;  // the fused FAST phase is specialised for the reference's 12-run
-    const Pyramid& pyr = p->pyr;
-    // index arithmetic: v_mul_i32_i24 takes 24-bit operands (rows, widths < 2^14 here) and returns 32 bits; RGBA byte
-    // offsets inside a frame are 4 * W * H < 2^32
-    if ((uint64_t)pyr.w[0] * pyr.h[0] > (1ull << 26) || pyr.h[0] > 16384u) return false;
-    if (pyr.w[0] > (uint32_t)kFrontMaxWidthTiled || pyr.w[0] < 8u) return false;
-    // rows of any width: k_front<..., UA> loads RGBA texel by texel (4-byte aligned) and Y8 byte by byte
-    return true;  // a level 1 that is not an exact half is built by k_mip from the stored level-0 plane (FrontGeom::store_grey)
-}
-
-uint32_t front_bands(const Pyramid& pyr, uint32_t lvl, uint32_t band_rows) {
-    const uint32_t gh = (((pyr.h[0] >> lvl) + 7u) / 8u) * 8u;  // orb.rs:513, 518
-    const uint32_t rows = pyr.h[lvl] > gh ? pyr.h[lvl] : gh;
-    return (rows + band_rows - 1) / band_rows;
-}
-
-// tile_w = 0: full-width bands; else column tiles of that width (rounded up to 8; FrontGeom::tiled)
-FrontGeom front_geometry(const Pyramid& pyr, uint32_t lvl, uint32_t gw, uint32_t gh, uint32_t n_frames,
-                         uint32_t band_rows = kFrontRows, uint32_t tile_w = 0, uint32_t threads = 0) {
-    FrontGeom g{};
-    g.lvl = lvl;
-    g.rows = band_rows;
-    g.gw = gw;
-    g.gh = gh;
-    const uint32_t w = pyr.w[lvl], h = pyr.h[lvl];
-    const uint32_t rows = h > gh ? h : gh;
-    g.n_bands = (rows + band_rows - 1) / band_rows;
-    g.n_frames = n_frames;
-    const uint32_t cols = (w > gw ? w : gw) + 4u;
-    g.ls = kLdsPad + ((cols + 7u) & ~7u);
-    g.ts = (w + 7u) & ~7u;
-    g.write_mip = (lvl + 1 < pyr.depth && w == 2u * pyr.w[lvl + 1] && h == 2u * pyr.h[lvl + 1]) ? 1u : 0u;
-    g.xcd_swizzle = (n_frames % 8u == 0u) ? 1u : 0u;
-    {   // constant stretches of the literal blur (tap 1 is monotone in x): see k_front phase C
-        uint32_t P = 0;
-        while (P < w && blur_tap(P, w, kBlurOffHost).i1 == 0) P++;
-        uint32_t Q = 0;
-        if (P > 0) while (Q < w && (uint32_t)blur_tap(Q, w, kBlurOffHost).i1 < P) Q++;
-        g.blur_p = P;
-        g.blur_q = Q;
-        g.n_var = w - Q;
-    }
-    if (tile_w) {
-        const uint32_t dom = ((w > gw ? w : gw) + 7u) & ~7u;  // columns of the level / of its dispatch domain
-        g.tiled = 1u;
-        g.tw = std::min((tile_w + 7u) & ~7u, dom);
-        g.n_ct = (dom + g.tw - 1u) / g.tw;
-        g.xb = 3u;
-        while ((1u << g.xb) < g.tw) g.xb++;
-        g.ls = kLdsPad + ((g.tw + 4u + 7u) & ~7u);
-        g.ts = std::min(g.tw, (w + 7u) & ~7u);
-        const BlurTap t = blur_tap(w - 1u, w, kBlurOffHost);
-        g.far_i0 = (uint32_t)t.i0;
-        g.far_i1 = (uint32_t)t.i1;
-        // queues B (3 ts entries) and C (ts), or the blur column table (24 bytes per column that varies), whichever is larger
-        g.tmp_halfs = std::max<uint32_t>(2u * kFrontTmpRows * g.ts, (uint32_t)(sizeof(BlurCol) / 2u) * g.n_var);
-        g.tmp_halfs = (g.tmp_halfs + 7u) & ~7u;
-    }
-    {   // pre-test items of a band (tile): rows x ceil(dispatch columns / 16) at level 0 and on 1024 threads, / 8 otherwise (orb_front_body.inc, B1)
-        const uint32_t cols_t = g.tiled ? std::min(g.tw, gw) : gw, iw = (lvl == 0 || threads == (uint32_t)kFrontThreadsLNBig) ? 16u : 8u;
-        g.ovf_words = (band_rows * ((cols_t + iw - 1u) / iw) + 31u) / 32u;
-    }
-    g.n_classes = 1u;
-    g.phase_mask = 15u;  // run_fused_range applies the program's experiment switches (TINYORB_PHASE_MASK, TINYORB_NO_SWIZZLE)
-    return g;
-}
-
-// Can tile 0 of a tiled level do the band's blur from its own columns?  The column table's grey texels lie in [0, ~0.12 w].
-bool front_tile0_holds_blur(const FrontGeom& g, uint32_t w) {
-    if (!g.tiled || g.n_ct == 1u) return true;
-    uint32_t hi = 0;
-    for (uint32_t x = g.blur_q; x < w; x++) {
-        const BlurTap t2 = blur_tap(x, w, kBlurOffHost);
-        for (int j : {t2.i0, t2.i1})
-            if ((uint32_t)j >= g.blur_p) hi = std::max<uint32_t>(hi, (uint32_t)blur_tap((uint32_t)j, w, kBlurOffHost).i1);
-    }
-    return hi + 1u <= g.tw;
-}
-
-// Geometry of k_brief_t over the band (or tile) slots described by `rg`; false when the frame is too large for its LDS
-// staging (then k_brief_rows does the work).
-bool brieft_geometry(const OrbProgram* p, const RowsGeom& rg, uint32_t n_classes, BriefTGeom* out) {
-    BriefTGeom g{};
-    g.n_slots = rg.n_slots;
-    g.seg_cap = rg.seg_cap;
-    g.n_classes = n_classes;
-    uint32_t rows = 0;
-    for (uint32_t m = 0; m < p->pyr.depth; m++) {
-        g.flat_end[m] = rg.flat_end[m];
-        g.qa[m] = rg.qa[m];
-        // 18 zero rows in front of a level and 26 behind it: the patch reaches 18 rows past the keypoint, and at
-        // octaves >= 1 a keypoint may sit up to 7 rows below the level's last row (8-rounded dispatch, Q8)
-        g.row_base[m] = rows + (uint32_t)kBriefHalo;
-        rows += p->pyr.h[m] + 2u * (uint32_t)kBriefHalo + 8u;
-    }
-    g.rows_padded = rows;
-    g.oob = p->oob;
-    *out = g;
-    if (getenv("TINYORB_BRIEF_ROWS")) return false;  // A/B and cross-check: the wave-per-keypoint kernel
-    return rg.n_slots >= 1u && rg.n_slots * n_classes <= kBriefTMaxSlots && rows <= kBriefTMaxRows;
 }
 
 // k_slot_prefix + BRIEF over the band (or tile) slots `rows_geom` of frames [f0, f0 + n).
@@ -850,14 +696,14 @@ int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_
                  uint32_t* d_counts, CornerData* d_corners, CornerDescriptor* d_desc, uint32_t f0 = 0) {
     const uint32_t cap = p->cfg.max_features;
     const BriefTables tab{p->d_pattern, p->d_cos, p->d_sin, p->d_rot};
-    const bool use_t = p->use_brief_t;
+    const bool use_t = p->plan.use_brief_t;
     {
         LaunchScope ls(p, s, KID_PREFIX);
         hipLaunchKernelGGL(k_slot_prefix, dim3(n), dim3(64), 0, s, seg_counts, seg_before, d_counts, rows_geom.n_slots,
-                           rows_geom.seg_cap, use_t ? p->brieft.n_classes : 1u);
+                           rows_geom.seg_cap, use_t ? p->plan.brieft.n_classes : 1u);
     }
     if (use_t) {
-        const BriefTGeom& tg = p->brieft;
+        const BriefTGeom& tg = p->plan.brieft;
         const dim3 grid(n, (cap + (uint32_t)kBriefNfChunk - 1u) / (uint32_t)kBriefNfChunk);  // k_brief_nf's
         // the not-flat mask of these frames in the current output set: written by k_brief_t, read by k_brief_nf behind it on the stream
         const uint32_t mask_words = brief_mask_words(cap);
@@ -866,7 +712,7 @@ int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_
             LaunchScope ls(p, s, KID_BRIEF_T);
 #define BRIEF_T_LAUNCH(ROT_)                                                                                                         \
     hipLaunchKernelGGL((k_brief_t<kBriefTWaves, ROT_>), dim3(n, (cap + kBriefTThreads - 1u) / kBriefTThreads), dim3(kBriefTThreads), \
-                       brieft_lds_bytes(tg), s, d_blur_rowc, p->pyr, tg, seg_counts, seg_before, seg, d_corners, cap, d_desc, tab, nf_mask, mask_words)
+                       brieft_lds_bytes(tg), s, d_blur_rowc, p->plan.pyr, tg, seg_counts, seg_before, seg, d_corners, cap, d_desc, tab, nf_mask, mask_words)
             switch (rot_form(p->opt.fp_contract)) {  // the rotation's form (OrbOptions::fp_contract): a template parameter of the straight-line tests
                 case 1: BRIEF_T_LAUNCH(1); break;
                 case 2: BRIEF_T_LAUNCH(2); break;
@@ -877,10 +723,10 @@ int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_
         LaunchScope ls(p, s, KID_BRIEF_NF);
         // the level constants: a scalar select between two levels' kernel arguments, or the LDS table for deeper pyramids
 #define BRIEF_NF_LAUNCH(OOB_, TABLE_)                                                                                                  \
-    hipLaunchKernelGGL((k_brief_nf<OOB_, TABLE_>), grid, dim3(256), 0, s, d_blur, d_blur_rowc, p->pyr, tg, d_corners, cap, d_desc, tab, \
+    hipLaunchKernelGGL((k_brief_nf<OOB_, TABLE_>), grid, dim3(256), 0, s, d_blur, d_blur_rowc, p->plan.pyr, tg, d_corners, cap, d_desc, tab, \
                        nf_mask, mask_words)
-        const bool table = p->pyr.depth > 2u;
-        if (p->oob != kOobZero) {
+        const bool table = p->plan.pyr.depth > 2u;
+        if (p->plan.oob != kOobZero) {
             if (table) BRIEF_NF_LAUNCH(true, true); else BRIEF_NF_LAUNCH(true, false);
         } else {
             if (table) BRIEF_NF_LAUNCH(false, true); else BRIEF_NF_LAUNCH(false, false);
@@ -889,11 +735,11 @@ int launch_brief(OrbProgram* p, hipStream_t s, uint32_t n, const RowsGeom& rows_
     } else {
         LaunchScope ls(p, s, KID_BRIEF_ROWS);
         RowsGeom rg = rows_geom;
-        rg.oob = p->oob;
+        rg.oob = p->plan.oob;
         rg.fp = p->opt.fp_contract;
         rg.split = 1u;  // small batches: several workgroups per band slot so that the chip still sees ~2000 of them
         while (rg.split < 16u && rg.n_slots * n * rg.split < 2048u) rg.split *= 2u;
-        hipLaunchKernelGGL(k_brief_rows, dim3(rg.n_slots * rg.split, n), dim3(256), 0, s, d_blur, d_blur_rowc, p->pyr, rg,
+        hipLaunchKernelGGL(k_brief_rows, dim3(rg.n_slots * rg.split, n), dim3(256), 0, s, d_blur, d_blur_rowc, p->plan.pyr, rg,
                            seg_counts, seg_before, seg, d_corners, cap, d_desc, tab);
     }
     return ORB_OK;
@@ -904,48 +750,12 @@ const BlurCol* front_blur_tab(const OrbProgram* p, const FrontGeom& g) {
     return (g.lvl == 0u && !g.tiled) ? reinterpret_cast<const BlurCol*>(p->d_blur_tab) : nullptr;
 }
 
-// The geometry of level `lvl` of the plain fused pipeline for a batch of n frames; gw, gh: the octave's FAST dispatch domain (orb.rs:501-519).
+// The geometry of level `lvl` of the plain fused pipeline for a batch of n frames: the plan's, with the program's device pointers.
 FrontGeom fused_level_geometry(const OrbProgram* p, uint32_t lvl, uint32_t gw, uint32_t gh, uint32_t n) {
-    const Pyramid& pyr = p->pyr;
-    FrontGeom g = front_geometry(pyr, lvl, gw ? gw : 8u, gh, n, p->band_rows_lvl[lvl], p->tile_w_lvl[lvl], p->ln_threads[lvl]);
-    if (gw == 0) g.gh = 0;  // no FAST dispatch at this octave (orb.rs:511-515 with width 0)
-    g.slot_base = p->bands.slot_base[lvl];
-    g.n_slots = p->bands.n_slots;
-    g.seg_cap = p->bands.seg_cap;
-    g.n_classes = p->seg_classes;
+    FrontGeom g = plan_level_geometry(p->plan, p->opt, p->env, lvl, gw, gh, n);
     g.stamps = p->d_stamps;
-    if (p->env.phase_mask >= 0) g.phase_mask = (uint32_t)p->env.phase_mask;
-    if (p->env.no_swizzle) g.xcd_swizzle = 0u;
-    g.oob = p->oob;
-    g.wq = p->wq;
-    g.fp = p->opt.fp_contract;
     g.blur_tab = front_blur_tab(p, g);
-    g.store_grey = (lvl == 0 && pyr.depth > 1 && !(pyr.w[0] == 2u * pyr.w[1] && pyr.h[0] == 2u * pyr.h[1])) ? 1u : 0u;
     return g;
-}
-
-// Which instance of k_front a prepared launch takes: one with a compile-time geometry (orb_kernels_front.h) when the launch is of that
-// instance's kind -- level, input, alignment, band height, threads, arithmetic form -- AND every field the geometry replaces holds the
-// compiled-in value, compared one by one (the frame size alone does not decide: TINYORB_BAND_ROWS, a program of one frame, a batch that
-// is not a multiple of 8, an out-of-level policy, another depth all change the geometry); the generic instance otherwise, and always
-// under TINYORB_FRONT_GENERIC=1.  `why`: what ruled the specialised instance out.
-FrontGeoId front_pick_geo(const OrbProgram* p, const FrontLaunch& L, const char** why = nullptr) {
-    const char* reason = nullptr;
-    FrontGeoId id = kFrontGeoGeneric;
-    const bool l0 = L.g.lvl == 0u;
-    if (p->env.front_generic) reason = "TINYORB_FRONT_GENERIC";
-    else if (L.g.lvl > 1u) reason = "lvl";
-    else if (L.input_y8) reason = "input_y8";
-    else if (L.general) reason = "general";
-    else if (L.oob) reason = "oob";
-    else if (L.from_plane) reason = "from_plane";
-    else if (front_form(p->opt.fp_contract, l0) != 0u) reason = "fp_contract";
-    else if (L.band_rows != (l0 ? FrontGeo720pL0::rows : FrontGeo720pL1::rows)) reason = "band_rows";
-    else if (!l0 && L.ln_threads != (uint32_t)kFrontThreadsLNBig) reason = "ln_threads";
-    else reason = l0 ? front_geo_mismatch<FrontGeo720pL0>(L.g, L.pyr) : front_geo_mismatch<FrontGeo720pL1>(L.g, L.pyr);
-    if (!reason) id = l0 ? kFrontGeo720pL0 : kFrontGeo720pL1;
-    if (why) *why = reason;
-    return id;
 }
 
 // The fused pipeline for frames [f0, f0 + n) of the batch on stream s: one k_front launch per level + BRIEF
@@ -953,16 +763,16 @@ FrontGeoId front_pick_geo(const OrbProgram* p, const FrontLaunch& L, const char*
 // first_level > 0 (single-frame call): the levels below it have been launched already (k_front_pair).
 int run_fused_range(OrbProgram* p, const uint8_t* frames_all, uint32_t f0, uint32_t n, hipStream_t s, bool with_brief = true,
                     uint32_t first_level = 0) {
-    const Pyramid& pyr = p->pyr;
+    const Pyramid& pyr = p->plan.pyr;
     const uint32_t D = pyr.depth, cap = p->cfg.max_features;
-    const uint8_t* frames = frames_all + (size_t)f0 * p->frame_bytes;
+    const uint8_t* frames = frames_all + (size_t)f0 * p->plan.frame_bytes;
     uint16_t* const d_gray = p->d_gray + (size_t)f0 * pyr.stride;
     uint16_t* const d_blur = p->d_blur + (size_t)f0 * pyr.stride;
     uint16_t* const d_blur_rowc = p->d_blur_rowc + (size_t)f0 * pyr.row_stride;
-    const size_t lists = (size_t)p->bands.n_slots * p->seg_classes;  // lists per frame
+    const size_t lists = (size_t)p->plan.bands.n_slots * p->plan.seg_classes;  // lists per frame
     uint32_t* const d_seg_counts = p->d_seg_counts + (size_t)f0 * lists;
     uint32_t* const d_seg_before = p->d_seg_before + (size_t)f0 * lists;
-    CornerData* const d_seg = p->d_seg + (size_t)f0 * lists * p->bands.seg_cap;
+    CornerData* const d_seg = p->d_seg + (size_t)f0 * lists * p->plan.bands.seg_cap;
     uint32_t* const d_counts = p->d_counts + f0;
     CornerData* const d_corners = p->d_corners + (size_t)f0 * cap;
     CornerDescriptor* const d_desc = p->d_desc + (size_t)f0 * cap;
@@ -978,11 +788,11 @@ int run_fused_range(OrbProgram* p, const uint8_t* frames_all, uint32_t f0, uint3
             hipStream_t sm = s;
             LaunchScope ls(p, sm, KID_MIP);  // inexact reduction (odd source size): generic bilinear blit
             dim3 grid((pyr.w[lvl] + 63u) / 64u, (pyr.h[lvl] + 4u * kMipRows - 1u) / (4u * kMipRows), n);
-            hipLaunchKernelGGL(k_mip, grid, dim3(64, 4), 0, sm, d_gray, pyr, lvl, (float)pyr.w[lvl - 1] / (float)pyr.w[lvl], (float)pyr.h[lvl - 1] / (float)pyr.h[lvl], p->wq);
+            hipLaunchKernelGGL(k_mip, grid, dim3(64, 4), 0, sm, d_gray, pyr, lvl, (float)pyr.w[lvl - 1] / (float)pyr.w[lvl], (float)pyr.h[lvl - 1] / (float)pyr.h[lvl], p->plan.wq);
         }
         const FrontGeom g = fused_level_geometry(p, lvl, gw, gh, n);
         hipStream_t s_lvl = s;
-        if (g.n_bands * (g.tiled ? g.n_ct : 1u) != p->bands.slot_base[lvl + 1] - p->bands.slot_base[lvl])
+        if (g.n_bands * (g.tiled ? g.n_ct : 1u) != p->plan.bands.slot_base[lvl + 1] - p->plan.bands.slot_base[lvl])
             return fail(p, ORB_EINVAL, "internal: band count mismatch at level %u", lvl);
         if (!g.tiled && sizeof(BlurCol) * (size_t)g.n_var > 8u * (size_t)g.ts)  // the column table borrows the queues' storage
             return fail(p, ORB_EINVAL, "internal: blur column table of level %u does not fit", lvl);
@@ -992,19 +802,19 @@ int run_fused_range(OrbProgram* p, const uint8_t* frames_all, uint32_t f0, uint3
         const dim3 grid(g.n_bands * (g.tiled ? g.n_ct : 1u) * n);
         // The kernel instances live in orb_front_inst.hip, one translation unit per arithmetic form (orb_front_launch.h); the form a
         // launch takes carries the luminance bits only where a luminance is computed (level 0 from RGBA).
-        FrontLaunch L{frames, p->frame_bytes, d_gray, d_blur, d_blur_rowc, pyr, g, p->threshold, d_seg_counts, d_seg, s_lvl, grid.x, lds,
-                      p->band_rows_lvl[lvl], p->ln_threads[lvl], p->input_y8,
+        FrontLaunch L{frames, p->plan.frame_bytes, d_gray, d_blur, d_blur_rowc, pyr, g, p->threshold, d_seg_counts, d_seg, s_lvl, grid.x, lds,
+                      p->plan.band_rows_lvl[lvl], p->plan.ln_threads[lvl], p->plan.input_y8,
                       // rows not aligned to a quad, or the level-0 plane is needed (level 1 not an exact half): the general variant
-                      lvl == 0 && ((pyr.w[0] & 3u) || g.store_grey), p->oob != kOobZero, false};
-        L.geo = front_pick_geo(p, L);
+                      lvl == 0 && ((pyr.w[0] & 3u) || g.store_grey), p->plan.oob != kOobZero, false};
+        L.geo = front_pick_geo(p->env, p->opt.fp_contract, L);
         {
             LaunchScope ls(p, s_lvl, lvl == 0 ? KID_FUSED_L0 : KID_FUSED_LN);
-            const hipError_t e = kFrontLaunch[front_form(p->opt.fp_contract, lvl == 0 && !p->input_y8)](L);
+            const hipError_t e = kFrontLaunch[front_form(p->opt.fp_contract, lvl == 0 && !p->plan.input_y8)](L);
             if (e != hipSuccess) return fail(p, ORB_EHIP, "k_front (level %u) failed to launch: %s", lvl, hipGetErrorString(e));
         }
     }
     // orb.rs:523-534, plus the compaction of the band segments into the final lists
-    if (with_brief) launch_brief(p, s, n, p->rows, d_blur, d_blur_rowc, d_seg_counts, d_seg_before, d_seg, d_counts, d_corners, d_desc, f0);
+    if (with_brief) launch_brief(p, s, n, p->plan.rows, d_blur, d_blur_rowc, d_seg_counts, d_seg_before, d_seg, d_counts, d_corners, d_desc, f0);
     HIP_TRY(p, hipGetLastError());
     return ORB_OK;
 }
@@ -1020,26 +830,12 @@ int run_fused(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s) {
     return ORB_OK;
 }
 
-// Tile width of a level for the fused "intended" pipeline.
-uint32_t itile_width(uint32_t w) {
-    const uint32_t w8 = (w + 7u) & ~7u;
-    return w8 < (uint32_t)kITileW ? w8 : (uint32_t)kITileW;
-}
-
-bool fused_i_eligible(const OrbProgram* p) {
-    if (!p->intended || (p->opt.flags & ORB_FLAG_STAGED)) return false;
-    const Pyramid& pyr = p->pyr;
-    if ((uint64_t)pyr.w[0] * pyr.h[0] > (1ull << 26)) return false;  // 32-bit byte offsets; W, H <= 16384 (create)
-    if ((pyr.w[0] & 3u) != 0u || pyr.w[0] < 8u) return false;       // level 0 is read as RGBA quads
-    return true;
-}
-
 // The fused "intended" pipeline: k_front_i per level (+ k_mip where a level is not an exact half), k_gauss per
 // level, k_select_i, k_brief_i.
 int run_fused_i(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s) {
-    const Pyramid& pyr = p->pyr;
+    const Pyramid& pyr = p->plan.pyr;
     const uint32_t D = pyr.depth, cap = p->cfg.max_features;
-    const IBriefGeom& bg = p->itiles;
+    const IBriefGeom& bg = p->plan.itiles;
     for (uint32_t lvl = 0; lvl < D; lvl++) {
         if (lvl > 0 && !(pyr.w[lvl - 1] == 2u * pyr.w[lvl] && pyr.h[lvl - 1] == 2u * pyr.h[lvl])) {
             LaunchScope ls(p, s, KID_MIP);
@@ -1057,7 +853,7 @@ int run_fused_i(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s)
         g.slot_base = bg.slot_base[lvl];
         g.n_slots = bg.n_slots;
         g.seg_cap = bg.seg_cap;
-        g.arc = p->arc;
+        g.arc = p->plan.arc;
         g.nms = (p->opt.flags & ORB_FLAG_NMS) ? 1u : 0u;
         g.phase_mask = p->env.phase_mask >= 0 ? (uint32_t)p->env.phase_mask : 63u;
         g.literal = 0u;
@@ -1065,21 +861,21 @@ int run_fused_i(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s)
         g.dh = pyr.h[lvl];
         g.gx1 = (uint32_t)((int)pyr.w[lvl] - 16);
         g.gy1 = (uint32_t)((int)pyr.h[lvl] - 16);
-        g.blur = p->igauss_fused ? 1u : 0u;
-        g.store_grey = p->igrey_stored ? 1u : 0u;
+        g.blur = p->plan.igauss_fused ? 1u : 0u;
+        g.store_grey = p->plan.igrey_stored ? 1u : 0u;
         if (g.n_bands * g.n_ct != bg.slot_base[lvl + 1] - bg.slot_base[lvl])
             return fail(p, ORB_EINVAL, "internal: tile count mismatch at level %u", lvl);
         if (g.blur && !ifront_gauss_fits(g.tw)) return fail(p, ORB_EINVAL, "internal: tile width %u too wide for the fused Gaussian", g.tw);
         const dim3 grid(g.n_bands * g.n_ct * n);
         LaunchScope ls(p, s, lvl == 0 ? KID_FRONT_I : KID_FRONT_I_LN);  // level 0 (RGBA in) and the levels above are different launches: one id each
         if (lvl == 0)
-            hipLaunchKernelGGL(k_front_i<true>, grid, dim3(kIThreads), ifront_lds_bytes(g), s, frames, p->frame_bytes,
+            hipLaunchKernelGGL(k_front_i<true>, grid, dim3(kIThreads), ifront_lds_bytes(g), s, frames, p->plan.frame_bytes,
                                p->d_gray, p->d_blur, pyr, g, p->threshold, p->d_iseg_counts, p->d_iseg, p->d_iseg_scores);
         else
-            hipLaunchKernelGGL(k_front_i<false>, grid, dim3(kIThreads), ifront_lds_bytes(g), s, frames, p->frame_bytes,
+            hipLaunchKernelGGL(k_front_i<false>, grid, dim3(kIThreads), ifront_lds_bytes(g), s, frames, p->plan.frame_bytes,
                                p->d_gray, p->d_blur, pyr, g, p->threshold, p->d_iseg_counts, p->d_iseg, p->d_iseg_scores);
     }
-    for (uint32_t m = 0; m < D && !p->igauss_fused; m++) {
+    for (uint32_t m = 0; m < D && !p->plan.igauss_fused; m++) {
         LaunchScope ls(p, s, KID_BLUR);
         hipLaunchKernelGGL(k_gauss, dim3((pyr.w[m] + kGaussTW - 1u) / kGaussTW, (pyr.h[m] + kGaussTH - 1u) / kGaussTH, n), dim3(256), 0, s, p->d_gray,
                            p->d_blur, pyr, m);
@@ -1095,7 +891,7 @@ int run_fused_i(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s)
         bgl.xcd_swizzle = (n % 8u == 0u) ? 1u : 0u;
         bgl.phase_mask = p->env.brief_i_mask >= 0 ? (uint32_t)p->env.brief_i_mask : 3u;
         bgl.angle_bins = p->opt.angle_bins;
-        hipLaunchKernelGGL(k_brief_i, dim3(bg.group_base[D] * n), dim3(kIBriefThreads), p->ibrief_lds, s, p->d_blur, pyr, bgl,
+        hipLaunchKernelGGL(k_brief_i, dim3(bg.group_base[D] * n), dim3(kIBriefThreads), p->plan.ibrief_lds, s, p->d_blur, pyr, bgl,
                            p->d_iseg_counts, p->d_iseg_before, p->d_thr_key, p->d_iseg, p->d_iseg_scores, p->d_corners, cap,
                            p->d_desc, BriefTables{p->d_pattern, p->d_cos, p->d_sin, p->d_rot});
     }
@@ -1104,34 +900,13 @@ int run_fused_i(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s)
     return ORB_OK;
 }
 
-// Dispatch grid of octave `lvl` in the reference (orb.rs:501-519: halved and 8-rounded per octave).
-void reference_grid(const Pyramid& pyr, uint32_t lvl, uint32_t* gw, uint32_t* gh) {
-    uint32_t width = pyr.w[0], height = pyr.h[0];
-    for (uint32_t m = 0; m < lvl; m++) {
-        width /= 2u;
-        height /= 2u;
-    }
-    *gw = ((width + 7u) / 8u) * 8u;
-    *gh = ((height + 7u) / 8u) * 8u;
-}
-
-bool fused_x_eligible(const OrbProgram* p) {
-    if (p->intended || p->input_y8 || (p->opt.flags & ORB_FLAG_STAGED)) return false;  // the tile kernel reads RGBA
-    if (p->arc == 12u && !(p->opt.flags & ORB_FLAG_NMS)) return false;  // that is the plain fused pipeline
-    const Pyramid& pyr = p->pyr;
-    if ((uint64_t)pyr.w[0] * pyr.h[0] > (1ull << 26) || pyr.h[0] > 16384u) return false;
-    if ((pyr.w[0] & 3u) != 0u || pyr.w[0] > (uint32_t)kFrontMaxWidth || pyr.w[0] < 8u) return false;
-    if (pyr.depth > 1 && !(pyr.w[0] == 2u * pyr.w[1] && pyr.h[0] == 2u * pyr.h[1])) return false;
-    return true;
-}
-
 // The reference's algorithm with the opt-in arc length / NMS, fused: k_front_i per level
 // in its literal setting (grey plane, detector, NMS, mip), k_front<false> per level with only its blur phase (row
 // constants + stored tail from the grey plane), k_slot_prefix, k_brief_rows over the tile slots.
 int run_fused_x(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s) {
-    const Pyramid& pyr = p->pyr;
+    const Pyramid& pyr = p->plan.pyr;
     const uint32_t D = pyr.depth;
-    const IBriefGeom& bg = p->itiles;
+    const IBriefGeom& bg = p->plan.itiles;
     uint32_t band_base = 0;
     for (uint32_t lvl = 0; lvl < D; lvl++) {
         if (lvl > 0 && !(pyr.w[lvl - 1] == 2u * pyr.w[lvl] && pyr.h[lvl - 1] == 2u * pyr.h[lvl])) {
@@ -1152,7 +927,7 @@ int run_fused_x(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s)
         g.slot_base = bg.slot_base[lvl];
         g.n_slots = bg.n_slots;
         g.seg_cap = bg.seg_cap;
-        g.arc = p->arc;
+        g.arc = p->plan.arc;
         g.nms = (p->opt.flags & ORB_FLAG_NMS) ? 1u : 0u;
         g.phase_mask = 63u;
         g.literal = 1u;
@@ -1168,10 +943,10 @@ int run_fused_x(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s)
             LaunchScope ls(p, s, lvl == 0 ? KID_FRONT_I : KID_FRONT_I_LN);  // level 0 (RGBA in) and the levels above are different launches: one id each
             const dim3 grid(g.n_bands * g.n_ct * n);
             if (lvl == 0)
-                hipLaunchKernelGGL(k_front_i<true>, grid, dim3(kIThreads), ifront_lds_bytes(g), s, frames, p->frame_bytes,
+                hipLaunchKernelGGL(k_front_i<true>, grid, dim3(kIThreads), ifront_lds_bytes(g), s, frames, p->plan.frame_bytes,
                                    p->d_gray, p->d_blur, pyr, g, p->threshold, p->d_iseg_counts, p->d_iseg, p->d_iseg_scores);
             else
-                hipLaunchKernelGGL(k_front_i<false>, grid, dim3(kIThreads), ifront_lds_bytes(g), s, frames, p->frame_bytes,
+                hipLaunchKernelGGL(k_front_i<false>, grid, dim3(kIThreads), ifront_lds_bytes(g), s, frames, p->plan.frame_bytes,
                                    p->d_gray, p->d_blur, pyr, g, p->threshold, p->d_iseg_counts, p->d_iseg, p->d_iseg_scores);
         }
         // else: no FAST dispatch at this octave (orb.rs:511-515 with width 0).  Its tile slots were zeroed at create and
@@ -1182,7 +957,7 @@ int run_fused_x(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s)
             fg.phase_mask = 8u;
             fg.write_mip = 0u;
             fg.slot_base = band_base;
-            fg.n_slots = p->xband_slots;
+            fg.n_slots = p->plan.xband_slots;
             fg.seg_cap = 1u;
             fg.n_classes = 1u;
             fg.stamps = nullptr;
@@ -1190,13 +965,13 @@ int run_fused_x(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s)
             const uint32_t lds = front_lds_bytes(fg);
             if (lds > p->max_lds) return fail(p, ORB_EINVAL, "level %u needs %u bytes of LDS", lvl, lds);
             LaunchScope ls(p, s, KID_FUSED_LN);
-            const FrontLaunch L{frames, p->frame_bytes, p->d_gray, p->d_blur, p->d_blur_rowc, pyr, fg, p->threshold, p->d_xband_counts, p->d_iseg, s,
+            const FrontLaunch L{frames, p->plan.frame_bytes, p->d_gray, p->d_blur, p->d_blur_rowc, pyr, fg, p->threshold, p->d_xband_counts, p->d_iseg, s,
                                 fg.n_bands * n, lds, (uint32_t)kFrontRows, (uint32_t)kFrontThreadsLN, false, false, false, true};
             const hipError_t e = kFrontLaunch[0](L);  // k_front<false> (16 rows, 512 threads), from the unit that instantiates it
             if (e != hipSuccess) return fail(p, ORB_EHIP, "k_front (blur of level %u) failed to launch: %s", lvl, hipGetErrorString(e));
         }
     }
-    launch_brief(p, s, n, p->xrows, p->d_blur, p->d_blur_rowc, p->d_iseg_counts, p->d_iseg_before, p->d_iseg, p->d_counts,
+    launch_brief(p, s, n, p->plan.xrows, p->d_blur, p->d_blur_rowc, p->d_iseg_counts, p->d_iseg_before, p->d_iseg, p->d_counts,
                  p->d_corners, p->d_desc);
     HIP_TRY(p, hipGetLastError());
     p->planes_valid = true;
@@ -1207,14 +982,191 @@ int launch_compact(OrbProgram* p, uint32_t n, uint32_t* counts, uint64_t* offset
                    size_t capacity, void* stream, hipStream_t* used);  // below, with the bulk read-back
 
 int run_pipeline(OrbProgram* p, const uint8_t* frames, uint32_t n, hipStream_t s) {
-    if (p->fused_i) return run_fused_i(p, frames, n, s);
-    if (p->fused_x) return run_fused_x(p, frames, n, s);
-    return p->fused ? run_fused(p, frames, n, s) : run_staged(p, frames, n, s);
+    if (p->plan.fused_i) return run_fused_i(p, frames, n, s);
+    if (p->plan.fused_x) return run_fused_x(p, frames, n, s);
+    return p->plan.fused ? run_fused(p, frames, n, s) : run_staged(p, frames, n, s);
 }
 
 int ensure_input(OrbProgram* p) {
-    if (!p->d_input) HIP_TRY(p, hipMalloc(&p->d_input, p->frame_bytes * p->max_batch));
+    if (!p->d_input) HIP_TRY(p, hipMalloc(&p->d_input, p->plan.frame_bytes * p->plan.max_batch));
     return ORB_OK;
+}
+
+// Entries of the rotated-pattern table, for the consumer this program has: k_brief_i's window (intended, full circle; IM-6b,
+// OrbOptions::angle_bins: one entry per angle bin instead of one per milliradian code) or k_brief_nf's patch (the reference's codes 0..3141)
+uint32_t rot_codes(const OrbProgram* p) {
+    return p->plan.fused_i ? (p->opt.angle_bins ? p->opt.angle_bins : (uint32_t)ORB_ANGLE_STEPS_FULL) : (uint32_t)ORB_ANGLE_STEPS;
+}
+
+// k_front's blur column table of level 0: a function of the level's width (and the sampler's weight bits) alone, so built at create
+// once, with the band's own arithmetic (blur_col_entry), instead of by every band of every frame.  A level 0 on column tiles
+// and the levels above keep building theirs in the band (orb_front_body.inc): n_var = 0, no table.
+FrontGeom blur_tab_geometry(const OrbProgram* p) {
+    if (!p->plan.fused || p->plan.tile_w_lvl[0]) return FrontGeom{};
+    return front_geometry(p->plan.pyr, 0, 8u, 8u, 1, p->plan.band_rows_lvl[0]);  // blur_p, blur_q, n_var: of the width alone
+}
+
+// The buffers orb_program_create allocates, named here and nowhere else: create fills the slots (and zeroes the cleared ones, a blocking
+// hipMemset before any launch), orb_program_destroy frees them.  A function of the plan, the options and the switches, which do not change.
+// Not here: what is allocated on first use (d_input, d_input_alt, the pack buffers, the stages' buffers).
+ProgramBufs program_buffers(OrbProgram* p) {
+    const ProgramPlan& pl = p->plan;
+    const size_t B = pl.max_batch, cap = p->cfg.max_features;
+    const int sets = (p->opt.flags & ORB_FLAG_DOUBLE_OUTPUT) ? 2 : 1;
+    ProgramBufs l;
+    enum { kDevice = 0, kPinned = 1, kCleared = 2 };
+#define PBUF(slot, bytes, kind) l.add(Buf{(void**)&p->slot, (bytes), ((kind) & kPinned) != 0, ((kind) & kCleared) != 0, #slot})
+    PBUF(d_gray, B * pl.pyr.stride * sizeof(uint16_t), kDevice);
+    PBUF(d_blur, B * pl.pyr.stride * sizeof(uint16_t), kDevice);
+    for (int set = 0; set < sets; set++) {
+        PBUF(out_counts[set], B * sizeof(uint32_t), kDevice | kCleared);
+        PBUF(out_corners[set], B * cap * sizeof(CornerData), kDevice | kCleared);
+        PBUF(out_desc[set], B * cap * sizeof(CornerDescriptor), kDevice | kCleared);
+    }
+    if (pl.fused || pl.fused_x) PBUF(d_blur_rowc, B * pl.pyr.row_stride * sizeof(uint16_t), kDevice | kCleared);
+    if (pl.fused) {
+        const size_t lists = (size_t)pl.bands.n_slots * pl.seg_classes;
+        PBUF(d_seg, B * lists * (size_t)pl.bands.seg_cap * sizeof(CornerData), kDevice);
+        PBUF(d_seg_counts, B * lists * sizeof(uint32_t), kDevice | kCleared);
+        PBUF(d_seg_before, B * lists * sizeof(uint32_t), kDevice);
+    }
+    if (pl.use_brief_t)  // (the band pipeline or the tile pipeline: whichever launch_brief serves)
+        for (int set = 0; set < sets; set++)  // (not cleared: k_brief_t writes every word of the frames of a batch before k_brief_nf reads them)
+            PBUF(d_nf_mask[set], B * brief_mask_words((uint32_t)cap) * sizeof(uint64_t), kDevice);
+    if (pl.fused_x) PBUF(d_xband_counts, B * (size_t)pl.xband_slots * sizeof(uint32_t), kDevice);
+    if (pl.fused_i || pl.fused_x) {
+        const size_t n_seg = B * (size_t)pl.itiles.n_slots;
+        PBUF(d_iseg, n_seg * pl.itiles.seg_cap * sizeof(CornerData), kDevice);
+        PBUF(d_iseg_scores, n_seg * pl.itiles.seg_cap * sizeof(float), kDevice);
+        PBUF(d_iseg_counts, n_seg * sizeof(uint32_t), kDevice | kCleared);
+        PBUF(d_iseg_before, n_seg * sizeof(uint32_t), kDevice);
+        PBUF(d_thr_key, B * sizeof(unsigned long long), kDevice);
+    } else if (p->opt.flags & (ORB_FLAG_NMS | ORB_FLAG_INTENDED)) {  // the staged kernels' score planes and provisional lists
+        if (p->opt.flags & ORB_FLAG_NMS) PBUF(d_score_planes, B * (size_t)pl.score_layout.stride * sizeof(float), kDevice);
+        PBUF(d_prov_counts, B * sizeof(uint32_t), kDevice);
+        PBUF(d_prov, B * (size_t)pl.cap_prov * sizeof(CornerData), kDevice);
+        PBUF(d_prov_scores, B * (size_t)pl.cap_prov * sizeof(float), kDevice);
+        if (pl.intended && (p->opt.flags & ORB_FLAG_NMS)) {
+            PBUF(d_prov2_counts, B * sizeof(uint32_t), kDevice);
+            PBUF(d_prov2, B * (size_t)pl.cap_prov * sizeof(CornerData), kDevice);
+            PBUF(d_prov2_scores, B * (size_t)pl.cap_prov * sizeof(float), kDevice);
+        }
+    }
+    PBUF(d_pattern, 256 * sizeof(uint32_t), kDevice);
+    PBUF(d_cos, ORB_ANGLE_STEPS_FULL * sizeof(float), kDevice);
+    PBUF(d_sin, ORB_ANGLE_STEPS_FULL * sizeof(float), kDevice);
+    PBUF(d_rot, (size_t)rot_codes(p) * 64u * sizeof(uint4), kDevice);
+    // (cleared on the program's stream in front of its kernel, create_tables: an odd n_var ends in the middle of a piece)
+    if (const uint32_t pieces = blur_col_pieces(blur_tab_geometry(p).n_var)) PBUF(d_blur_tab, (size_t)pieces * sizeof(uint4), kDevice);
+    if (pl.fused && p->env.stamps) PBUF(d_stamps, 32 * sizeof(unsigned long long), kDevice | kCleared);  // diagnostic builds only (tools/stamps.py)
+    PBUF(h_count, kSingleCountWords * sizeof(uint32_t), kPinned);  // (cleared by the host, create_buffers)
+    PBUF(d_single_done, sizeof(uint32_t), kDevice | kCleared);
+    PBUF(h_corners, cap * sizeof(CornerData), kPinned);
+    PBUF(h_desc, cap * sizeof(CornerDescriptor), kPinned);
+#undef PBUF
+    return l;
+}
+
+// orb_program_create, step by step.  Each returns ORB_OK or the code of fail(p, ...); create then destroys the program.
+
+int create_device(OrbProgram* p) {
+    int n_dev = 0;
+    const hipError_t e = hipGetDeviceCount(&n_dev);
+    if (e != hipSuccess || n_dev <= 0) return fail(p, ORB_EHIP, "no HIP device available (%s)", e == hipSuccess ? "count is 0" : hipGetErrorString(e));
+    if (p->device < 0 || p->device >= n_dev) return fail(p, ORB_EINVAL, "device %d out of range (0..%d)", p->device, n_dev - 1);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    int lds_max = 0, cus = 0;
+    HIP_TRY(p, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, p->device));
+    HIP_TRY(p, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
+    p->max_lds = (uint32_t)lds_max;
+    p->n_cus = cus > 0 ? (uint32_t)cus : 256u;
+    return ORB_OK;
+}
+
+// The dynamic-LDS attribute belongs to the function on this device, not to the program: always raise it to the device's limit (less
+// the kernel's static LDS), never to this program's own need, so that a later, smaller program never lowers it under a live, larger one.
+int create_attributes(OrbProgram* p) {
+    if (p->plan.fused)
+        for (auto set_max_lds : kFrontSetMaxLds) HIP_TRY(p, set_max_lds((int)p->max_lds));  // every instance of k_front / k_front_pair
+    if (p->plan.fused_i) {
+        hipFuncAttributes fa{};
+        hipError_t ea = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_brief_i));
+        if (ea == hipSuccess && p->plan.ibrief_lds + (uint32_t)fa.sharedSizeBytes > p->max_lds)
+            return fail(p, ORB_EINVAL, "k_brief_i needs %u bytes of LDS", p->plan.ibrief_lds + (uint32_t)fa.sharedSizeBytes);
+        if (ea == hipSuccess)
+            ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_brief_i), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(p->max_lds - (uint32_t)fa.sharedSizeBytes));
+        if (ea != hipSuccess) return fail(p, ORB_EHIP, "hipFuncSetAttribute(k_brief_i): %s", hipGetErrorString(ea));
+    }
+    if (p->plan.fused_x) {
+        const hipError_t ea = kFrontSetMaxLds[0]((int)p->max_lds);  // (the unit that holds k_front<false>)
+        if (ea != hipSuccess) return fail(p, ORB_EHIP, "hipFuncSetAttribute(k_front): %s", hipGetErrorString(ea));
+    }
+    return ORB_OK;
+}
+
+// TINYORB_FRONT_TRACE=1: which instance of k_front a full batch takes at each level; and the staged pipeline's note, once per process
+void create_say(const OrbProgram* p) {
+    if (p->plan.fused && p->env.front_trace) fputs(front_trace_text(p->plan, p->opt, p->env).c_str(), stderr);
+    static bool warned = false;
+    if (!p->plan.pipeline_note.empty() && !warned && !p->env.quiet) {
+        warned = true;
+        fprintf(stderr, "libtinyorb: %s\n", p->plan.pipeline_note.c_str());
+    }
+}
+
+int create_buffers(OrbProgram* p) {
+    const ProgramBufs l = program_buffers(p);
+    if (l.overflow) return fail(p, ORB_ESTATE, "internal: the program names more than %d buffers", ProgramBufs::kMax);
+    for (int i = 0; i < l.n; i++) {
+        const Buf& b = l.b[i];
+        const hipError_t e = b.pinned ? hipHostMalloc(b.slot, b.bytes, hipHostMallocDefault) : hipMalloc(b.slot, b.bytes);
+        if (e != hipSuccess) {
+            *b.slot = nullptr;
+            return fail(p, ORB_EHIP, "%s of %s (%zu bytes) failed: %s", b.pinned ? "hipHostMalloc" : "hipMalloc", b.name, b.bytes, hipGetErrorString(e));
+        }
+        if (b.cleared) HIP_TRY(p, hipMemset(*b.slot, 0, b.bytes));
+    }
+    memset(p->h_count, 0, kSingleCountWords * sizeof(uint32_t));
+    p->d_counts = p->out_counts[0];
+    p->d_corners = p->out_corners[0];
+    p->d_desc = p->out_desc[0];
+    return ORB_OK;
+}
+
+// The constant tables and the two kernels that derive a table from them, on the program's stream
+int create_tables(OrbProgram* p) {
+    HIP_TRY(p, hipMemcpy(p->d_pattern, ORB_BRIEF_PATTERN, 1024, hipMemcpyHostToDevice));
+    HIP_TRY(p, hipMemcpy(p->d_cos, ORB_COS_BITS, ORB_ANGLE_STEPS_FULL * 4, hipMemcpyHostToDevice));
+    HIP_TRY(p, hipMemcpy(p->d_sin, ORB_SIN_BITS, ORB_ANGLE_STEPS_FULL * 4, hipMemcpyHostToDevice));
+    const bool fi = p->plan.fused_i;  // the pattern rotated by every angle code, for k_brief_i's window or k_brief_nf's patch (rot_codes)
+    hipLaunchKernelGGL(k_rot_table, dim3(rot_codes(p)), dim3(64), 0, p->stream, p->d_pattern, p->d_cos, p->d_sin, fi ? (int)p->plan.itiles.pitch : kNfPatchCols,
+                       fi ? 1 : 0, p->d_rot, p->opt.fp_contract, fi ? p->opt.angle_bins : 0u);
+    HIP_TRY(p, hipGetLastError());
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (p->d_blur_tab) {
+        const FrontGeom g = blur_tab_geometry(p);
+        HIP_TRY(p, hipMemsetAsync(p->d_blur_tab, 0, (size_t)blur_col_pieces(g.n_var) * sizeof(uint4), p->stream));  // an odd n_var ends in the middle of a piece
+        hipLaunchKernelGGL(k_blur_col_table<>, dim3((g.n_var + 63u) / 64u), dim3(64), 0, p->stream, p->plan.pyr.w[0], g.blur_p, g.blur_q, g.n_var, p->plan.wq,
+                           reinterpret_cast<BlurCol*>(p->d_blur_tab));
+        HIP_TRY(p, hipGetLastError());
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+    }
+    return ORB_OK;
+}
+
+// Device-visible addresses of the staging arrays, once (null: the runtime cannot map them -> the three copies of orb.rs:537-547)
+void create_staging_pointers(OrbProgram* p) {
+    void *dc = nullptr, *dk = nullptr, *dd = nullptr;
+    if (hipHostGetDevicePointer(&dc, p->h_count, 0) == hipSuccess && hipHostGetDevicePointer(&dk, p->h_corners, 0) == hipSuccess &&
+        hipHostGetDevicePointer(&dd, p->h_desc, 0) == hipSuccess) {
+        p->dv_count = static_cast<uint32_t*>(dc);
+        p->dv_corners = static_cast<CornerData*>(dk);
+        p->dv_desc = static_cast<CornerDescriptor*>(dd);
+    } else {
+        (void)hipGetLastError();
+    }
 }
 
 }  // namespace
@@ -1225,494 +1177,39 @@ uint32_t orb_abi_version(void) { return TINYORB_ABI_VERSION; }
 
 const char* orb_last_error(const OrbProgram* p) { return p ? p->err.c_str() : g_create_error.c_str(); }
 
-const char* orb_pipeline(const OrbProgram* p) { return p ? ((p->fused || p->fused_i || p->fused_x) ? "fused" : "staged") : ""; }
+const char* orb_pipeline(const OrbProgram* p) { return p ? ((p->plan.fused || p->plan.fused_i || p->plan.fused_x) ? "fused" : "staged") : ""; }
 
-const char* orb_pipeline_note(const OrbProgram* p) { return p ? p->pipeline_note.c_str() : ""; }
+const char* orb_pipeline_note(const OrbProgram* p) { return p ? p->plan.pipeline_note.c_str() : ""; }
 
 const char* orb_kernel_name(int id) { return (id >= 0 && id < ORB_KERNEL_COUNT) ? kKernelNames[id] : ""; }
 
 int orb_program_create(const OrbConfig* config, const OrbOptions* options, OrbProgram** out) {
     if (!out) return fail(nullptr, ORB_EINVAL, "out is NULL");
     *out = nullptr;
-    if (!config) return fail(nullptr, ORB_EINVAL, "config is NULL");
-    const uint32_t W = config->image_size.width, H = config->image_size.height;
-    if (W == 0 || H == 0 || config->image_size.depth_or_array_layers != 1)
-        return fail(nullptr, ORB_EINVAL, "image_size must be WxHx1 with W,H > 0");
-    if ((uint64_t)W * H > (1ull << 28)) return fail(nullptr, ORB_EINVAL, "image too large");
-    if (config->hierarchy_depth < 1 || config->hierarchy_depth > ORB_MAX_HIERARCHY_DEPTH)
-        return fail(nullptr, ORB_EINVAL, "hierarchy_depth must be 1..=10 (orb.rs:66-67)");
-    if (config->max_features == 0 || config->max_features > (1u << 24))
-        return fail(nullptr, ORB_EINVAL, "max_features must be 1..=2^24");
-    if (!(config->initial_threshold >= 0.f)) return fail(nullptr, ORB_EINVAL, "initial_threshold must be >= 0");
-    if (options && options->fast_arc != 0 && (options->fast_arc < 9 || options->fast_arc > 16))
-        return fail(nullptr, ORB_EINVAL, "fast_arc must be 0 (= 12) or 9..16");
-    if (options && (options->flags & ORB_FLAG_INPUT_Y8) &&
-        ((options->flags & (ORB_FLAG_INTENDED | ORB_FLAG_NMS)) || (options->fast_arc != 0 && options->fast_arc != 12)))
-        return fail(nullptr, ORB_EINVAL, "ORB_FLAG_INPUT_Y8 is defined for the reference's detector only (no "
-                                         "ORB_FLAG_INTENDED, ORB_FLAG_NMS or fast_arc other than 12)");
-    if (options && (options->oob_policy > ORB_OOB_UMIN || options->sampler_weight_bits > 23u))
-        return fail(nullptr, ORB_EINVAL, "oob_policy must be ORB_OOB_ZERO / _CLAMP / _UMIN and sampler_weight_bits 0..23");
-    if (options && (options->oob_policy != ORB_OOB_ZERO || options->sampler_weight_bits != 0u) &&
-        ((options->flags & (ORB_FLAG_INTENDED | ORB_FLAG_NMS)) || (options->fast_arc != 0 && options->fast_arc != 12)))
-        return fail(nullptr, ORB_EINVAL, "oob_policy / sampler_weight_bits follow the reference's adapter: they are defined for the "
-                                         "reference's detector only (no ORB_FLAG_INTENDED, ORB_FLAG_NMS or fast_arc other than 12)");
-    if (options && options->fp_contract > (ORB_FP_CONTRACT_ALL | ORB_FP_LAST_TERM_FIRST))
-        return fail(nullptr, ORB_EINVAL, "fp_contract is a mask of ORB_FP_CONTRACT_LUMINANCE / _BLUR / _ROTATION and ORB_FP_LAST_TERM_FIRST");
-    if (options && options->fp_contract &&
-        ((options->flags & (ORB_FLAG_INTENDED | ORB_FLAG_NMS | ORB_FLAG_INPUT_Y8)) || (options->fast_arc != 0 && options->fast_arc != 12)))
-        return fail(nullptr, ORB_EINVAL, "fp_contract follows the reference's shader compiler: it is defined for the reference's detector on RGBA "
-                                         "input only (no ORB_FLAG_INTENDED, ORB_FLAG_NMS, ORB_FLAG_INPUT_Y8 or fast_arc other than 12)");
-    if (options && options->angle_bins && (!(options->flags & ORB_FLAG_INTENDED) || options->angle_bins < 8u || options->angle_bins > 6284u))
-        return fail(nullptr, ORB_EINVAL, "angle_bins is an option of ORB_FLAG_INTENDED (IM-6b): 0, or 8..6284 bins of the full circle");
-    if (options && (options->flags & ORB_FLAG_INTENDED) && (W > 16384u || H > 16384u))
-        return fail(nullptr, ORB_EINVAL, "ORB_FLAG_INTENDED needs W, H <= 16384 (14-bit coordinates in the top-K key)");
-
+    if (const char* msg = check_config(config, options)) return fail(nullptr, ORB_EINVAL, "%s", msg);
     OrbProgram* p = new (std::nothrow) OrbProgram();
     if (!p) return fail(nullptr, ORB_EINVAL, "out of host memory");
     p->cfg = *config;
     if (options) p->opt = *options;
     p->device = p->opt.device;
-    p->max_batch = p->opt.max_batch ? p->opt.max_batch : 1u;
     p->threshold = config->initial_threshold;  // orb.rs:178
-    p->intended = (p->opt.flags & ORB_FLAG_INTENDED) != 0u;
-    p->input_y8 = (p->opt.flags & ORB_FLAG_INPUT_Y8) != 0u;
-    p->arc = p->opt.fast_arc ? p->opt.fast_arc : (p->intended ? 9u : 12u);
-    p->oob = p->opt.oob_policy;
-    p->wq = p->opt.sampler_weight_bits ? (float)(1u << p->opt.sampler_weight_bits) : 0.0f;
-    p->frame_bytes = (size_t)W * H * (p->input_y8 ? 1u : 4u);
-    layout_pyramid(W, H, config->hierarchy_depth, &p->pyr);
-    {   // experiment / cross-check switches: the environment is read here and nowhere on a per-call path
-        auto on = [](const char* name) { const char* e = getenv(name); return e && *e && atoi(e) != 0; };
-        auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e && *e ? atoi(e) : dflt; };
-        p->env.single_memcpy = on("TINYORB_SINGLE_MEMCPY");
-        p->env.single_split = on("TINYORB_SINGLE_SPLIT");
-        p->env.single_serial = on("TINYORB_SINGLE_SERIAL");
-        p->env.single_sync = on("TINYORB_SINGLE_SYNC");
-        {   // how orb_extract_corners waits: "poll" (default) spins on the completion word; "block" spins for kSingleSpinUs, then sleeps
-            // in hipEventSynchronize on a blocking-sync event (an interrupt instead of a spin -- the reference blocks in device.poll(Wait),
-            // orb.rs:547); ORB_FLAG_SINGLE_BLOCKING_WAIT asks for the same from code
-            const char* w = getenv("TINYORB_SINGLE_WAIT");
-            p->env.single_block = (w && !strcmp(w, "block")) || (p->opt.flags & ORB_FLAG_SINGLE_BLOCKING_WAIT) != 0u;
-        }
-        p->env.no_swizzle = on("TINYORB_NO_SWIZZLE");
-        p->env.quiet = getenv("TINYORB_QUIET") != nullptr;
-        p->env.front_generic = on("TINYORB_FRONT_GENERIC");
-        p->env.front_trace = on("TINYORB_FRONT_TRACE");
-        p->env.phase_mask = num("TINYORB_PHASE_MASK", -1);
-        p->env.brief_i_mask = num("TINYORB_BRIEF_I_MASK", -1);
-        p->env.lds_pad = num("TINYORB_LDS_PAD", 0);
+    p->env = read_plan_env(p->opt.flags);
+    int rc = create_device(p);
+    if (!rc) {
+        p->plan = plan_program(p->cfg, p->opt, p->max_lds, p->env);
+        rc = create_attributes(p);
     }
-
-    auto bail = [&](int code) {
+    if (!rc) {
+        create_say(p);
+        rc = create_buffers(p);
+    }
+    if (!rc) rc = create_tables(p);
+    if (rc) {
         g_create_error = p->err;
         orb_program_destroy(p);
-        return code;
-    };
-    int n_dev = 0;
-    hipError_t e = hipGetDeviceCount(&n_dev);
-    if (e != hipSuccess || n_dev <= 0) {
-        fail(p, ORB_EHIP, "no HIP device available (%s)", e == hipSuccess ? "count is 0" : hipGetErrorString(e));
-        return bail(ORB_EHIP);
+        return rc;
     }
-    if (p->device < 0 || p->device >= n_dev) {
-        fail(p, ORB_EINVAL, "device %d out of range (0..%d)", p->device, n_dev - 1);
-        return bail(ORB_EINVAL);
-    }
-#define CREATE_TRY(expr)                                                            \
-    do {                                                                            \
-        hipError_t e2_ = (expr);                                                    \
-        if (e2_ != hipSuccess) {                                                    \
-            fail(p, ORB_EHIP, "%s failed: %s", #expr, hipGetErrorString(e2_));      \
-            return bail(ORB_EHIP);                                                  \
-        }                                                                           \
-    } while (0)
-    CREATE_TRY(hipSetDevice(p->device));
-    CREATE_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    {
-        int lds_max = 0;
-        CREATE_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, p->device));
-        p->max_lds = (uint32_t)lds_max;
-        int cus = 0;
-        CREATE_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
-        p->n_cus = cus > 0 ? (uint32_t)cus : 256u;
-        p->fused = fused_eligible(p);
-        if (p->fused) {
-            // Band height per level, from kFrontBandHeights (64, 32, 16, 8 rows: x of a queue entry in 9, 10, 11, 12 bits).
-            // Two workgroups per CU matter more than the smaller halo share of a taller band (0.62 against 0.45 ms at 720p
-            // with one), and a band should hold about 20 k pixels (the 1024 threads then take 2.5 pre-test items each): a
-            // level takes the tallest band of which two fit the CU's LDS -- level 0: 64 rows up to about 330 wide, 32 up to
-            // 700, 16 up to 1390, 8 up to 1980 --, else the tallest that fits at all (16 rows up to 2048, 8 rows up to 4096).
-            uint32_t need = 0;
-            {
-                uint32_t width = W, height = H;
-                const char* force = getenv("TINYORB_BAND_ROWS");  // experiments: one band height for every level that can have it
-                for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) {
-                    const uint32_t gw = ((width + 7u) / 8u) * 8u, gh = ((height + 7u) / 8u) * 8u, w = p->pyr.w[lvl];
-                    width /= 2u;
-                    height /= 2u;
-                    // the tallest band of which two fit a CU; else the tallest that fits at all
-                    uint32_t rows = 0, rows_lds = 0, fits = 0, fits_lds = 0, want = 0, want_lds = 0;
-                    const uint32_t forced = force ? (uint32_t)atoi(force) : 0u;
-                    auto pick = [&](uint32_t threads) {
-                        rows = rows_lds = fits = fits_lds = want = want_lds = 0u;
-                        for (int cand : kFrontBandHeights) {
-                            if (std::max(w, gw) > (1u << front_x_bits(cand)) || std::max(w, gw) > (uint32_t)kFrontMaxWidthWide) continue;
-                            // levels >= 1: beyond about 32 pixels per thread a band only gets longer (at 512 threads: 640 wide, 32 rows
-                            // 4 % slower than 16; 480 wide, 32 rows 16 % faster than 16)
-                            if (lvl > 0 && (uint32_t)cand * gw > 32u * threads && cand > kFrontRowsWide) continue;
-                            const uint32_t lds = front_lds_bytes(front_geometry(p->pyr, lvl, gw, gh, 1, (uint32_t)cand, 0u, threads));
-                            if (lds > p->max_lds) continue;
-                            if (forced == (uint32_t)cand) want = (uint32_t)cand, want_lds = lds;
-                            if (!fits) fits = (uint32_t)cand, fits_lds = lds;
-                            if (!rows && 2u * lds <= p->max_lds) rows = (uint32_t)cand, rows_lds = lds;
-                        }
-                    };
-                    // Levels >= 1 take level 0's shape -- 1024 threads, sixteen-pixel pre-test items -- where a band of which two fit
-                    // a CU holds about as many pixels as level 0's at 1280 columns (18 k and more: 640 columns x 32 rows, 320 x 64,
-                    // 1280 x 16; measured at 720p, 640x480, 2560x1440: 5 ... 21 % off k_front<false>), and 512 threads otherwise
-                    // (480 columns: the tallest band that fits twice is 32 x 480 = 15 k pixels, 13 % slower on 1024 threads; 160
-                    // columns: 27 % slower).  Not for programs of one frame (flat bands), forced heights, tiles or an out-of-level
-                    // policy (those instances exist for 512 threads only).
-                    p->ln_threads[lvl] = (uint32_t)kFrontThreadsLN;
-                    if (lvl > 0 && p->max_batch > 1u && !forced && !getenv("TINYORB_TILE_W") && p->oob == kOobZero && !getenv("TINYORB_LN_512")) {
-                        pick((uint32_t)kFrontThreadsLNBig);
-                        if (rows != 0u && rows * gw >= 18432u) p->ln_threads[lvl] = (uint32_t)kFrontThreadsLNBig;
-                    }
-                    if (p->ln_threads[lvl] != (uint32_t)kFrontThreadsLNBig) pick(lvl == 0 ? (uint32_t)kFrontThreadsL0 : (uint32_t)kFrontThreadsLN);
-                    const bool two_per_cu = rows != 0u;
-                    if (!rows) rows = fits, rows_lds = fits_lds;
-                    // A program for one frame at a time (the reference's call shape) is after latency, not throughput: its 45 + 23
-                    // bands cannot fill 256 CUs anyway, so it takes the flattest bands -- twice the workgroups, each with half
-                    // the work on its critical path (k_front<true> 16.3 -> 13.6 us at 720p).
-                    if (p->max_batch == 1u && two_per_cu && !want && !getenv("TINYORB_NO_LATENCY_BANDS")) {
-                        const uint32_t flat = (uint32_t)kFrontRowsWide;
-                        const uint32_t lds = front_lds_bytes(front_geometry(p->pyr, lvl, gw, gh, 1, flat));
-                        if (std::max(w, gw) <= (1u << front_x_bits((int)flat)) && lds <= p->max_lds) rows = flat, rows_lds = lds;
-                    }
-                    if (want) rows = want, rows_lds = want_lds;
-                    // Too wide for two full-width bands per CU (one workgroup per CU costs a third of the rate: 0.62 against
-                    // 0.45 ms at 720p), or for any: column tiles of about kFrontTileW columns -- 16 rows x 1280 columns is the
-                    // shape the kernel is tuned on --, equal ones, wide enough for tile 0 to hold the columns the band's blur
-                    // reads (front_tile0_holds_blur); 8 rows where 16-row tiles of that width do not fit a CU twice.
-                    const char* force_w = getenv("TINYORB_TILE_W");
-                    if ((!two_per_cu && !want) || force_w) {
-                        const uint32_t dom = (std::max(w, gw) + 7u) & ~7u;
-                        uint32_t want_w = force_w ? std::max(64u, (uint32_t)atoi(force_w)) : (uint32_t)kFrontTileW, tw = dom, t_rows = 0, t_lds = 0;
-                        for (; tw >= dom || t_rows == 0u; want_w += 64u) {
-                            const uint32_t n_ct = std::max(1u, (dom + want_w - 1u) / want_w);
-                            tw = std::min(dom, (((dom + n_ct - 1u) / n_ct) + 7u) & ~7u);
-                            t_rows = 0;
-                            for (uint32_t cand : {16u, 8u}) {
-                                const FrontGeom tg = front_geometry(p->pyr, lvl, gw, gh, 1, cand, tw);
-                                const uint32_t lds = front_lds_bytes(tg);
-                                const uint32_t items = lvl == 0 ? (tg.tw + 12u) / 4u : (tg.tw + 20u) / 8u;  // staged items of a row <= threads
-                                if (!front_tile0_holds_blur(tg, w) || cand > (1u << (15u - tg.xb)) || lds > p->max_lds ||
-                                    items > (lvl == 0 ? (uint32_t)kFrontThreadsL0 : (uint32_t)kFrontThreadsLN))
-                                    continue;
-                                if (!t_rows || (2u * lds <= p->max_lds && 2u * t_lds > p->max_lds)) t_rows = cand, t_lds = lds;
-                                if (2u * t_lds <= p->max_lds) break;
-                            }
-                            if (t_rows || want_w >= dom) break;
-                        }
-                        if (t_rows) {
-                            rows = t_rows, rows_lds = t_lds;
-                            p->tile_w_lvl[lvl] = tw;
-                        }
-                    }
-                    p->band_rows_lvl[lvl] = rows;
-                    need = rows == 0 ? p->max_lds + 1u : std::max(need, rows_lds);
-                }
-            }
-            if (need > p->max_lds) {
-                p->fused = false;
-            } else {
-                BandGeom& bg = p->bands;
-                uint32_t slots = 0;
-                uint64_t band_px = 0;  // pixels of the largest band (tile): no band can hold more corners
-                for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) {
-                    bg.slot_base[lvl] = slots;
-                    const uint64_t lvl_cols = ((uint64_t)(W >> lvl) + 7u) / 8u * 8u;
-                    uint32_t n_ct = 1;
-                    if (p->tile_w_lvl[lvl]) n_ct = (uint32_t)((lvl_cols + p->tile_w_lvl[lvl] - 1u) / p->tile_w_lvl[lvl]);
-                    slots += front_bands(p->pyr, lvl, p->band_rows_lvl[lvl]) * n_ct;
-                    band_px = std::max<uint64_t>(band_px, (uint64_t)p->band_rows_lvl[lvl] * (p->tile_w_lvl[lvl] ? p->tile_w_lvl[lvl] : lvl_cols));
-                }
-                bg.slot_base[p->pyr.depth] = slots;
-                bg.n_slots = slots;
-                bg.seg_cap = (uint32_t)(band_px < config->max_features ? band_px : config->max_features);
-                RowsGeom& rg = p->rows;
-                rg.n_slots = bg.n_slots;
-                rg.seg_cap = bg.seg_cap;
-                for (uint32_t lvl = 0; lvl <= p->pyr.depth; lvl++) rg.slot_base[lvl] = bg.slot_base[lvl];
-                for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) {
-                    // columns [0, qa) of the level's blur are kept as one constant per row (k_front, phase C)
-                    const uint32_t q = front_geometry(p->pyr, lvl, 8, 8, 1).blur_q, qa = q & ~7u;
-                    p->blur_qa[lvl] = qa;
-                    rg.qa[lvl] = qa;
-                    // a keypoint is "flat" when every sample column lies below Q, not only below qa: the stored columns [qa, Q) hold
-                    // the row constant too
-                    rg.flat_end[lvl] = q > (uint32_t)kBriefHalo ? q - kBriefHalo : 0u;
-                }
-                // The attribute belongs to the function on this device, not to the program: always raise it to the
-                // device's limit, so that a later, smaller program never lowers it under a live, larger one.
-                p->use_brief_t = brieft_geometry(p, rg, 2u, &p->brieft);
-                p->seg_classes = p->use_brief_t ? 2u : 1u;
-                for (auto set_max_lds : kFrontSetMaxLds) CREATE_TRY(set_max_lds((int)p->max_lds));  // every instance of k_front / k_front_pair
-                if (p->env.front_trace) {  // which instance of k_front a full batch (max_batch frames) takes at each level
-                    uint32_t width = W, height = H;
-                    for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) {
-                        const uint32_t gw = ((width + 7u) / 8u) * 8u, gh = ((height + 7u) / 8u) * 8u;
-                        width /= 2u;
-                        height /= 2u;
-                        const FrontGeom g = fused_level_geometry(p, lvl, gw, gh, p->max_batch);
-                        FrontLaunch L{};
-                        L.pyr = p->pyr, L.g = g, L.band_rows = p->band_rows_lvl[lvl], L.ln_threads = p->ln_threads[lvl], L.input_y8 = p->input_y8;
-                        L.general = lvl == 0 && ((p->pyr.w[0] & 3u) || g.store_grey), L.oob = p->oob != kOobZero;
-                        const char* why = nullptr;
-                        const FrontGeoId id = front_pick_geo(p, L, &why);
-                        fprintf(stderr, "tinyorb: k_front level %u (%ux%u, %u-row bands, batch %u) takes the %s instance%s%s\n", lvl, p->pyr.w[lvl], p->pyr.h[lvl],
-                                p->band_rows_lvl[lvl], p->max_batch, id == kFrontGeoGeneric ? "generic" : (id == kFrontGeo720pL0 ? "specialised 720p-L0" : "specialised 720p-L1"),
-                                why ? ": " : "", why ? why : "");
-                    }
-                }
-            }
-        }
-    }
-    p->fused_i = fused_i_eligible(p);
-    if (p->fused_i) {
-        IBriefGeom& bg = p->itiles;
-        uint32_t slots = 0;
-        for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) {
-            bg.tw[lvl] = itile_width(p->pyr.w[lvl]);
-            bg.n_ct[lvl] = (p->pyr.w[lvl] + bg.tw[lvl] - 1u) / bg.tw[lvl];
-            bg.slot_base[lvl] = slots;
-            slots += ((p->pyr.h[lvl] + kFrontRows - 1) / kFrontRows) * bg.n_ct[lvl];
-        }
-        bg.slot_base[p->pyr.depth] = slots;
-        bg.n_slots = slots;
-        uint32_t groups = 0, max_rows = 0;
-        for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) {
-            bg.n_bands[lvl] = (p->pyr.h[lvl] + kFrontRows - 1) / kFrontRows;
-            bg.group_base[lvl] = groups;
-            groups += ((bg.n_bands[lvl] + kIBriefStack - 1) / kIBriefStack) * bg.n_ct[lvl];
-            const uint32_t rows = std::min<uint32_t>(bg.n_bands[lvl], kIBriefStack) * kFrontRows + 2u * kBriefHalo;
-            if (rows > max_rows) max_rows = rows;
-        }
-        bg.group_base[p->pyr.depth] = groups;
-        // The Gaussian (IM-3) inside k_front_i, straight from the tile; the level-0 grey plane is then only stored when a level
-        // that is not an exact half needs it (k_mip reads planes).
-        p->igauss_fused = !getenv("TINYORB_I_GAUSS_KERNEL");
-        for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) p->igauss_fused = p->igauss_fused && ifront_gauss_fits(bg.tw[lvl]);
-        p->igrey_stored = !p->igauss_fused || (p->pyr.depth > 1 && !(p->pyr.w[0] == 2u * p->pyr.w[1] && p->pyr.h[0] == 2u * p->pyr.h[1]));
-        // a tile's segment holds every keypoint the tile can have (one per pixel), whatever max_features is: the
-        // top-K cut (IM-8) must see all candidates, not the ones that happened to be appended first
-        bg.seg_cap = (uint32_t)kFrontRows * bg.tw[0];
-        bg.pitch = (uint32_t)kITileW + 2u * kIBriefApronX;
-        p->ibrief_lds = max_rows * bg.pitch * (uint32_t)sizeof(uint16_t);
-        // as for k_front: raise to the device limit (less the kernel's static LDS), never to this program's own need
-        hipFuncAttributes fa{};
-        hipError_t ea = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_brief_i));
-        if (ea == hipSuccess && p->ibrief_lds + (uint32_t)fa.sharedSizeBytes > p->max_lds) {
-            fail(p, ORB_EINVAL, "k_brief_i needs %u bytes of LDS", p->ibrief_lds + (uint32_t)fa.sharedSizeBytes);
-            return bail(ORB_EINVAL);
-        }
-        if (ea == hipSuccess)
-            ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_brief_i), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(p->max_lds - (uint32_t)fa.sharedSizeBytes));
-        if (ea != hipSuccess) {
-            fail(p, ORB_EHIP, "hipFuncSetAttribute(k_brief_i): %s", hipGetErrorString(ea));
-            return bail(ORB_EHIP);
-        }
-    }
-    p->fused_x = fused_x_eligible(p);
-    if (p->fused_x) {
-        // tiles over the reference's dispatch grid of every octave; blur-only k_front launches over 16-row bands
-        IBriefGeom& bg = p->itiles;
-        RowsGeom& rg = p->xrows;
-        uint32_t slots = 0, bands = 0, need = 0;
-        for (uint32_t lvl = 0; lvl < p->pyr.depth; lvl++) {
-            uint32_t gw, gh;
-            reference_grid(p->pyr, lvl, &gw, &gh);
-            const uint32_t dw = std::max(p->pyr.w[lvl], gw), dh = std::max(p->pyr.h[lvl], gh);
-            bg.tw[lvl] = itile_width(dw);
-            bg.n_ct[lvl] = (dw + bg.tw[lvl] - 1u) / bg.tw[lvl];
-            bg.n_bands[lvl] = (dh + kFrontRows - 1) / kFrontRows;
-            bg.slot_base[lvl] = slots;
-            rg.slot_base[lvl] = slots;
-            slots += bg.n_bands[lvl] * bg.n_ct[lvl];
-            const FrontGeom fg = front_geometry(p->pyr, lvl, gw ? gw : 8u, gh, 1);
-            bands += fg.n_bands;
-            need = std::max(need, front_lds_bytes(fg));
-            const uint32_t qa = fg.blur_q & ~7u;
-            p->blur_qa[lvl] = qa;
-            rg.qa[lvl] = qa;
-            rg.flat_end[lvl] = fg.blur_q > (uint32_t)kBriefHalo ? fg.blur_q - kBriefHalo : 0u;
-        }
-        bg.slot_base[p->pyr.depth] = slots;
-        rg.slot_base[p->pyr.depth] = slots;
-        bg.n_slots = slots;
-        bg.seg_cap = (uint32_t)kFrontRows * bg.tw[0];
-        rg.n_slots = slots;
-        rg.seg_cap = bg.seg_cap;
-        p->xband_slots = bands;
-        if (need > p->max_lds) {
-            p->fused_x = false;
-        } else {
-            p->use_brief_t = brieft_geometry(p, rg, 1u, &p->brieft);  // the tile kernels keep one list per tile
-            hipError_t ea = kFrontSetMaxLds[0]((int)p->max_lds);  // (the unit that holds k_front<false>)
-            if (ea != hipSuccess) {
-                fail(p, ORB_EHIP, "hipFuncSetAttribute(k_front): %s", hipGetErrorString(ea));
-                return bail(ORB_EHIP);
-            }
-        }
-    }
-    if (!(p->fused || p->fused_i || p->fused_x) && !(p->opt.flags & ORB_FLAG_STAGED)) {
-        // A silent fall to the per-stage kernels is a 7x performance cliff: say why, once, and keep it readable.
-        const Pyramid& py = p->pyr;
-        char why[256];
-        const bool plain = !p->intended && !(p->opt.flags & ORB_FLAG_NMS) && p->arc == 12u;  // the reference's own algorithm
-        if ((py.w[0] & 3u) != 0u && !plain)
-            snprintf(why, sizeof why, "width %u is not a multiple of 4 (the tile kernels read RGBA quads)", py.w[0]);
-        else if (py.w[0] < 8u)
-            snprintf(why, sizeof why, "width %u is below 8", py.w[0]);
-        else if (!p->intended && py.w[0] > (uint32_t)kFrontMaxWidthTiled)
-            snprintf(why, sizeof why, "width %u exceeds %d", py.w[0], kFrontMaxWidthTiled);
-        else if ((uint64_t)py.w[0] * py.h[0] > (1ull << 26) || py.h[0] > 16384u)
-            snprintf(why, sizeof why, "%ux%u exceeds the fused kernels' 2^26-pixel / 16384-row index range", py.w[0], py.h[0]);
-        else if (!p->intended && !plain && py.depth > 1 && !(py.w[0] == 2u * py.w[1] && py.h[0] == 2u * py.h[1]))
-            snprintf(why, sizeof why, "level 0 (%ux%u) does not halve exactly and hierarchy_depth > 1", py.w[0], py.h[0]);
-        else if (p->input_y8 && ((p->opt.flags & ORB_FLAG_NMS) || p->arc != 12u))
-            snprintf(why, sizeof why, "the tile kernels of the arc/NMS extensions read RGBA");
-        else
-            snprintf(why, sizeof why, "the band does not fit in %u bytes of LDS", p->max_lds);
-        p->pipeline_note = std::string("staged pipeline (one kernel per reference stage, about 1/7 of the fused rate): ") + why;
-        static bool warned = false;
-        if (!warned && !p->env.quiet) {
-            warned = true;
-            fprintf(stderr, "libtinyorb: %s\n", p->pipeline_note.c_str());
-        }
-    }
-    const size_t B = p->max_batch, cap = config->max_features;
-    CREATE_TRY(hipMalloc(&p->d_gray, B * p->pyr.stride * sizeof(uint16_t)));
-    CREATE_TRY(hipMalloc(&p->d_blur, B * p->pyr.stride * sizeof(uint16_t)));
-    for (int set = 0; set < ((p->opt.flags & ORB_FLAG_DOUBLE_OUTPUT) ? 2 : 1); set++) {
-        CREATE_TRY(hipMalloc(&p->out_counts[set], B * sizeof(uint32_t)));
-        CREATE_TRY(hipMalloc(&p->out_corners[set], B * cap * sizeof(CornerData)));
-        CREATE_TRY(hipMalloc(&p->out_desc[set], B * cap * sizeof(CornerDescriptor)));
-        CREATE_TRY(hipMemset(p->out_counts[set], 0, B * sizeof(uint32_t)));
-        CREATE_TRY(hipMemset(p->out_corners[set], 0, B * cap * sizeof(CornerData)));
-        CREATE_TRY(hipMemset(p->out_desc[set], 0, B * cap * sizeof(CornerDescriptor)));
-    }
-    p->d_counts = p->out_counts[0];
-    p->d_corners = p->out_corners[0];
-    p->d_desc = p->out_desc[0];
-    if (p->fused) {
-        CREATE_TRY(hipMalloc(&p->d_blur_rowc, B * p->pyr.row_stride * sizeof(uint16_t)));
-        CREATE_TRY(hipMemset(p->d_blur_rowc, 0, B * p->pyr.row_stride * sizeof(uint16_t)));
-        const size_t lists = (size_t)p->bands.n_slots * p->seg_classes;
-        CREATE_TRY(hipMalloc(&p->d_seg, B * lists * (size_t)p->bands.seg_cap * sizeof(CornerData)));
-        CREATE_TRY(hipMalloc(&p->d_seg_counts, B * lists * sizeof(uint32_t)));
-        CREATE_TRY(hipMemset(p->d_seg_counts, 0, B * lists * sizeof(uint32_t)));
-        CREATE_TRY(hipMalloc(&p->d_seg_before, B * lists * sizeof(uint32_t)));
-    }
-    if (p->use_brief_t)  // (the band pipeline or the tile pipeline: whichever launch_brief serves)
-        for (int set = 0; set < ((p->opt.flags & ORB_FLAG_DOUBLE_OUTPUT) ? 2 : 1); set++) {
-            // (not cleared: k_brief_t writes every word of the frames of a batch before k_brief_nf reads them)
-            CREATE_TRY(hipMalloc(&p->d_nf_mask[set], B * brief_mask_words((uint32_t)cap) * sizeof(uint64_t)));
-        }
-    if (p->fused_x) {
-        CREATE_TRY(hipMalloc(&p->d_blur_rowc, B * p->pyr.row_stride * sizeof(uint16_t)));
-        CREATE_TRY(hipMemset(p->d_blur_rowc, 0, B * p->pyr.row_stride * sizeof(uint16_t)));
-        CREATE_TRY(hipMalloc(&p->d_xband_counts, B * (size_t)p->xband_slots * sizeof(uint32_t)));
-    }
-    if (p->fused_i || p->fused_x) {
-        const size_t n_seg = B * (size_t)p->itiles.n_slots;
-        CREATE_TRY(hipMalloc(&p->d_iseg, n_seg * p->itiles.seg_cap * sizeof(CornerData)));
-        CREATE_TRY(hipMalloc(&p->d_iseg_scores, n_seg * p->itiles.seg_cap * sizeof(float)));
-        CREATE_TRY(hipMalloc(&p->d_iseg_counts, n_seg * sizeof(uint32_t)));
-        CREATE_TRY(hipMemset(p->d_iseg_counts, 0, n_seg * sizeof(uint32_t)));
-        CREATE_TRY(hipMalloc(&p->d_iseg_before, n_seg * sizeof(uint32_t)));
-        CREATE_TRY(hipMalloc(&p->d_thr_key, B * sizeof(unsigned long long)));
-    } else if (p->opt.flags & (ORB_FLAG_NMS | ORB_FLAG_INTENDED)) {
-        // score planes: one float per dispatch-grid pixel of every octave + a 1-px border; provisional list
-        uint32_t off = 0, width = W, height = H;
-        for (uint32_t m = 0; m < p->pyr.depth; m++) {
-            const uint32_t gw = ((width + 7u) / 8u) * 8u, gh = ((height + 7u) / 8u) * 8u;
-            p->score_layout.off[m] = off;
-            p->score_layout.pitch[m] = gw + 2u;
-            off += (gw + 2u) * (gh + 2u);
-            width /= 2u;
-            height /= 2u;
-        }
-        p->score_layout.stride = (off + 63u) & ~63u;
-        // The provisional list must hold every detection (the NMS and the top-K cut have to see all of them): one
-        // slot per texel of the pyramid is the worst case and what is allocated (20 bytes per texel and frame).
-        p->cap_prov = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(p->pyr.stride, cap), 1u << 24);
-        if (p->opt.flags & ORB_FLAG_NMS)
-        CREATE_TRY(hipMalloc(&p->d_score_planes, B * (size_t)p->score_layout.stride * sizeof(float)));
-        CREATE_TRY(hipMalloc(&p->d_prov_counts, B * sizeof(uint32_t)));
-        CREATE_TRY(hipMalloc(&p->d_prov, B * (size_t)p->cap_prov * sizeof(CornerData)));
-        CREATE_TRY(hipMalloc(&p->d_prov_scores, B * (size_t)p->cap_prov * sizeof(float)));
-        if (p->intended && (p->opt.flags & ORB_FLAG_NMS)) {
-            CREATE_TRY(hipMalloc(&p->d_prov2_counts, B * sizeof(uint32_t)));
-            CREATE_TRY(hipMalloc(&p->d_prov2, B * (size_t)p->cap_prov * sizeof(CornerData)));
-            CREATE_TRY(hipMalloc(&p->d_prov2_scores, B * (size_t)p->cap_prov * sizeof(float)));
-        }
-    }
-    CREATE_TRY(hipMalloc(&p->d_pattern, 256 * sizeof(uint32_t)));
-    CREATE_TRY(hipMalloc(&p->d_cos, ORB_ANGLE_STEPS_FULL * sizeof(float)));
-    CREATE_TRY(hipMalloc(&p->d_sin, ORB_ANGLE_STEPS_FULL * sizeof(float)));
-    CREATE_TRY(hipMemcpy(p->d_pattern, ORB_BRIEF_PATTERN, 1024, hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(p->d_cos, ORB_COS_BITS, ORB_ANGLE_STEPS_FULL * 4, hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(p->d_sin, ORB_SIN_BITS, ORB_ANGLE_STEPS_FULL * 4, hipMemcpyHostToDevice));
-    {   // the pattern rotated by every angle code, for the consumer this program has: k_brief_i's window (intended, full circle) or
-        // k_brief_nf's patch (the reference's codes 0..3141)
-        // (IM-6b, OrbOptions::angle_bins: one entry per angle bin instead of one per milliradian code)
-        const uint32_t n_codes = p->fused_i ? (p->opt.angle_bins ? p->opt.angle_bins : (uint32_t)ORB_ANGLE_STEPS_FULL) : (uint32_t)ORB_ANGLE_STEPS;
-        const int pitch = p->fused_i ? (int)p->itiles.pitch : kNfPatchCols;
-        CREATE_TRY(hipMalloc(&p->d_rot, (size_t)n_codes * 64u * sizeof(uint4)));
-        hipLaunchKernelGGL(k_rot_table, dim3(n_codes), dim3(64), 0, p->stream, p->d_pattern, p->d_cos, p->d_sin, pitch, p->fused_i ? 1 : 0, p->d_rot,
-                           p->opt.fp_contract, p->fused_i ? p->opt.angle_bins : 0u);
-        CREATE_TRY(hipGetLastError());
-        CREATE_TRY(hipStreamSynchronize(p->stream));
-    }
-    if (p->fused && !p->tile_w_lvl[0]) {
-        // k_front's blur column table of level 0: a function of the level's width (and the sampler's weight bits) alone, so built here
-        // once, with the band's own arithmetic (blur_col_entry), instead of by every band of every frame.  A level 0 on column tiles
-        // and the levels above keep building theirs in the band (orb_front_body.inc).
-        const FrontGeom g = front_geometry(p->pyr, 0, 8u, 8u, 1, p->band_rows_lvl[0]);  // blur_p, blur_q, n_var: of the width alone
-        const uint32_t pieces = blur_col_pieces(g.n_var);
-        if (pieces) {
-            CREATE_TRY(hipMalloc(&p->d_blur_tab, (size_t)pieces * sizeof(uint4)));
-            CREATE_TRY(hipMemsetAsync(p->d_blur_tab, 0, (size_t)pieces * sizeof(uint4), p->stream));  // an odd n_var ends in the middle of a piece
-            hipLaunchKernelGGL(k_blur_col_table<>, dim3((g.n_var + 63u) / 64u), dim3(64), 0, p->stream, p->pyr.w[0], g.blur_p, g.blur_q, g.n_var, p->wq,
-                               reinterpret_cast<BlurCol*>(p->d_blur_tab));
-            CREATE_TRY(hipGetLastError());
-            CREATE_TRY(hipStreamSynchronize(p->stream));
-        }
-    }
-    if (p->fused && getenv("TINYORB_STAMPS")) {  // diagnostic builds only (tools/stamps.py)
-        CREATE_TRY(hipMalloc(&p->d_stamps, 32 * sizeof(unsigned long long)));
-        CREATE_TRY(hipMemset(p->d_stamps, 0, 32 * sizeof(unsigned long long)));
-    }
-    CREATE_TRY(hipHostMalloc(&p->h_count, kSingleCountWords * sizeof(uint32_t), hipHostMallocDefault));
-    memset(p->h_count, 0, kSingleCountWords * sizeof(uint32_t));
-    CREATE_TRY(hipMalloc(&p->d_single_done, sizeof(uint32_t)));
-    CREATE_TRY(hipMemset(p->d_single_done, 0, sizeof(uint32_t)));
-    CREATE_TRY(hipHostMalloc(&p->h_corners, cap * sizeof(CornerData), hipHostMallocDefault));
-    CREATE_TRY(hipHostMalloc(&p->h_desc, cap * sizeof(CornerDescriptor), hipHostMallocDefault));
-    {   // device-visible addresses of the staging arrays, once (null: the runtime cannot map them -> the three copies of orb.rs:537-547)
-        void *dc = nullptr, *dk = nullptr, *dd = nullptr;
-        if (hipHostGetDevicePointer(&dc, p->h_count, 0) == hipSuccess && hipHostGetDevicePointer(&dk, p->h_corners, 0) == hipSuccess &&
-            hipHostGetDevicePointer(&dd, p->h_desc, 0) == hipSuccess) {
-            p->dv_count = static_cast<uint32_t*>(dc);
-            p->dv_corners = static_cast<CornerData*>(dk);
-            p->dv_desc = static_cast<CornerDescriptor*>(dd);
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-#undef CREATE_TRY
+    create_staging_pointers(p);
     *out = p;
     return ORB_OK;
 }
@@ -1721,67 +1218,32 @@ void orb_program_destroy(OrbProgram* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    for (auto& sp : p->pending) {
-        (void)hipEventDestroy(sp.start);
-        (void)hipEventDestroy(sp.stop);
-    }
-    for (auto e : p->event_pool) (void)hipEventDestroy(e);
-    (void)hipFree(p->d_input);
-    (void)hipFree(p->d_input_alt);
-    for (hipEvent_t ev : p->in_uploaded)
+    const auto drop = [](hipEvent_t ev) {
         if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(p->d_gray);
-    (void)hipFree(p->d_blur);
-    (void)hipFree(p->d_blur_rowc);
-    for (int set = 0; set < 2; set++) {
-        (void)hipFree(p->out_counts[set]);
-        (void)hipFree(p->out_corners[set]);
-        (void)hipFree(p->out_desc[set]);
-    }
-    (void)hipFree(p->d_seg);
-    (void)hipFree(p->d_seg_counts);
-    (void)hipFree(p->d_seg_before);
-    for (int set = 0; set < 2; set++) (void)hipFree(p->d_nf_mask[set]);
-    (void)hipFree(p->d_score_planes);
-    (void)hipFree(p->d_prov_counts);
-    (void)hipFree(p->d_prov);
-    (void)hipFree(p->d_prov_scores);
-    (void)hipFree(p->d_xband_counts);
-    (void)hipFree(p->d_iseg);
-    (void)hipFree(p->d_iseg_scores);
-    (void)hipFree(p->d_iseg_counts);
-    (void)hipFree(p->d_iseg_before);
-    (void)hipFree(p->d_thr_key);
-    (void)hipFree(p->d_prov2_counts);
-    (void)hipFree(p->d_prov2);
-    (void)hipFree(p->d_prov2_scores);
-    (void)hipFree(p->d_pattern);
-    (void)hipFree(p->d_cos);
-    (void)hipFree(p->d_sin);
-    if (p->d_rot) (void)hipFree(p->d_rot);
-    (void)hipFree(p->d_blur_tab);
-    (void)hipFree(p->d_stamps);
+    };
+    for (auto& sp : p->pending) drop(sp.start), drop(sp.stop);
+    for (hipEvent_t ev : p->event_pool) drop(ev);
+    (void)hipFree(p->d_input);  // these two and the pack buffers: allocated on first use
+    (void)hipFree(p->d_input_alt);
+    for (hipEvent_t ev : p->in_uploaded) drop(ev);
+    free_bufs(program_buffers(p));
     for (int st = 0; st < ST_COUNT; st++) {
         free_stage_buffers(p, st);
-        if (p->stage[st].done) (void)hipEventDestroy(p->stage[st].done);
+        drop(p->stage[st].done);
     }
-    if (p->single_done_ev) (void)hipEventDestroy(p->single_done_ev);
-    if (p->place_copied) (void)hipEventDestroy(p->place_copied);
-    if (p->h_count) (void)hipHostFree(p->h_count);
-    if (p->d_single_done) (void)hipFree(p->d_single_done);
-    if (p->h_corners) (void)hipHostFree(p->h_corners);
-    if (p->h_desc) (void)hipHostFree(p->h_desc);
+    drop(p->single_done_ev);
+    drop(p->place_copied);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
-    if (p->order_event) (void)hipEventDestroy(p->order_event);
-    for (hipEvent_t ev : p->upload_events) (void)hipEventDestroy(ev);
-    if (p->upload_done) (void)hipEventDestroy(p->upload_done);
+    drop(p->order_event);
+    for (hipEvent_t ev : p->upload_events) drop(ev);
+    drop(p->upload_done);
     for (int set = 0; set < 2; set++) {
         (void)hipFree(p->d_pack_c[set]);
         (void)hipFree(p->d_pack_d[set]);
         if (p->h_pack_counts[set]) (void)hipHostFree(p->h_pack_counts[set]);
         if (p->h_pack_offsets[set]) (void)hipHostFree(p->h_pack_offsets[set]);
-        if (p->pack_event[set]) (void)hipEventDestroy(p->pack_event[set]);
+        drop(p->pack_event[set]);
     }
     delete p;
 }
@@ -1805,7 +1267,7 @@ static int pick_input_slab(OrbProgram* p, bool ahead, uint32_t* slab_out, uint8_
         if (p->in_async[slab]) HIP_TRY(p, hipEventSynchronize(p->in_uploaded[slab]));  // its upload must not land on top of this one
         *appended = false;
     }
-    if (slab == 1u && !p->d_input_alt) HIP_TRY(p, hipMalloc(&p->d_input_alt, p->frame_bytes));
+    if (slab == 1u && !p->d_input_alt) HIP_TRY(p, hipMalloc(&p->d_input_alt, p->plan.frame_bytes));
     *slab_out = slab;
     *dst = slab ? p->d_input_alt : p->d_input;
     return ORB_OK;
@@ -1822,8 +1284,8 @@ static void drop_newest_input(OrbProgram* p, bool appended) {
 
 int orb_write_input_image(OrbProgram* p, const uint8_t* bytes, size_t len) {
     if (!p) return ORB_EINVAL;
-    if (!bytes || len != p->frame_bytes)
-        return fail(p, ORB_EINVAL, "write_input_image: expected %zu bytes (4*W*H), got %zu", p->frame_bytes, len);
+    if (!bytes || len != p->plan.frame_bytes)
+        return fail(p, ORB_EINVAL, "write_input_image: expected %zu bytes (4*W*H), got %zu", p->plan.frame_bytes, len);
     HIP_TRY(p, hipSetDevice(p->device));
     uint32_t slab = 0;
     uint8_t* dst = nullptr;
@@ -1841,8 +1303,8 @@ int orb_write_input_image(OrbProgram* p, const uint8_t* bytes, size_t len) {
 
 int orb_write_input_image_pinned(OrbProgram* p, const uint8_t* bytes_pinned, size_t len) {
     if (!p) return ORB_EINVAL;
-    if (!bytes_pinned || len != p->frame_bytes)
-        return fail(p, ORB_EINVAL, "write_input_image_pinned: expected %zu bytes, got %zu", p->frame_bytes, len);
+    if (!bytes_pinned || len != p->plan.frame_bytes)
+        return fail(p, ORB_EINVAL, "write_input_image_pinned: expected %zu bytes, got %zu", p->plan.frame_bytes, len);
     HIP_TRY(p, hipSetDevice(p->device));
     uint32_t slab = 0;
     uint8_t* dst = nullptr;
@@ -1893,15 +1355,15 @@ int orb_extract_corners(OrbProgram* p, uint32_t* corner_count) {
     // What lies behind the stored records in the staging arrays is stale, as it is in the reference's buffers.
     void *dc = p->dv_count, *dk = p->dv_corners, *dd = p->dv_desc;
     const bool direct = !p->env.single_memcpy && dc != nullptr;
-    if (direct && p->fused && p->use_brief_t && p->oob == kOobZero && !p->env.single_split) {  // k_brief_one is built for the default policy
+    if (direct && p->plan.fused && p->plan.use_brief_t && p->plan.oob == kOobZero && !p->env.single_split) {  // k_brief_one is built for the default policy
         // Three launches per frame: one k_front per level, then k_brief_one -- slot prefix, both BRIEF kernels and the
         // write to host staging in one (a dependent launch costs 6-10 us whatever it does, and this call is the
         // reference's only shape).
         // Levels 0 and 1 in ONE launch when level 1 can build its rows from the frame (k_front_pair): RGBA or Y8 input, level 1 an
         // exact half of a level 0 whose width is a multiple of 8, both on full-width bands of 8 rows (the latency shape).
-        const Pyramid& py = p->pyr;
+        const Pyramid& py = p->plan.pyr;
         const bool pair_ok = py.depth >= 2u && py.w[0] == 2u * py.w[1] && py.h[0] == 2u * py.h[1] && (py.w[0] & 7u) == 0u &&
-                             p->tile_w_lvl[0] == 0u && p->tile_w_lvl[1] == 0u && p->band_rows_lvl[0] == 8u && p->band_rows_lvl[1] == 8u &&
+                             p->plan.tile_w_lvl[0] == 0u && p->plan.tile_w_lvl[1] == 0u && p->plan.band_rows_lvl[0] == 8u && p->plan.band_rows_lvl[1] == 8u &&
                              !p->d_stamps && !p->env.single_serial &&
                              // a band stages a row with one thread per four texels (level 1 from the frame: per four of ITS texels):
                              // both rows must fit the 1024 threads, else no thread would stage anything (orb_front_body.inc)
@@ -1916,12 +1378,12 @@ int orb_extract_corners(OrbProgram* p, uint32_t* corner_count) {
                 height /= 2u;
                 g[lvl] = front_geometry(py, lvl, gw ? gw : 8u, gh, 1, 8u, 0u);
                 if (gw == 0) g[lvl].gh = 0;
-                g[lvl].slot_base = p->bands.slot_base[lvl];
-                g[lvl].n_slots = p->bands.n_slots;
-                g[lvl].seg_cap = p->bands.seg_cap;
-                g[lvl].n_classes = p->seg_classes;
+                g[lvl].slot_base = p->plan.bands.slot_base[lvl];
+                g[lvl].n_slots = p->plan.bands.n_slots;
+                g[lvl].seg_cap = p->plan.bands.seg_cap;
+                g[lvl].n_classes = p->plan.seg_classes;
                 g[lvl].xcd_swizzle = 0u;
-                g[lvl].wq = p->wq;
+                g[lvl].wq = p->plan.wq;
                 g[lvl].fp = p->opt.fp_contract;
                 g[lvl].blur_tab = front_blur_tab(p, g[lvl]);
                 if (p->env.phase_mask >= 0) g[lvl].phase_mask = (uint32_t)p->env.phase_mask;
@@ -1932,9 +1394,9 @@ int orb_extract_corners(OrbProgram* p, uint32_t* corner_count) {
                 return fail(p, ORB_EINVAL, "internal: k_front_pair does not fit this frame (%u bytes of LDS, %u columns)", lds, py.w[0]);
             {
                 LaunchScope ls(p, s, KID_FUSED_L0);
-                const FrontPairLaunch PL{d_in, p->frame_bytes, p->d_gray, p->d_blur, p->d_blur_rowc, py, g[0], g[1], p->threshold, p->d_seg_counts, p->d_seg, s, lds,
-                                         p->input_y8};
-                const hipError_t e = kFrontPairLaunch[front_form(p->opt.fp_contract, !p->input_y8)](PL);
+                const FrontPairLaunch PL{d_in, p->plan.frame_bytes, p->d_gray, p->d_blur, p->d_blur_rowc, py, g[0], g[1], p->threshold, p->d_seg_counts, p->d_seg, s, lds,
+                                         p->plan.input_y8};
+                const hipError_t e = kFrontPairLaunch[front_form(p->opt.fp_contract, !p->plan.input_y8)](PL);
                 if (e != hipSuccess) return fail(p, ORB_EHIP, "k_front_pair failed to launch: %s", hipGetErrorString(e));
             }
             if (py.depth > 2u)
@@ -1946,8 +1408,8 @@ int orb_extract_corners(OrbProgram* p, uint32_t* corner_count) {
         {
             LaunchScope ls(p, s, KID_BRIEF_ONE);
 #define BRIEF_ONE_LAUNCH(ROT_)                                                                                                                                  \
-    hipLaunchKernelGGL(k_brief_one<ROT_>, dim3((unsigned)((cap + kBriefOneChunk - 1u) / kBriefOneChunk)), dim3(kBriefOneThreads), brieft_lds_bytes(p->brieft), s, \
-                       p->d_blur, p->d_blur_rowc, p->pyr, p->brieft, p->d_seg_counts, p->d_seg_before, p->d_seg, p->d_counts, p->d_corners, (uint32_t)cap,      \
+    hipLaunchKernelGGL(k_brief_one<ROT_>, dim3((unsigned)((cap + kBriefOneChunk - 1u) / kBriefOneChunk)), dim3(kBriefOneThreads), brieft_lds_bytes(p->plan.brieft), s, \
+                       p->d_blur, p->d_blur_rowc, p->plan.pyr, p->plan.brieft, p->d_seg_counts, p->d_seg_before, p->d_seg, p->d_counts, p->d_corners, (uint32_t)cap,      \
                        p->d_desc, BriefTables{p->d_pattern, p->d_cos, p->d_sin, p->d_rot}, static_cast<uint32_t*>(dc), static_cast<CornerData*>(dk),            \
                        static_cast<CornerDescriptor*>(dd), p->d_single_done, seq)
             switch (rot_form(p->opt.fp_contract)) {  // the rotation's form (OrbOptions::fp_contract)
@@ -2051,8 +1513,8 @@ int orb_read_descriptors(OrbProgram* p, CornerDescriptor* dst, size_t n) {
 int orb_extract_batch_device(OrbProgram* p, const uint8_t* frames_dev, uint32_t n_frames, void* stream) {
     if (!p) return ORB_EINVAL;
     if (!frames_dev) return fail(p, ORB_EINVAL, "frames_dev is NULL");
-    if (n_frames == 0 || n_frames > p->max_batch)
-        return fail(p, ORB_EINVAL, "n_frames %u outside 1..=max_batch (%u)", n_frames, p->max_batch);
+    if (n_frames == 0 || n_frames > p->plan.max_batch)
+        return fail(p, ORB_EINVAL, "n_frames %u outside 1..=max_batch (%u)", n_frames, p->plan.max_batch);
     HIP_TRY(p, hipSetDevice(p->device));
     hipStream_t s = stream ? (hipStream_t)stream : p->stream;
     if (int rc = run_pipeline(p, frames_dev, n_frames, s)) return rc;
@@ -2067,9 +1529,9 @@ int orb_extract_batch_device(OrbProgram* p, const uint8_t* frames_dev, uint32_t 
 // crossing PCIe (only the fused path can work on a sub-range of the batch).  Asynchronous.
 static int upload_chunked_and_run(OrbProgram* p, const uint8_t* frames_pinned, uint32_t n_frames, hipStream_t s) {
     const uint32_t chunk = 16;
-    const size_t total = p->frame_bytes * n_frames;
+    const size_t total = p->plan.frame_bytes * n_frames;
     if (!p->upload_done) HIP_TRY(p, hipEventCreateWithFlags(&p->upload_done, hipEventDisableTiming));
-    if (!p->fused || n_frames <= chunk) {
+    if (!p->plan.fused || n_frames <= chunk) {
         HIP_TRY(p, hipMemcpyAsync(p->d_input, frames_pinned, total, hipMemcpyHostToDevice, s));
         HIP_TRY(p, hipEventRecord(p->upload_done, s));
         return run_pipeline(p, p->d_input, n_frames, s);
@@ -2087,8 +1549,8 @@ static int upload_chunked_and_run(OrbProgram* p, const uint8_t* frames_pinned, u
     HIP_TRY(p, hipStreamWaitEvent(p->copy_stream, p->order_event, 0));
     for (uint32_t c = 0, f0 = 0; f0 < n_frames; c++, f0 += chunk) {
         const uint32_t m = n_frames - f0 < chunk ? n_frames - f0 : chunk;
-        HIP_TRY(p, hipMemcpyAsync(p->d_input + (size_t)f0 * p->frame_bytes, frames_pinned + (size_t)f0 * p->frame_bytes,
-                                  (size_t)m * p->frame_bytes, hipMemcpyHostToDevice, p->copy_stream));
+        HIP_TRY(p, hipMemcpyAsync(p->d_input + (size_t)f0 * p->plan.frame_bytes, frames_pinned + (size_t)f0 * p->plan.frame_bytes,
+                                  (size_t)m * p->plan.frame_bytes, hipMemcpyHostToDevice, p->copy_stream));
         HIP_TRY(p, hipEventRecord(p->upload_events[c], p->copy_stream));
         HIP_TRY(p, hipStreamWaitEvent(s, p->upload_events[c], 0));
         if (int rc = run_fused_range(p, p->d_input, f0, m, s)) return rc;
@@ -2101,8 +1563,8 @@ static int upload_chunked_and_run(OrbProgram* p, const uint8_t* frames_pinned, u
 int orb_extract_batch_pinned(OrbProgram* p, const uint8_t* frames_pinned, uint32_t n_frames) {
     if (!p) return ORB_EINVAL;
     if (!frames_pinned) return fail(p, ORB_EINVAL, "frames_pinned is NULL");
-    if (n_frames == 0 || n_frames > p->max_batch)
-        return fail(p, ORB_EINVAL, "n_frames %u outside 1..=max_batch (%u)", n_frames, p->max_batch);
+    if (n_frames == 0 || n_frames > p->plan.max_batch)
+        return fail(p, ORB_EINVAL, "n_frames %u outside 1..=max_batch (%u)", n_frames, p->plan.max_batch);
     HIP_TRY(p, hipSetDevice(p->device));
     if (int rc = ensure_input(p)) return rc;
     if (int rc = upload_chunked_and_run(p, frames_pinned, n_frames, p->stream)) return rc;
@@ -2123,15 +1585,15 @@ int orb_upload_sync(OrbProgram* p) {
 int orb_extract_batch_host(OrbProgram* p, const uint8_t* frames_host, uint32_t n_frames) {
     if (!p) return ORB_EINVAL;
     if (!frames_host) return fail(p, ORB_EINVAL, "frames_host is NULL");
-    if (n_frames == 0 || n_frames > p->max_batch)
-        return fail(p, ORB_EINVAL, "n_frames %u outside 1..=max_batch (%u)", n_frames, p->max_batch);
+    if (n_frames == 0 || n_frames > p->plan.max_batch)
+        return fail(p, ORB_EINVAL, "n_frames %u outside 1..=max_batch (%u)", n_frames, p->plan.max_batch);
     HIP_TRY(p, hipSetDevice(p->device));
     if (int rc = ensure_input(p)) return rc;
     hipStream_t s = p->stream;
     // Ingest (README.md:42 of the reference): the caller's frames are pinned in place for the
     // duration of the call and uploaded in chunks on a copy stream; the kernels of chunk c run while chunk c+1 is
     // still crossing PCIe.
-    const size_t total = p->frame_bytes * n_frames;
+    const size_t total = p->plan.frame_bytes * n_frames;
     const bool pinned = hipHostRegister(const_cast<uint8_t*>(frames_host), total, hipHostRegisterDefault) == hipSuccess;
     if (!pinned) (void)hipGetLastError();
     int rc = ORB_OK;
@@ -2269,7 +1731,7 @@ int orb_batch_pack(OrbProgram* p, uint32_t n_frames, void* stream) {
     if (n_frames == 0 || n_frames > p->last_batch) return fail(p, ORB_EINVAL, "pack: n_frames %u not in the last batch (%u)", n_frames, p->last_batch);
     HIP_TRY(p, hipSetDevice(p->device));
     const uint32_t set = p->cur_set;
-    const size_t B = p->max_batch, cap = p->cfg.max_features;
+    const size_t B = p->plan.max_batch, cap = p->cfg.max_features;
     if (!p->d_pack_c[set]) {
         HIP_TRY(p, hipMalloc(&p->d_pack_c[set], B * cap * sizeof(CornerData)));
         HIP_TRY(p, hipMalloc(&p->d_pack_d[set], B * cap * sizeof(CornerDescriptor)));
@@ -2312,9 +1774,9 @@ int orb_batch_pack_transport(OrbProgram* p, uint32_t set, uint32_t n_frames, voi
                              uint64_t* offsets_dev, void* stream) {
     if (!p) return ORB_EINVAL;
     if (set > 1u || !p->out_counts[set]) return fail(p, ORB_EINVAL, "pack_transport: output set %u does not exist", set);
-    if (n_frames == 0 || n_frames > p->max_batch) return fail(p, ORB_EINVAL, "pack_transport: n_frames %u outside 1..=max_batch (%u)", n_frames, p->max_batch);
+    if (n_frames == 0 || n_frames > p->plan.max_batch) return fail(p, ORB_EINVAL, "pack_transport: n_frames %u outside 1..=max_batch (%u)", n_frames, p->plan.max_batch);
     if (!dst_dev) return fail(p, ORB_EINVAL, "pack_transport: destination is NULL");
-    if (p->pyr.w[0] >= 65536u || p->pyr.h[0] >= 65536u) return fail(p, ORB_EINVAL, "pack_transport: coordinates do not fit 16 bits");
+    if (p->plan.pyr.w[0] >= 65536u || p->plan.pyr.h[0] >= 65536u) return fail(p, ORB_EINVAL, "pack_transport: coordinates do not fit 16 bits");
     HIP_TRY(p, hipSetDevice(p->device));
     hipStream_t s = stream ? (hipStream_t)stream : p->stream;
     const uint32_t cap = p->cfg.max_features;
@@ -2393,7 +1855,7 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     if (p->cfg.max_features > (1u << 23)) return fail(p, ORB_EINVAL, "match_consecutive: max_features must be <= 2^23");
     HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
-    if (!p->d_matches) HIP_TRY(p, hipMalloc(&p->d_matches, (size_t)p->max_batch * cap * sizeof(MatchRecord)));
+    if (!p->d_matches) HIP_TRY(p, hipMalloc(&p->d_matches, (size_t)p->plan.max_batch * cap * sizeof(MatchRecord)));
     if (p->match_valu < 0) {  // which matcher: 0 the block-scaled fp4 form on the matrix cores (default), 1 the vector unit, 2 the int8 form
         const char* e = getenv("TINYORB_MATCH_VALU");
         const char* e8 = getenv("TINYORB_MATCH_I8");
@@ -2403,7 +1865,7 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     // record of the batch.  A capacity beyond their key's index range, or no memory for the bytes, leaves the vector-unit kernel.
     const bool i8 = p->match_valu == 2;
     bool mfma = p->match_valu != 1 && cap <= (size_t)(i8 ? kMatchMaxCap : kMatch4MaxCap);
-    if (mfma && !p->d_desc8 && hipMalloc(&p->d_desc8, (size_t)p->max_batch * cap * (i8 ? 256u : 128u)) != hipSuccess) {
+    if (mfma && !p->d_desc8 && hipMalloc(&p->d_desc8, (size_t)p->plan.max_batch * cap * (i8 ? 256u : 128u)) != hipSuccess) {
         (void)hipGetLastError();
         p->d_desc8 = nullptr;
         mfma = false;
@@ -2510,7 +1972,7 @@ int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uin
     hipStream_t s;
     if (int rc = stage_open(p, kind.stage, stream, kStages[kind.stage].reads, &s)) return rc;  // the matches come from the matcher's stream
     // GV-2: coordinates centred on the level-0 image and scaled by 2 / max(W, H)
-    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    const uint32_t W = p->plan.pyr.w[0], H = p->plan.pyr.h[0];
     VerifyArgs a{};
     a.counts = p->d_counts;
     a.corners = p->d_corners;
@@ -2550,7 +2012,7 @@ int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uin
 
 // k_guide_bin's part of GuideArgs, for the guided and the band call: the frame's records into the cells of the program's grid
 GuideArgs guide_bin_args(const OrbProgram* p, const GridSearchState& g) {
-    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    const uint32_t W = p->plan.pyr.w[0], H = p->plan.pyr.h[0];
     GuideArgs a{};
     a.counts = p->d_counts;
     a.corners = p->d_corners;
@@ -2606,7 +2068,7 @@ LocArgs loc_args(const OrbProgram* p, const PnpState& l, const Params& g, uint32
 // power of two 1..256) that keeps the frame within kGuideMaxCells
 void guide_grid(OrbProgram* p) {
     if (p->guide_cell >= 0) return;
-    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
+    const uint32_t W = p->plan.pyr.w[0], H = p->plan.pyr.h[0];
     int sh = 3;
     if (const char* e = getenv("TINYORB_GUIDE_CELL")) {
         const int c = atoi(e);
@@ -2718,8 +2180,8 @@ int orb_match_epipolar(OrbProgram* p, uint32_t n_frames, const OrbBandParams* pa
     a.gw = bin.gw;
     a.gh = bin.gh;
     a.shift = bin.shift;
-    a.fw = (float)p->pyr.w[0];
-    a.fh = (float)p->pyr.h[0];
+    a.fw = (float)p->plan.pyr.w[0];
+    a.fh = (float)p->plan.pyr.h[0];
     a.srec = bin.srec;
     a.sdesc = bin.sdesc;
     a.cell_start = bin.cell_start;
@@ -3062,7 +2524,7 @@ int orb_place_frames(OrbProgram* p, uint32_t n_frames, const OrbPlaceParams* par
     const uint32_t n_ids = n_db + n_frames;
     // slices of a signature's words (orb_kernels_place.h): whole chunks, as many as the score buffer has room for beside each other
     const dim3 tiles((n_ids + kPlaceTile - 1u) / kPlaceTile, (n_frames + kPlaceTile - 1u) / kPlaceTile);
-    const size_t room = (size_t)p->max_batch * (ORB_PLACE_DB_MAX + p->max_batch) / ((size_t)n_frames * n_ids);
+    const size_t room = (size_t)p->plan.max_batch * (ORB_PLACE_DB_MAX + p->plan.max_batch) / ((size_t)n_frames * n_ids);
     const uint32_t chunks = (a.words + kPlaceChunk - 1u) / kPlaceChunk;
     const uint32_t wanted = std::max(1u, kPlaceWantedGroups / (tiles.x * tiles.y));
     const uint32_t most = (uint32_t)std::min<size_t>(std::min<size_t>(kPlaceMaxSlices, room), std::min(chunks, wanted));
@@ -3150,7 +2612,7 @@ int orb_track_consecutive(OrbProgram* p, uint32_t n_frames, const OrbTrackParams
         if (!t.max_distance) t.max_distance = 64u;
         if (t.ratio == 0.0f) t.ratio = 0.8f;
     }
-    const size_t cap = p->cfg.max_features, B = p->max_batch;
+    const size_t cap = p->cfg.max_features, B = p->plan.max_batch;
     if (p->track_global_keys < 0) {
         const char* e = getenv("TINYORB_TRACK_GLOBAL_KEYS");
         p->track_global_keys = (e && atoi(e) != 0) ? 1 : 0;
@@ -3255,28 +2717,28 @@ int orb_debug_frame_buffer(OrbProgram* p, void** frames) {
 }
 
 int orb_level_size(const OrbProgram* p, uint32_t level, uint32_t* width, uint32_t* height) {
-    if (!p || level >= p->pyr.depth) return ORB_EINVAL;
-    if (width) *width = p->pyr.w[level];
-    if (height) *height = p->pyr.h[level];
+    if (!p || level >= p->plan.pyr.depth) return ORB_EINVAL;
+    if (width) *width = p->plan.pyr.w[level];
+    if (height) *height = p->plan.pyr.h[level];
     return ORB_OK;
 }
 
 int orb_debug_read_plane(OrbProgram* p, uint32_t frame, int kind, uint32_t level, uint16_t* dst, size_t n_texels) {
     if (!p) return ORB_EINVAL;
-    if (!dst || level >= p->pyr.depth || frame >= p->last_batch || (kind != ORB_PLANE_GRAY && kind != ORB_PLANE_BLUR))
+    if (!dst || level >= p->plan.pyr.depth || frame >= p->last_batch || (kind != ORB_PLANE_GRAY && kind != ORB_PLANE_BLUR))
         return fail(p, ORB_EINVAL, "debug_read_plane: bad arguments");
-    if (!p->planes_valid || ((p->fused || (p->fused_i && !p->igrey_stored)) && kind == ORB_PLANE_GRAY && level == 0))
+    if (!p->planes_valid || ((p->plan.fused || (p->plan.fused_i && !p->plan.igrey_stored)) && kind == ORB_PLANE_GRAY && level == 0))
         return fail(p, ORB_ESTATE, "plane not materialised by the last call");
-    const size_t texels = (size_t)p->pyr.w[level] * p->pyr.h[level];
+    const size_t texels = (size_t)p->plan.pyr.w[level] * p->plan.pyr.h[level];
     if (n_texels != texels) return fail(p, ORB_EINVAL, "debug_read_plane: expected %zu texels", texels);
     if (int rc = orb_batch_sync(p)) return rc;
-    const uint16_t* base = (kind == ORB_PLANE_GRAY ? p->d_gray : p->d_blur) + (size_t)frame * p->pyr.stride + p->pyr.off[level];
+    const uint16_t* base = (kind == ORB_PLANE_GRAY ? p->d_gray : p->d_blur) + (size_t)frame * p->plan.pyr.stride + p->plan.pyr.off[level];
     HIP_TRY(p, hipMemcpy(dst, base, texels * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    if ((p->fused || p->fused_x) && kind == ORB_PLANE_BLUR && p->blur_qa[level] > 0) {
+    if ((p->plan.fused || p->plan.fused_x) && kind == ORB_PLANE_BLUR && p->plan.blur_qa[level] > 0) {
         // the fused path keeps columns [0, qa) of a blur level as one constant per row (k_front, phase C)
-        const uint32_t w = p->pyr.w[level], h = p->pyr.h[level], qa = p->blur_qa[level];
+        const uint32_t w = p->plan.pyr.w[level], h = p->plan.pyr.h[level], qa = p->plan.blur_qa[level];
         std::vector<uint16_t> rowc(h);
-        HIP_TRY(p, hipMemcpy(rowc.data(), p->d_blur_rowc + (size_t)frame * p->pyr.row_stride + p->pyr.row_off[level],
+        HIP_TRY(p, hipMemcpy(rowc.data(), p->d_blur_rowc + (size_t)frame * p->plan.pyr.row_stride + p->plan.pyr.row_off[level],
                              h * sizeof(uint16_t), hipMemcpyDeviceToHost));
         for (uint32_t y = 0; y < h; y++)
             for (uint32_t x = 0; x < qa && x < w; x++) dst[(size_t)y * w + x] = rowc[y];
@@ -3330,9 +2792,9 @@ int orb_debug_angle_code(OrbProgram* p, const float* cy, const float* cx, uint32
 int orb_debug_rot_table(OrbProgram* p, int16_t* dst, size_t n_entries, uint32_t* codes, uint32_t* pitch) {
     if (!p) return ORB_EINVAL;
     if (!p->d_rot) return fail(p, ORB_ESTATE, "this program has no rotated-pattern table");
-    const uint32_t n_codes = p->fused_i ? (p->opt.angle_bins ? p->opt.angle_bins : (uint32_t)ORB_ANGLE_STEPS_FULL) : (uint32_t)ORB_ANGLE_STEPS;
+    const uint32_t n_codes = p->plan.fused_i ? (p->opt.angle_bins ? p->opt.angle_bins : (uint32_t)ORB_ANGLE_STEPS_FULL) : (uint32_t)ORB_ANGLE_STEPS;
     if (codes) *codes = n_codes;
-    if (pitch) *pitch = p->fused_i ? p->itiles.pitch : (uint32_t)kNfPatchCols;
+    if (pitch) *pitch = p->plan.fused_i ? p->plan.itiles.pitch : (uint32_t)kNfPatchCols;
     const size_t n = std::min(n_entries, (size_t)n_codes * 512u);
     if (n && !dst) return fail(p, ORB_EINVAL, "dst is NULL");
     HIP_TRY(p, hipSetDevice(p->device));
@@ -3343,8 +2805,8 @@ int orb_debug_rot_table(OrbProgram* p, int16_t* dst, size_t n_entries, uint32_t*
 // The program's ready-made BlurCol table of one level, as k_blur_col_table wrote it (tinyorb.h).
 int orb_debug_blur_col_table(OrbProgram* p, uint32_t level, void* dst, size_t n_entries, uint32_t* n_var, uint32_t* blur_p, uint32_t* blur_q) {
     if (!p) return ORB_EINVAL;
-    if (level >= p->pyr.depth) return fail(p, ORB_EINVAL, "level %u of %u", level, p->pyr.depth);
-    FrontGeom g = front_geometry(p->pyr, level, 8u, 8u, 1, p->band_rows_lvl[level] ? p->band_rows_lvl[level] : (uint32_t)kFrontRows, p->tile_w_lvl[level]);
+    if (level >= p->plan.pyr.depth) return fail(p, ORB_EINVAL, "level %u of %u", level, p->plan.pyr.depth);
+    FrontGeom g = front_geometry(p->plan.pyr, level, 8u, 8u, 1, p->plan.band_rows_lvl[level] ? p->plan.band_rows_lvl[level] : (uint32_t)kFrontRows, p->plan.tile_w_lvl[level]);
     const BlurCol* tab = front_blur_tab(p, g);
     if (n_var) *n_var = tab ? g.n_var : 0u;
     if (blur_p) *blur_p = g.blur_p;
@@ -3388,7 +2850,7 @@ int orb_synth_frames_device(OrbProgram* p, uint8_t* frames_dev, uint32_t n_frame
     if (n_frames == 0) return fail(p, ORB_EINVAL, "n_frames is 0");
     HIP_TRY(p, hipSetDevice(p->device));
     if (!frames_dev) {
-        if (n_frames > p->max_batch) return fail(p, ORB_EINVAL, "n_frames %u > max_batch %u", n_frames, p->max_batch);
+        if (n_frames > p->plan.max_batch) return fail(p, ORB_EINVAL, "n_frames %u > max_batch %u", n_frames, p->plan.max_batch);
         if (int rc = ensure_input(p)) return rc;
         frames_dev = p->d_input;
         // the program's own slab is what extract_corners works on next: an upload still in flight on the copy stream
@@ -3397,13 +2859,13 @@ int orb_synth_frames_device(OrbProgram* p, uint8_t* frames_dev, uint32_t n_frame
             if (p->in_async[sl] && p->in_uploaded[sl]) HIP_TRY(p, hipEventSynchronize(p->in_uploaded[sl]));
         p->in_pending = 0u, p->in_last = 0u, p->in_async[0] = p->in_async[1] = false;
     }
-    const uint32_t W = p->pyr.w[0], H = p->pyr.h[0];
-    if (p->input_y8) flags |= ORB_SYN_Y8;  // a Y8 program's frames are one byte per pixel
-    if ((flags & ORB_SYN_Y8) && !p->input_y8) return fail(p, ORB_EINVAL, "ORB_SYN_Y8 needs a program created with ORB_FLAG_INPUT_Y8");
+    const uint32_t W = p->plan.pyr.w[0], H = p->plan.pyr.h[0];
+    if (p->plan.input_y8) flags |= ORB_SYN_Y8;  // a Y8 program's frames are one byte per pixel
+    if ((flags & ORB_SYN_Y8) && !p->plan.input_y8) return fail(p, ORB_EINVAL, "ORB_SYN_Y8 needs a program created with ORB_FLAG_INPUT_Y8");
     {
         LaunchScope ls(p, p->stream, KID_SYNTH);
         hipLaunchKernelGGL(k_synth, dim3((W + 255u) / 256u, H, n_frames), dim3(256), 0, p->stream, frames_dev,
-                           p->frame_bytes, W, H, seed0, flags);
+                           p->plan.frame_bytes, W, H, seed0, flags);
     }
     HIP_TRY(p, hipGetLastError());
     HIP_TRY(p, hipStreamSynchronize(p->stream));
