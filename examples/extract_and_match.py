@@ -81,3 +81,15 @@ with orb.OrbProgram(cfg) as prog:  # == OrbProgram { config, .. }.init() in the 
         where = ("entry %d of the database" % (who & 0x7FFFFFFF) if who & orb.ORB_PLACE_DB
                  else "frame %d of this batch" % who) if row["n"] else "nothing"
         print("batch B frame %d: %d of its %d signature bits are shared with %s" % (f, int(best["score"]), int(row["bits_set"]), where))
+
+    # --- closing a proposed loop: the place stage proposes frames of this batch, match_pairs and verify_pairs
+    # confirm them.  The caller reads the rows and decides which pairs to list; any pairs of the batch's frames may be listed.
+    prog.place_frames(2, min_gap=1)
+    rows = prog.place_read(0, 2)
+    proposed = [(f, int(c["frame"])) for f in range(2) for c in rows[f]["best"][:int(rows[f]["n"])] if c["frame"] < orb.ORB_PLACE_DB]
+    pairs = proposed or [(1, 0)]  # (query frame, target frame); backward, distant, consecutive and repeated pairs are all allowed
+    prog.match_pairs(pairs)
+    prog.verify_pairs(len(pairs), model=orb.ORB_PAIRS_HOMOGRAPHY)
+    for i, (q, t) in enumerate(pairs):
+        model, inlier = prog.verify_pairs_read(i, int(prog.batch_counts(2)[q]))
+        print("loop candidate %d -> %d: status %d, %d candidates, %d inliers" % (q, t, int(model["status"]), int(model["candidates"]), int(inlier.sum())))

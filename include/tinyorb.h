@@ -943,6 +943,46 @@ int orb_place_read(OrbProgram *p, uint32_t frame, OrbPlaceRow *rows, size_t n);
  * before any call, ORB_EINVAL for a frame outside its frames or dst NULL with n_bytes > 0. */
 int orb_place_signature(OrbProgram *p, uint32_t frame, uint8_t *dst, size_t n_bytes);
 
+/* ---- matching and verification of caller-listed frame pairs (NOT in the reference; definition MP-1..MP-5 in DESIGN.md section 27) ----
+ * orb_match_consecutive and the two verifiers work on the pairs (f, f + 1).  A loop candidate of orb_place_frames is a pair of
+ * frames far apart: these two calls match and verify any pairs of frames of the last batch that the caller lists.  Entry i of
+ * the list is pair i: frame `query` gives the queries, frame `target` the candidates.  Duplicates, backward pairs
+ * (query > target) and consecutive pairs are allowed; 1 <= n_pairs <= ORB_PAIRS_PER_FRAME * max_batch, query and target below
+ * the last batch's frame count, query != target.  Nothing is fed back into another stage, and no other stage's results are
+ * written. */
+typedef struct { uint32_t query, target; } OrbFramePair;            /* 8 bytes */
+#define ORB_PAIRS_PER_FRAME 4u           /* a call takes at most this many pairs per frame of max_batch (orb_place_frames' default `top`) */
+#define ORB_PAIRS_HOMOGRAPHY 0u          /* orb_verify_pairs: GV-1..GV-7, as orb_verify_consecutive */
+#define ORB_PAIRS_EPIPOLAR 1u            /* orb_verify_pairs: EP-1..EP-6, as orb_verify_epipolar */
+/* Row i of the result holds orb_match_consecutive's record for every stored keypoint of frame pairs_host[i].query against the
+ * stored keypoints of frame pairs_host[i].target (best index with ties to the smallest, distance, runner-up distance;
+ * ORB_MATCH_NONE / 0xffff without candidates): for a listed pair (f, f + 1) the row equals orb_match_read(f) byte for byte.
+ * ORB_EINVAL for a NULL program or list, n_pairs outside 1 .. ORB_PAIRS_PER_FRAME * max_batch, or an entry that breaks the rules
+ * above (the message names the first one); ORB_ESTATE when the program holds no batch.  Asynchronous on `stream` (NULL: as
+ * orb_match_guided chooses; the call does not change it), ordered behind its own last call and a running orb_verify_pairs on
+ * another stream.  The list is copied through a pinned buffer of the stage: pairs_host is the caller's again when the call
+ * returns.  Buffers of its own, allocated by the first call: the list, ORB_PAIRS_PER_FRAME * max_batch rows of max_features
+ * records, and -- on the matrix cores: max_features <= 16383, TINYORB_MATCH_VALU unset, memory at hand -- 128 bytes per record
+ * of a batch for the descriptors as fp4, apart from orb_match_consecutive's (TINYORB_MATCH_I8 has no form here and selects
+ * fp4). */
+int orb_match_pairs(OrbProgram *p, const OrbFramePair *pairs_host, uint32_t n_pairs, void *stream);
+/* Copy up to n records of row `pair` of the last orb_match_pairs call, the queries of that entry's `query` frame (synchronises);
+ * ORB_ESTATE before any call, ORB_EINVAL for a pair at or past its n_pairs or dst NULL with n > 0; n is clipped to
+ * max_features. */
+int orb_match_pairs_read(OrbProgram *p, uint32_t pair, OrbMatch *dst, size_t n);
+/* Verifies pairs 0 .. n_pairs - 1 of the last orb_match_pairs call on its rows and the two frames' keypoints: `model`
+ * ORB_PAIRS_HOMOGRAPHY gives pair i exactly what orb_verify_consecutive gives a consecutive pair, ORB_PAIRS_EPIPOLAR what
+ * orb_verify_epipolar gives, with the list index i wherever those definitions say "pair" (the draw stream's seed, the record's
+ * place) -- never a frame.  params NULL: the defaults.  The record's h maps (relates) frame `query` to frame `target`; one
+ * inlier byte per query of frame `query`.  ORB_ESTATE unless the last orb_match_pairs is of the current batch and output set;
+ * ORB_EINVAL for n_pairs outside 1 .. the pairs it matched, an unknown model or a parameter out of OrbVerifyParams' ranges.
+ * Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not change it), ordered behind the last
+ * orb_match_pairs and its own last call on another stream; an orb_match_pairs on another stream waits for it.  Result buffers
+ * of its own (allocated by the first call), shared by the two models: a call overwrites the results of the call before. */
+int orb_verify_pairs(OrbProgram *p, uint32_t n_pairs, uint32_t model, const OrbVerifyParams *params, void *stream);
+/* As orb_verify_read, for pair `pair` of the last orb_verify_pairs call (ORB_ESTATE before the first). */
+int orb_verify_pairs_read(OrbProgram *p, uint32_t pair, OrbPairModel *model, uint8_t *inlier, size_t n);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

@@ -37,6 +37,7 @@
 #include "orb_kernels_bridge.h"
 #include "orb_kernels_adjust.h"
 #include "orb_kernels_place.h"
+#include "orb_kernels_pairs.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -72,7 +73,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_PLACE, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -118,6 +119,9 @@ constexpr StageInfo kStages[ST_COUNT] = {
      1u << ST_LANDMARK},  // d_mland
     {"place_frames", "place_read",
      1u << ST_TRACK},     // d_tframe: the keyframe column (ORB_PLACE_KEYFRAMES)
+    {"match_pairs", "match_pairs_read", 0u},
+    {"verify_pairs", "verify_pairs_read",
+     1u << ST_PAIRS},     // d_plist, d_prows: the list and its rows
 };
 static_assert(kStages[ST_COUNT - 1].name != nullptr, "a row of kStages for every StageId");
 
@@ -150,6 +154,7 @@ static_assert(sizeof(OrbAdjustedPose) == kBaPoseWords * sizeof(uint32_t) && size
 static_assert(sizeof(OrbPlaceRow) == kPlaceRowWords * sizeof(uint32_t) && sizeof(OrbPlaceParams) == 32 && sizeof(OrbPlaceCandidate) == 8 &&
                   sizeof(OrbTrackFrame) == kPlaceFrameWords * sizeof(uint32_t) && offsetof(OrbTrackFrame, keyframe) == kPlaceKeyframeWord * sizeof(uint32_t),
               "place layouts");
+static_assert(sizeof(OrbFramePair) == 8 && offsetof(OrbFramePair, target) == 4, "pairs layouts");
 
 // The last call of a stage
 struct Stage {
@@ -168,6 +173,7 @@ struct VerifierState {
     unsigned long long* keys = nullptr; // [max_batch][kVerifyMaxHyp]
     uint32_t* model = nullptr;          // [max_batch] OrbPairModel
     uint8_t* mask = nullptr;            // [max_batch][max_features] inlier bytes
+    uint32_t* qcount = nullptr;         // orb_verify_pairs only: [pairs] the raw counter of each pair's query frame (k_verify_gather_pairs)
 };
 
 // The buffers of a grid search (k_guide_bin and a search kernel), one set for the guided and one for the band call
@@ -268,6 +274,12 @@ struct OrbProgram {
     uint32_t* d_prow = nullptr;           // [max_batch] OrbPlaceRow
     hipEvent_t place_copied = nullptr;    // behind the database's copy of the last call
     uint32_t place_sig_bytes = 0;         // of the last call
+    // orb_match_pairs and orb_verify_pairs (orb_kernels_pairs.h); P = ORB_PAIRS_PER_FRAME * max_batch
+    OrbFramePair* d_plist = nullptr;      // [P] the list of the last orb_match_pairs call
+    OrbFramePair* h_plist = nullptr;      // pinned staging of the same
+    MatchRecord* d_prows = nullptr;       // [P][max_features] row i: the queries of pair i's query frame
+    uint8_t* d_pdesc4 = nullptr;          // [max_batch][max_features][128] the descriptors as +-1 in fp4: the stage's own, apart from d_desc8
+    VerifierState pverify;                // orb_verify_pairs: every per-pair dimension is P
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -373,6 +385,7 @@ struct Buf {
     bool pinned;   // host memory (hipHostMalloc); else device memory
     bool cleared = false;        // a create-time buffer that is zeroed before any launch
     const char* name = nullptr;  // a create-time buffer's, for the message of a failed allocation
+    bool soft = false;           // a stage's buffer that its call allocates itself and can do without: listed to be freed
 };
 // A list of buffers of fixed capacity on the caller's stack, which says so when more are named than it holds
 template <int N>
@@ -485,6 +498,27 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&p->d_pscore, B * (ORB_PLACE_DB_MAX + B) * sizeof(uint32_t));
         add(&p->d_prow, B * sizeof(OrbPlaceRow));
         break;
+    case ST_PAIRS: {
+        const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
+        add(&p->d_plist, P * sizeof(OrbFramePair));
+        add(&p->h_plist, P * sizeof(OrbFramePair), true);
+        add(&p->d_prows, P * cap * sizeof(MatchRecord));
+        add(&p->d_pdesc4, B * cap * 128u);  // allocated by orb_match_pairs itself, for the fp4 matcher only, and softly
+        l.b[l.n - 1].soft = true;
+        break;
+    }
+    case ST_PAIRS_VERIFY: {
+        const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
+        VerifierState& v = p->pverify;
+        add(&v.rec, P * cap * sizeof(float4));
+        add(&v.cand, P * cap * sizeof(uint32_t));
+        add(&v.n, P * sizeof(uint32_t));
+        add(&v.keys, P * kVerifyMaxHyp * sizeof(unsigned long long));
+        add(&v.model, P * sizeof(OrbPairModel));
+        add(&v.mask, P * cap);
+        add(&v.qcount, P * sizeof(uint32_t));
+        break;
+    }
     }
     return l;
 }
@@ -499,6 +533,7 @@ int alloc_all_or_none(OrbProgram* p, int which, const char* who) {
     if (*l.b[0].slot) return ORB_OK;
     for (int i = 0; i < l.n; i++) {
         const Buf& b = l.b[i];
+        if (b.soft) continue;
         const hipError_t e = b.pinned ? hipHostMalloc(b.slot, b.bytes, hipHostMallocDefault) : hipMalloc(b.slot, b.bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
@@ -1848,6 +1883,25 @@ void orb_corner_level0_xy(const CornerData* c, float* x0, float* y0) {
     *y0 = ((float)c->y + 0.5f) * s - 0.5f;
 }
 
+}  // extern "C"
+
+namespace {
+
+// Which matcher, read once per program: 0 the block-scaled fp4 form on the matrix cores (default), 1 the vector unit
+// (TINYORB_MATCH_VALU=1), 2 the int8 form (TINYORB_MATCH_I8=1; orb_match_pairs has none and takes fp4)
+int match_form(OrbProgram* p) {
+    if (p->match_valu < 0) {
+        const char* e = getenv("TINYORB_MATCH_VALU");
+        const char* e8 = getenv("TINYORB_MATCH_I8");
+        p->match_valu = (e && atoi(e) != 0) ? 1 : ((e8 && atoi(e8) != 0) ? 2 : 0);
+    }
+    return p->match_valu;
+}
+
+}  // namespace
+
+extern "C" {
+
 int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     if (!p) return ORB_EINVAL;
     if (n_frames < 2u || n_frames > p->last_batch)
@@ -1856,11 +1910,7 @@ int orb_match_consecutive(OrbProgram* p, uint32_t n_frames, void* stream) {
     HIP_TRY(p, hipSetDevice(p->device));
     const size_t cap = p->cfg.max_features;
     if (!p->d_matches) HIP_TRY(p, hipMalloc(&p->d_matches, (size_t)p->plan.max_batch * cap * sizeof(MatchRecord)));
-    if (p->match_valu < 0) {  // which matcher: 0 the block-scaled fp4 form on the matrix cores (default), 1 the vector unit, 2 the int8 form
-        const char* e = getenv("TINYORB_MATCH_VALU");
-        const char* e8 = getenv("TINYORB_MATCH_I8");
-        p->match_valu = (e && atoi(e) != 0) ? 1 : ((e8 && atoi(e8) != 0) ? 2 : 0);
-    }
+    match_form(p);
     // The matrix-core matchers (orb_kernels_match.h) need the descriptors as signed elements: 128 (fp4) or 256 (int8) bytes per
     // record of the batch.  A capacity beyond their key's index range, or no memory for the bytes, leaves the vector-unit kernel.
     const bool i8 = p->match_valu == 2;
@@ -1957,27 +2007,31 @@ int read_stage(OrbProgram* p, int which, uint32_t index, void* head, const void*
     return ORB_OK;
 }
 
-int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
-    const char* const name = kStages[kind.stage].name;
+// What the consecutive verifiers and orb_verify_pairs share: the parameter block, the VerifyArgs and the three launches.  They differ
+// in the gather kernel, the state, the stage, the freshness test and the extent, which stay with the two callers below.
+
+// OrbVerifyParams checked, zero fields replaced by the defaults (params NULL: all defaults); `which` names the call in messages
+int verifier_params(OrbProgram* p, int which, const OrbVerifyParams* params, OrbVerifyParams* out) {
+    const char* const name = kStages[which].name;
     OrbVerifyParams v{};
     if (params) v = *params;
     if (v.reserved[0] || v.reserved[1] || v.reserved[2]) return fail(p, ORB_EINVAL, "%s: reserved words must be 0", name);
-    if (int rc = ransac_params(p, kind.stage, &v.hypotheses, &v.max_distance, &v.ratio)) return rc;
+    if (int rc = ransac_params(p, which, &v.hypotheses, &v.max_distance, &v.ratio)) return rc;
     if (!(std::isfinite(v.inlier_px) && v.inlier_px >= 0.0f)) return fail(p, ORB_EINVAL, "%s: inlier_px must be finite and >= 0", name);
-    if (int rc = stages_fresh(p, kind.stage, kStages[kind.stage].reads)) return rc;
-    const Stage& m = p->stage[ST_MATCH];
-    if (n_frames < 2u || n_frames > m.extent) return fail(p, ORB_EINVAL, "%s: need 2..%u frames (the matched ones)", name, m.extent);
     if (v.inlier_px == 0.0f) v.inlier_px = 3.0f;
-    const size_t cap = p->cfg.max_features;
-    hipStream_t s;
-    if (int rc = stage_open(p, kind.stage, stream, kStages[kind.stage].reads, &s)) return rc;  // the matches come from the matcher's stream
+    *out = v;
+    return ORB_OK;
+}
+
+// VerifyArgs over a set of buffers and the match rows the gather reads
+VerifyArgs verifier_args(const OrbProgram* p, const VerifierKind& kind, const VerifierState& st, const OrbVerifyParams& v, const MatchRecord* matches) {
     // GV-2: coordinates centred on the level-0 image and scaled by 2 / max(W, H)
     const uint32_t W = p->plan.pyr.w[0], H = p->plan.pyr.h[0];
     VerifyArgs a{};
     a.counts = p->d_counts;
     a.corners = p->d_corners;
-    a.matches = p->d_matches;
-    a.cap = (uint32_t)cap;
+    a.matches = matches;
+    a.cap = p->cfg.max_features;
     a.hyps = v.hypotheses;
     a.max_distance = v.max_distance;
     a.ratio = v.ratio;
@@ -1993,21 +2047,61 @@ int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uin
     a.keys = st.keys;
     a.model = st.model;
     a.mask = st.mask;
-    const uint32_t pairs = n_frames - 1u;
-    const auto launch = [&](int kid, void (*kernel)(VerifyArgs), dim3 grid) {
+    return a;
+}
+
+// The three launches over `pairs` rows: `gather` launches the caller's gather kernel (EP-1: GV-1 and GV-2 serve both verifiers), then
+// the kind's score and refine kernels on `tail` -- the gather's arguments, or those with the counters the rows are indexed by
+template <class Gather>
+void verifier_launches(OrbProgram* p, hipStream_t s, const VerifierKind& kind, bool profiled, const VerifyArgs& tail, uint32_t pairs, Gather gather) {
+    const auto scoped = [&](int kid, auto&& launch) {
         std::optional<LaunchScope> ls;
-        if (kind.profiled) ls.emplace(p, s, kid);
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, a);
+        if (profiled) ls.emplace(p, s, kid);
+        launch();
     };
-    launch(KID_VERIFY_GATHER, k_verify_gather, dim3(pairs));  // EP-1: GV-1 and GV-2 serve both verifiers
-    launch(KID_VERIFY_SCORE, kind.score, dim3(pairs, (v.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg));
-    launch(KID_VERIFY_REFINE, kind.refine, dim3(pairs));
+    scoped(KID_VERIFY_GATHER, gather);
+    scoped(KID_VERIFY_SCORE, [&] {
+        hipLaunchKernelGGL(kind.score, dim3(pairs, (tail.hyps + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, tail);
+    });
+    scoped(KID_VERIFY_REFINE, [&] { hipLaunchKernelGGL(kind.refine, dim3(pairs), dim3(256), 0, s, tail); });
+}
+
+int run_verifier(OrbProgram* p, const VerifierKind& kind, VerifierState& st, uint32_t n_frames, const OrbVerifyParams* params, void* stream) {
+    const char* const name = kStages[kind.stage].name;
+    OrbVerifyParams v;
+    if (int rc = verifier_params(p, kind.stage, params, &v)) return rc;
+    if (int rc = stages_fresh(p, kind.stage, kStages[kind.stage].reads)) return rc;
+    const Stage& m = p->stage[ST_MATCH];
+    if (n_frames < 2u || n_frames > m.extent) return fail(p, ORB_EINVAL, "%s: need 2..%u frames (the matched ones)", name, m.extent);
+    hipStream_t s;
+    if (int rc = stage_open(p, kind.stage, stream, kStages[kind.stage].reads, &s)) return rc;  // the matches come from the matcher's stream
+    const VerifyArgs a = verifier_args(p, kind, st, v, p->d_matches);
+    const uint32_t pairs = n_frames - 1u;
+    verifier_launches(p, s, kind, kind.profiled, a, pairs, [&] { hipLaunchKernelGGL(k_verify_gather, dim3(pairs), dim3(256), 0, s, a); });
     // The batch and output set stage_end records are the matcher's, which this call read: stage_fresh(p, m) above says they are the
     // same.  Guided and track calls check them before they read the homography verifier's models and inlier bytes, the band
     // call before it reads the epipolar verifier's models.
     if (int rc = stage_end(p, kind.stage, s, pairs)) return rc;
     p->last_stream = s;  // as the matcher does
     return ORB_OK;
+}
+
+// orb_verify_pairs: the same on the list and rows of the last orb_match_pairs, into the pairs stage's own state
+int run_pairs_verifier(OrbProgram* p, const VerifierKind& kind, uint32_t n_pairs, const OrbVerifyParams* params, void* stream) {
+    OrbVerifyParams v;
+    if (int rc = verifier_params(p, ST_PAIRS_VERIFY, params, &v)) return rc;
+    if (int rc = stages_fresh(p, ST_PAIRS_VERIFY, kStages[ST_PAIRS_VERIFY].reads)) return rc;
+    const Stage& m = p->stage[ST_PAIRS];
+    if (n_pairs < 1u || n_pairs > m.extent) return fail(p, ORB_EINVAL, "verify_pairs: need 1..%u pairs (the matched ones)", m.extent);
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_PAIRS_VERIFY, stream, kStages[ST_PAIRS_VERIFY].reads, &s)) return rc;
+    const VerifierState& st = p->pverify;
+    const VerifyArgs a = verifier_args(p, kind, st, v, p->d_prows);
+    VerifyArgs tail = a;
+    tail.counts = st.qcount;  // row i's queries are frame list[i].query's: the gather leaves that frame's counter at i
+    verifier_launches(p, s, kind, false, tail, n_pairs,
+                      [&] { hipLaunchKernelGGL(k_verify_gather_pairs, dim3(n_pairs), dim3(256), 0, s, a, (const OrbFramePair*)p->d_plist, st.qcount); });
+    return stage_end(p, ST_PAIRS_VERIFY, s, n_pairs);  // p->last_stream stays, as after a guided call
 }
 
 // k_guide_bin's part of GuideArgs, for the guided and the band call: the frame's records into the cells of the program's grid
@@ -2096,6 +2190,58 @@ int orb_verify_epipolar(OrbProgram* p, uint32_t n_frames, const OrbVerifyParams*
 
 int orb_verify_epipolar_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
     return p ? read_stage(p, ST_EPI, pair, model, p->epi.model, sizeof(OrbPairModel), inlier, p->epi.mask, 1, n) : ORB_EINVAL;
+}
+
+int orb_match_pairs(OrbProgram* p, const OrbFramePair* pairs_host, uint32_t n_pairs, void* stream) {
+    if (!p) return ORB_EINVAL;
+    if (!p->last_batch) return fail(p, ORB_ESTATE, "match_pairs before a batch");
+    const size_t cap = p->cfg.max_features, P = (size_t)ORB_PAIRS_PER_FRAME * p->plan.max_batch;
+    if (!pairs_host || n_pairs < 1u || n_pairs > P) return fail(p, ORB_EINVAL, "match_pairs: need a list of 1..%zu pairs", P);
+    if (cap > (1u << 23)) return fail(p, ORB_EINVAL, "match_pairs: max_features must be <= 2^23");
+    uint32_t last = 0;  // MP-1: the largest listed frame
+    for (uint32_t i = 0; i < n_pairs; i++) {
+        const OrbFramePair e = pairs_host[i];
+        if (e.query >= p->last_batch || e.target >= p->last_batch || e.query == e.target)
+            return fail(p, ORB_EINVAL, "match_pairs: entry %u is (%u, %u): two different frames below %u are needed", i, e.query, e.target, p->last_batch);
+        last = std::max(last, std::max(e.query, e.target));
+    }
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_PAIRS, stream, 0u, &s)) return rc;  // reads no other stage's results
+    // The matrix-core matcher needs the descriptors as fp4, 128 bytes per record of the batch, in a buffer of the stage's own.  A
+    // capacity beyond its key's index range, TINYORB_MATCH_VALU=1 or no memory for the bytes leaves the vector-unit kernel.
+    bool mfma = match_form(p) != 1 && cap <= (size_t)kMatch4MaxCap;
+    if (mfma && !p->d_pdesc4 && hipMalloc(&p->d_pdesc4, (size_t)p->plan.max_batch * cap * 128u) != hipSuccess) {
+        (void)hipGetLastError();
+        p->d_pdesc4 = nullptr;
+        mfma = false;
+    }
+    // MP-5: the list through the stage's pinned buffer, once the previous call's copy out of it is done
+    if (p->stage[ST_PAIRS].stream) HIP_TRY(p, hipEventSynchronize(p->stage[ST_PAIRS].done));
+    memcpy(p->h_plist, pairs_host, (size_t)n_pairs * sizeof(OrbFramePair));
+    HIP_TRY(p, hipMemcpyAsync(p->d_plist, p->h_plist, (size_t)n_pairs * sizeof(OrbFramePair), hipMemcpyHostToDevice, s));
+    if (mfma) {
+        hipLaunchKernelGGL(k_desc_expand4, dim3((unsigned)((cap + 31u) / 32u), last + 1u), dim3(256), 0, s, p->d_counts, p->d_desc, (uint32_t)cap, p->d_pdesc4);
+        hipLaunchKernelGGL(k_match_pairs_fp4, dim3(n_pairs, (unsigned)((cap + kMatchQueriesPerWg - 1u) / kMatchQueriesPerWg)), dim3(64 * kMatchWaves), 0, s,
+                           (const OrbFramePair*)p->d_plist, p->d_counts, p->d_pdesc4, (uint32_t)cap, p->d_prows);
+    } else {
+        hipLaunchKernelGGL(k_match_pairs, dim3(n_pairs, (unsigned)((cap + 64u * kMatchQ - 1u) / (64u * kMatchQ))), dim3(64), 0, s,
+                           (const OrbFramePair*)p->d_plist, p->d_counts, p->d_desc, (uint32_t)cap, p->d_prows);
+    }
+    return stage_end(p, ST_PAIRS, s, n_pairs);  // p->last_stream stays, as after a guided call
+}
+
+int orb_match_pairs_read(OrbProgram* p, uint32_t pair, OrbMatch* dst, size_t n) {
+    return p ? read_stage(p, ST_PAIRS, pair, nullptr, nullptr, 0, dst, p->d_prows, sizeof(OrbMatch), n) : ORB_EINVAL;
+}
+
+int orb_verify_pairs(OrbProgram* p, uint32_t n_pairs, uint32_t model, const OrbVerifyParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    if (model > ORB_PAIRS_EPIPOLAR) return fail(p, ORB_EINVAL, "verify_pairs: unknown model %u", model);
+    return run_pairs_verifier(p, model == ORB_PAIRS_EPIPOLAR ? kEpipolar : kHomography, n_pairs, params, stream);
+}
+
+int orb_verify_pairs_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
+    return p ? read_stage(p, ST_PAIRS_VERIFY, pair, model, p->pverify.model, sizeof(OrbPairModel), inlier, p->pverify.mask, 1, n) : ORB_EINVAL;
 }
 
 int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {

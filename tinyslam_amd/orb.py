@@ -96,6 +96,12 @@ ORB_PLACE_KEYFRAMES = 1
 ORB_PLACE_DB = 0x80000000
 ORB_PLACE_SIG_BYTES_MAX = 65536
 ORB_PLACE_DB_MAX = 1024
+# matching and verification of caller-listed frame pairs (orb_match_pairs, orb_verify_pairs): OrbFramePair (8 B),
+# the pairs a call takes per frame of max_batch, and the two models of orb_verify_pairs
+FRAME_PAIR_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4")])
+ORB_PAIRS_PER_FRAME = 4
+ORB_PAIRS_HOMOGRAPHY = 0
+ORB_PAIRS_EPIPOLAR = 1
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -123,6 +129,7 @@ EXPORTS = [
     "orb_bridge_consecutive", "orb_bridge_read",
     "orb_adjust_consecutive", "orb_adjust_read",
     "orb_place_frames", "orb_place_read", "orb_place_signature",
+    "orb_match_pairs", "orb_match_pairs_read", "orb_verify_pairs", "orb_verify_pairs_read",
 ]
 
 
@@ -335,6 +342,10 @@ def load_library(path=None):
     L.orb_place_frames.argtypes = [vp, u32, ctypes.POINTER(_PlaceParams), vp, u32, vp]
     L.orb_place_read.argtypes = [vp, u32, vp, sz]
     L.orb_place_signature.argtypes = [vp, u32, vp, sz]
+    L.orb_match_pairs.argtypes = [vp, vp, u32, vp]
+    L.orb_match_pairs_read.argtypes = [vp, u32, vp, sz]
+    L.orb_verify_pairs.argtypes = [vp, u32, u32, ctypes.POINTER(_VerifyParams), vp]
+    L.orb_verify_pairs_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -902,6 +913,48 @@ class OrbProgram:
         out = np.zeros(getattr(self, "_place", (0, ORB_PLACE_SIG_BYTES_MAX))[1], dtype=np.uint8)
         self._check(self._lib.orb_place_signature(self._handle(), frame, _ptr(out), len(out)))
         return out
+
+    def match_pairs(self, pairs, stream=None):
+        """Hamming-match caller-listed frame pairs of the last batch (not in the reference):
+        `pairs` is an (n, 2) integer array, a list of (query, target) tuples or a FRAME_PAIR_DTYPE array; row i of the result
+        holds match_consecutive's record for every stored keypoint of frame query_i against those of frame target_i.  At most
+        ORB_PAIRS_PER_FRAME * max_batch pairs, frames of the last batch, query != target; duplicates, backward and consecutive
+        pairs are allowed.  Asynchronous on `stream` (None: as match_guided chooses); `pairs` may be reused as soon as the call
+        returns."""
+        a = np.asarray(pairs)
+        if a.dtype != FRAME_PAIR_DTYPE:
+            a = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            if len(a) and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise OrbError(ORB_EINVAL, "match_pairs: frame indices must be 0 .. 2^32 - 1")
+            a = np.ascontiguousarray(a.astype(np.uint32)).view(FRAME_PAIR_DTYPE).reshape(-1)
+        a = np.ascontiguousarray(a.reshape(-1))
+        self._check(self._lib.orb_match_pairs(self._handle(), _ptr(a) if len(a) else None, len(a), ctypes.c_void_p(stream) if stream else None))
+
+    def match_pairs_read(self, pair, n):
+        """MATCH_DTYPE records of the first n queries of pair `pair` of the last match_pairs (its query frame's) -- synchronises."""
+        out = np.zeros(min(n, self.config.max_features), dtype=MATCH_DTYPE)
+        self._check(self._lib.orb_match_pairs_read(self._handle(), pair, _ptr(out) if len(out) else None, len(out)))
+        return out
+
+    def verify_pairs(self, n_pairs, model=ORB_PAIRS_HOMOGRAPHY, hypotheses=0, max_distance=0, ratio=0.0, inlier_px=0.0, seed=0, stream=None,
+                     reserved=(0, 0, 0)):
+        """Geometric verification of pairs 0 .. n_pairs - 1 of the last match_pairs: model
+        ORB_PAIRS_HOMOGRAPHY gives pair i what verify_consecutive gives a consecutive pair (GV-1..GV-7), ORB_PAIRS_EPIPOLAR what
+        verify_epipolar gives (EP-1..EP-6), with the list index i as the pair of the draw stream's seed.  Parameters and defaults
+        as verify_consecutive.  Asynchronous on `stream` (None: as match_guided chooses); raises OrbError(ORB_ESTATE) without a
+        match_pairs of the current batch and output set."""
+        prm = _VerifyParams(hypotheses, max_distance, float(np.float32(ratio)), float(np.float32(inlier_px)), seed & 0xFFFFFFFF,
+                            (ctypes.c_uint32 * 3)(*reserved))
+        self._check(self._lib.orb_verify_pairs(self._handle(), n_pairs, model, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def verify_pairs_read(self, pair, n):
+        """(record of VERIFY_MODEL_DTYPE, uint8[min(n, max_features)] inlier bytes of the queries of pair's query frame) of the last
+        verify_pairs -- synchronises.  The record's h maps (homography) or relates (F: x2^T F x1 = 0) level-0 keypoint coordinates
+        of the pair's query frame to its target frame."""
+        rec = np.zeros((), dtype=VERIFY_MODEL_DTYPE)
+        mask = np.zeros(min(n, self.config.max_features), dtype=np.uint8)
+        self._check(self._lib.orb_verify_pairs_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
+        return rec, mask
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
