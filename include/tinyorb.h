@@ -983,6 +983,60 @@ int orb_verify_pairs(OrbProgram *p, uint32_t n_pairs, uint32_t model, const OrbV
 /* As orb_verify_read, for pair `pair` of the last orb_verify_pairs call (ORB_ESTATE before the first). */
 int orb_verify_pairs_read(OrbProgram *p, uint32_t pair, OrbPairModel *model, uint8_t *inlier, size_t n);
 
+/* ---- a listed query's pose from its target's landmarks (NOT in the reference; definition LC-1..LC-7 in DESIGN.md section 28) ----
+ * A pair confirmed by orb_verify_pairs says that two frames show the same place, not where the query camera is in the map.  Here
+ * row i of the last orb_match_pairs sends every keypoint of entry i's `query` frame q to a keypoint of its `target` frame T; that
+ * keypoint is a view of a GOOD landmark of the last orb_landmarks_consecutive (when several see it, the one of T's segment with
+ * the smallest pair * capacity + slot), and the landmark is a 3D point in the frame and unit of T's segment.  Each such landmark,
+ * moved into camera T's frame, and the level-0 position of the query keypoint are a 3D-2D correspondence;
+ * orb_localize_consecutive's RANSAC and refit (with the list index in the draw stream's seed) give camera q relative to camera T
+ * in the unit of T's segment -- X_q = r X_T + t -- and, composed with T's pose, camera q in that segment's frame (pose_r,
+ * pose_t).  T must lie inside the landmarks call's frames; q may be any frame of the batch.  orb_verify_pairs is not read: the
+ * RANSAC is the outlier filter.  Binary32 arithmetic in a fixed order, no fused operations: a CPU restatement gives the same
+ * bits.  Nothing is fed back into another stage. */
+typedef struct {            /* zero-initialised is NOT valid: fx, fy must be > 0 */
+    float fx, fy, cx, cy;   /* the intrinsics given to orb_pose_consecutive */
+    float max_reproj_px;    /* frame q reprojection error an inlier may have (0: 2.0); finite, >= 0 */
+    uint32_t hypotheses;    /* minimal samples per list entry, 1..4096 (0: 512) */
+    uint32_t max_distance;  /* a record of the row is followed iff distance <= this (0: 64); 0..256 */
+    float ratio;            /* ... and distance < ratio * second (0: 0.8); finite, >= 0 */
+    uint32_t seed;          /* of the sampling; the same seed gives the same result */
+    uint32_t reserved[7];   /* must be 0 (ORB_EINVAL otherwise) */
+} OrbLoopParams;            /* 64 bytes */
+
+typedef struct {
+    float r[9];             /* row-major R, X_q = R X_T + t */
+    float t[3];             /* in units of the segment of frame T */
+    float step;             /* |t| */
+    float pose_r[9];        /* row-major R, X_q = R X_origin + t: camera q in the frame of `origin`; 0 when an entry is not finite */
+    float pose_t[3];        /* in units of that segment */
+    uint32_t origin;        /* the origin of frame T in the last orb_trajectory_consecutive */
+    uint32_t query_origin;  /* the origin of frame q there, 0xffffffff for a q above that call's frames: pose_* compares with q's own
+                             * OrbFramePose exactly when the two origins are equal */
+    uint32_t candidates;    /* 3D-2D correspondences */
+    uint32_t inliers;       /* of them: within max_reproj_px under the model written */
+    uint32_t hypothesis;    /* the winning sample */
+    uint32_t status;        /* ORB_LOCALIZE_*; NOMAP: T outside the landmarks call's frames, or its pose there not finite.  NOMAP, FEW
+                             * and DEGENERATE: every other word 0 */
+    uint32_t reserved[1];   /* 0 */
+} OrbLoopFix;               /* 128 bytes */
+
+/* Fixes of entries 0 .. n_pairs - 1 of the last orb_match_pairs call.  ORB_EINVAL for a NULL program or params, fx or fy not
+ * finite or not > 0, cx or cy not finite, another parameter out of range or a reserved word that is not 0; then ORB_ESTATE unless
+ * the last orb_match_pairs, orb_match_consecutive, orb_trajectory_consecutive and orb_landmarks_consecutive are all of the current
+ * batch and output set; then ORB_EINVAL for n_pairs outside 1 .. the pairs the last orb_match_pairs matched, or when the landmarks
+ * call's frames * max_features reach 2^32 - 1.  Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not
+ * change it), ordered behind those four stages' last calls and the last call of its own when they ran on another stream; the four
+ * wait for such a call on another stream before they overwrite what it reads.  Result buffers of its own (allocated by the first
+ * call: about 40 bytes per keypoint slot of ORB_PAIRS_PER_FRAME * max_batch rows and 32 KiB of keys per row): no other stage's
+ * results are ever written. */
+int orb_loop_pairs(OrbProgram *p, uint32_t n_pairs, const OrbLoopParams *params, void *stream);
+/* Copy the record of entry `pair` of the last orb_loop_pairs call (fix may be NULL) and up to n inlier bytes -- byte a is 1 iff
+ * keypoint a of the entry's query frame (indexed as orb_match_pairs_read) gave a correspondence that is an inlier of the model
+ * written -- to the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside its pairs or inliers NULL with
+ * n > 0. */
+int orb_loop_pairs_read(OrbProgram *p, uint32_t pair, OrbLoopFix *fix, uint8_t *inliers, size_t n);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

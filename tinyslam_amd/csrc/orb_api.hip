@@ -38,6 +38,7 @@
 #include "orb_kernels_adjust.h"
 #include "orb_kernels_place.h"
 #include "orb_kernels_pairs.h"
+#include "orb_kernels_loop.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -73,7 +74,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -122,6 +123,11 @@ constexpr StageInfo kStages[ST_COUNT] = {
     {"match_pairs", "match_pairs_read", 0u},
     {"verify_pairs", "verify_pairs_read",
      1u << ST_PAIRS},     // d_plist, d_prows: the list and its rows
+    {"loop_pairs", "loop_pairs_read",
+     1u << ST_PAIRS |     // d_plist, d_prows: the list and its rows
+     1u << ST_MATCH |     // d_matches: the views of a landmark
+     1u << ST_TRAJ |      // d_jframe
+     1u << ST_LANDMARK},  // d_mland
 };
 static_assert(kStages[ST_COUNT - 1].name != nullptr, "a row of kStages for every StageId");
 
@@ -155,6 +161,9 @@ static_assert(sizeof(OrbPlaceRow) == kPlaceRowWords * sizeof(uint32_t) && sizeof
                   sizeof(OrbTrackFrame) == kPlaceFrameWords * sizeof(uint32_t) && offsetof(OrbTrackFrame, keyframe) == kPlaceKeyframeWord * sizeof(uint32_t),
               "place layouts");
 static_assert(sizeof(OrbFramePair) == 8 && offsetof(OrbFramePair, target) == 4, "pairs layouts");
+static_assert(sizeof(OrbLoopFix) == kLcFixWords * sizeof(uint32_t) && sizeof(OrbLoopParams) == 64 && offsetof(OrbLoopFix, pose_r) == 13 * sizeof(uint32_t) &&
+                  offsetof(OrbLoopFix, origin) == 25 * sizeof(uint32_t) && kLcFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) && sizeof(OrbFramePair) == sizeof(uint2),
+              "loop layouts");
 
 // The last call of a stage
 struct Stage {
@@ -280,6 +289,9 @@ struct OrbProgram {
     MatchRecord* d_prows = nullptr;       // [P][max_features] row i: the queries of pair i's query frame
     uint8_t* d_pdesc4 = nullptr;          // [max_batch][max_features][128] the descriptors as +-1 in fp4: the stage's own, apart from d_desc8
     VerifierState pverify;                // orb_verify_pairs: every per-pair dimension is P
+    // orb_loop_pairs (orb_kernels_loop.h): fix is [P][32] OrbLoopFix, a row is a list entry, cand the candidate of each slot of its query frame
+    PnpState loop;
+    uint32_t* d_lowner = nullptr;         // [max_batch][max_features] the owner of every keypoint slot
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -517,6 +529,19 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&v.model, P * sizeof(OrbPairModel));
         add(&v.mask, P * cap);
         add(&v.qcount, P * sizeof(uint32_t));
+        break;
+    }
+    case ST_LOOP: {
+        const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
+        PnpState& l = p->loop;
+        add(&l.fix, P * sizeof(OrbLoopFix));
+        add(&l.reca, P * cap * sizeof(float4));
+        add(&l.recb, P * cap * sizeof(float4));
+        add(&l.cand, P * cap * sizeof(uint32_t));
+        add(&l.n, P * sizeof(uint32_t));
+        add(&l.keys, P * kVerifyMaxHyp * sizeof(unsigned long long));
+        add(&l.mask, P * cap);
+        add(&p->d_lowner, B * cap * sizeof(uint32_t));
         break;
     }
     }
@@ -2242,6 +2267,47 @@ int orb_verify_pairs(OrbProgram* p, uint32_t n_pairs, uint32_t model, const OrbV
 
 int orb_verify_pairs_read(OrbProgram* p, uint32_t pair, OrbPairModel* model, uint8_t* inlier, size_t n) {
     return p ? read_stage(p, ST_PAIRS_VERIFY, pair, model, p->pverify.model, sizeof(OrbPairModel), inlier, p->pverify.mask, 1, n) : ORB_EINVAL;
+}
+
+int orb_loop_pairs(OrbProgram* p, uint32_t n_pairs, const OrbLoopParams* params, void* stream) {
+    if (!p || !params) return p ? fail(p, ORB_EINVAL, "loop_pairs: params is NULL") : ORB_EINVAL;
+    OrbLoopParams g = *params;
+    for (uint32_t w : g.reserved)
+        if (w) return fail(p, ORB_EINVAL, "loop_pairs: reserved words must be 0");
+    if (int rc = check_intrinsics(p, ST_LOOP, g.fx, g.fy, g.cx, g.cy)) return rc;
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f)) return fail(p, ORB_EINVAL, "loop_pairs: max_reproj_px must be finite and >= 0");
+    if (int rc = ransac_params(p, ST_LOOP, &g.hypotheses, &g.max_distance, &g.ratio)) return rc;
+    if (int rc = stages_fresh(p, ST_LOOP, kStages[ST_LOOP].reads)) return rc;
+    const Stage* const st = p->stage;
+    if (n_pairs < 1u || n_pairs > st[ST_PAIRS].extent) return fail(p, ORB_EINVAL, "loop_pairs: need 1..%u pairs (the matched ones)", st[ST_PAIRS].extent);
+    // LC-1: L, the frames of the last landmarks call (a later matcher or trajectory call of fewer frames lowers it)
+    const uint32_t n_frames = std::min(st[ST_LANDMARK].extent + 1u, std::min(st[ST_MATCH].extent, st[ST_TRAJ].extent));
+    const size_t cap = p->cfg.max_features;
+    if ((unsigned long long)n_frames * cap >= 0xffffffffull)  // LC-2: a key p * cap + i below the "no owner" word
+        return fail(p, ORB_EINVAL, "loop_pairs: the landmarks call's frames * max_features must be below 2^32 - 1");
+    if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_LOOP, stream, kStages[ST_LOOP].reads, &s)) return rc;
+    LcArgs a{};
+    a.loc = loc_args(p, p->loop, g, kLcSeedSalt);
+    a.list = (const uint2*)p->d_plist;
+    a.rows = p->d_prows;
+    a.frames = p->d_jframe;
+    a.lms = p->d_mland;
+    a.n_frames = n_frames;
+    a.traj_frames = st[ST_TRAJ].extent;
+    a.owner = p->d_lowner;
+    HIP_TRY(p, hipMemsetAsync(p->d_lowner, 0xff, (size_t)n_frames * cap * sizeof(uint32_t), s));
+    if (n_frames > 1u)
+        hipLaunchKernelGGL(k_lc_index, dim3(n_frames - 1u, (unsigned)((cap + kLcThreads - 1u) / kLcThreads)), dim3(kLcThreads), 0, s, a);
+    hipLaunchKernelGGL(k_lc_gather, dim3(n_pairs), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_loc_score, dim3(n_pairs, (g.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a.loc);
+    hipLaunchKernelGGL(k_lc_refine, dim3(n_pairs), dim3(256), 0, s, a);
+    return stage_end(p, ST_LOOP, s, n_pairs);  // p->last_stream stays, as after a guided call
+}
+
+int orb_loop_pairs_read(OrbProgram* p, uint32_t pair, OrbLoopFix* fix, uint8_t* inliers, size_t n) {
+    return p ? read_stage(p, ST_LOOP, pair, fix, p->loop.fix, sizeof(OrbLoopFix), inliers, p->loop.mask, 1, n) : ORB_EINVAL;
 }
 
 int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {

@@ -102,6 +102,11 @@ FRAME_PAIR_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4")])
 ORB_PAIRS_PER_FRAME = 4
 ORB_PAIRS_HOMOGRAPHY = 0
 ORB_PAIRS_EPIPOLAR = 1
+# a listed query's pose from its target's landmarks (orb_loop_pairs): OrbLoopFix (128 B); status ORB_LOCALIZE_*
+LOOP_FIX_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("step", "<f4"), ("pose_r", "<f4", (9,)), ("pose_t", "<f4", (3,)),
+                           ("origin", "<u4"), ("query_origin", "<u4"), ("candidates", "<u4"), ("inliers", "<u4"), ("hypothesis", "<u4"),
+                           ("status", "<u4"), ("reserved", "<u4", (1,))])
+ORB_LOOP_NO_ORIGIN = 0xFFFFFFFF
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -130,6 +135,7 @@ EXPORTS = [
     "orb_adjust_consecutive", "orb_adjust_read",
     "orb_place_frames", "orb_place_read", "orb_place_signature",
     "orb_match_pairs", "orb_match_pairs_read", "orb_verify_pairs", "orb_verify_pairs_read",
+    "orb_loop_pairs", "orb_loop_pairs_read",
 ]
 
 
@@ -227,6 +233,16 @@ class _AdjustParams(ctypes.Structure):
 
 
 OrbAdjustParams = _AdjustParams
+
+
+class _LoopParams(ctypes.Structure):
+    """OrbLoopParams (64 bytes; fx and fy must be > 0, the other zero fields = the defaults)"""
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("max_reproj_px", ctypes.c_float), ("hypotheses", ctypes.c_uint32), ("max_distance", ctypes.c_uint32),
+                ("ratio", ctypes.c_float), ("seed", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+OrbLoopParams = _LoopParams
 
 
 class _PlaceParams(ctypes.Structure):
@@ -346,6 +362,8 @@ def load_library(path=None):
     L.orb_match_pairs_read.argtypes = [vp, u32, vp, sz]
     L.orb_verify_pairs.argtypes = [vp, u32, u32, ctypes.POINTER(_VerifyParams), vp]
     L.orb_verify_pairs_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_loop_pairs.argtypes = [vp, u32, ctypes.POINTER(_LoopParams), vp]
+    L.orb_loop_pairs_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -954,6 +972,27 @@ class OrbProgram:
         rec = np.zeros((), dtype=VERIFY_MODEL_DTYPE)
         mask = np.zeros(min(n, self.config.max_features), dtype=np.uint8)
         self._check(self._lib.orb_verify_pairs_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
+        return rec, mask
+
+    def loop_pairs(self, n_pairs, fx, fy, cx, cy, max_reproj_px=0.0, hypotheses=0, max_distance=0, ratio=0.0, seed=0, stream=None,
+                   reserved=(0,) * 7):
+        """The pose of each listed query frame from its target's landmarks (not in the reference; DESIGN.md section 28,
+        LC-1..LC-7): row i of the last match_pairs sends the keypoints of entry i's query frame to keypoints of its target frame,
+        those are views of GOOD landmarks of the last landmarks_consecutive, and localize_consecutive's RANSAC on the 3D-2D
+        correspondences gives the query camera relative to the target camera in the unit of the target's segment, and, composed
+        with the target's pose of the last trajectory_consecutive, in that segment's frame.  Zero parameters are the defaults; the
+        intrinsics are those given to pose_consecutive.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        prm = _LoopParams(float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
+                          float(np.float32(max_reproj_px)), hypotheses, max_distance, float(np.float32(ratio)), seed & 0xFFFFFFFF,
+                          (ctypes.c_uint32 * 7)(*reserved))
+        self._check(self._lib.orb_loop_pairs(self._handle(), n_pairs, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def loop_pairs_read(self, pair, n=None):
+        """(record of LOOP_FIX_DTYPE, uint8[min(n, max_features)]: the inlier bytes of the keypoint slots of entry `pair`'s query
+        frame; n None: max_features) of the last loop_pairs -- synchronises."""
+        rec = np.zeros((), dtype=LOOP_FIX_DTYPE)
+        mask = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=np.uint8)
+        self._check(self._lib.orb_loop_pairs_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
         return rec, mask
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
