@@ -73,8 +73,11 @@ def test_the_source_states_what_the_restatement_states():
         [12, 13, 22, 25, 26, 27, 28, 29, 30]  # the words k_lc_refine writes
     assert orb.FRAME_POSE_DTYPE.fields["origin"][1] // 4 == 14 and orb.FRAME_PAIR_DTYPE.names == ("query", "target")  # rec[14]; list[e].x, .y
     assert [orb.LANDMARK_DTYPE.fields[k][1] for k in ("flags", "views", "origin")] == [12, 16, 20]  # lo.w, hi.x's low half, hi.y
-    # the existing kernel and its solver's copy under a name of the stage's own
-    assert "k_loc_score" not in re.sub(r"//[^\n]*", "", kern) and "lc_solve6(part, aug, sol)" in kern and "verify_solve_n" not in re.sub(r"//[^\n]*", "", kern)
+    # the existing kernel is not redefined, and the fit is section 21's: no solver and no second refit in the loop or the bridge header
+    for text in (kern, open(os.path.join(CSRC, "orb_kernels_bridge.h")).read()):
+        code = re.sub(r"//[^\n]*", "", text)
+        assert "k_loc_score" not in code and "_solve6" not in text and "verify_solve_n" not in code and "loc_accumulate" not in code
+        assert code.count("loc_fit(") == 1
     call = api[api.index("int orb_loop_pairs("):api.index("int orb_loop_pairs_read(")]
     assert "hipLaunchKernelGGL(k_loc_score, dim3(n_pairs, (g.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a.loc);" in call
     assert "loc_args(p, p->loop, g, kLcSeedSalt)" in call

@@ -6,8 +6,9 @@
 // poses, `rounds` times; a closing pass evaluates the cost and checks every landmark again.  The first two cameras of a segment are
 // held, which fixes the gauge.  Every binary32 operation below is written out in the order the definition gives
 // (-ffp-contract=off, correctly rounded division, no square root), so the CPU restatement (tests/adjust_ref.py) reproduces every bit.
-// The arithmetic of LO-6, GV-6's solver, RP-4 and LM-4/LM-5 is written out again under names of its own: a second inlined copy of a
-// function of the other headers changes the register allocation of the kernels that use it (section 23).
+// LO-6's sums and update, GV-6's solver and RP-4's cofactors are the functions of orb_kernels_localize.h, orb_kernels_verify.h and
+// orb_kernels_pose.h, and a view is section 22's LmView.  LM-4's sums and LM-5's check stay here as lambdas: in
+// orb_kernels_landmark.h they are lambdas of k_lm_fuse, not functions, and made into functions there they change that kernel's code.
 //
 //   k_ba_index      grid (frames, ceil(cap / 256)): a thread per landmark slot; a GOOD landmark walks its views and puts its key
 //                   p * cap + i on every registered one with an integer atomicMin (the owners are set to 0xffffffff by a memset
@@ -24,10 +25,11 @@
 // Kernels are ordered by launch boundaries only.
 #pragma once
 #include "orb_kernels_landmark.h"
+#include "orb_kernels_localize.h"
 
 namespace orb {
 
-constexpr uint32_t kBaThreads = 256u;
+constexpr uint32_t kBaThreads = 256u;    // verify_solve_n reads the sums of [sum][256] partials
 constexpr uint32_t kBaFrameWords = 20u;  // OrbFramePose
 constexpr uint32_t kBaPoseWords = 16u;   // OrbAdjustedPose: r[9], t[3], cost_before, cost_after, observations, status
 constexpr uint32_t kBaSums = 28u;        // BA-4: LO-6's 27 and the cost
@@ -62,19 +64,6 @@ __device__ __forceinline__ void ba_keypoint(const BaArgs& a, uint32_t g, uint32_
     v = ((float)c.y + 0.5f) * s - 0.5f;
 }
 
-// RP-4's cofactors
-__device__ __forceinline__ void ba_cof(const float m[9], float c[9]) {
-    c[0] = m[4] * m[8] - m[5] * m[7];
-    c[1] = m[5] * m[6] - m[3] * m[8];
-    c[2] = m[3] * m[7] - m[4] * m[6];
-    c[3] = m[7] * m[2] - m[8] * m[1];
-    c[4] = m[8] * m[0] - m[6] * m[2];
-    c[5] = m[6] * m[1] - m[7] * m[0];
-    c[6] = m[1] * m[5] - m[2] * m[4];
-    c[7] = m[2] * m[3] - m[0] * m[5];
-    c[8] = m[0] * m[4] - m[1] * m[3];
-}
-
 // grid (n_frames, ceil(cap / kBaThreads)), block kBaThreads; the owners are set to kBaNone by a memset before
 __global__ __launch_bounds__(kBaThreads) void k_ba_index(BaArgs a) {
     const uint32_t p = blockIdx.x, i = blockIdx.y * kBaThreads + threadIdx.x;
@@ -106,97 +95,6 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_index(BaArgs a) {
         if (rec[17] == ORB_TRAJ_CHAINED && rec[14] == o) atomicMin(&a.owner[(size_t)g * a.cap + k], (uint32_t)slot);
         if (s + 1u < views) k = a.matches[(size_t)g * a.cap + k].index;  // g <= n_frames - 2
     }
-}
-
-// LO-6's two Jacobian rows of slot (Y, (u2, v2)) under (R, t) added to the 27 sums in GV-6's order, and the cost to the 28th
-__device__ __forceinline__ void ba_accumulate(float acc[kBaSums], const float R[9], const float t[3], const float4& Y, float u2, float v2,
-                                              const BaArgs& g) {
-    const float x = ((R[0] * Y.x + R[1] * Y.y) + R[2] * Y.z) + t[0];
-    const float y = ((R[3] * Y.x + R[4] * Y.y) + R[5] * Y.z) + t[1];
-    const float z = ((R[6] * Y.x + R[7] * Y.y) + R[8] * Y.z) + t[2];
-    const float ex = (g.fx * (x / z) + g.cx) - u2, ey = (g.fy * (y / z) + g.cy) - v2;
-    const float a = g.fx / z, b = -((g.fx * x / z) / z), c = g.fy / z, d = -((g.fy * y / z) / z);
-    const float J1[6] = {b * y, a * z - b * x, -(a * y), a, 0.0f, b};
-    const float J2[6] = {d * y - c * z, -(d * x), c * x, 0.0f, c, d};
-    int e = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = i; j < 6; j++, e++) acc[e] = acc[e] + (J1[i] * J1[j] + J2[i] * J2[j]);
-#pragma unroll
-    for (int i = 0; i < 6; i++) acc[21 + i] = acc[21 + i] + -(J1[i] * ex + J2[i] * ey);
-    acc[27] = acc[27] + (ex * ex + ey * ey);
-}
-
-// GV-6's solver at 6 x 7 on the reduced sums (column 0 of `part`), as section 23 wrote it out
-__device__ __forceinline__ uint32_t ba_solve6(const float (*part)[kBaThreads], float (*aug)[7], float* sol) {
-    constexpr int N = 6;
-    for (int i = 0, e = 0; i < N; i++)
-        for (int j = i; j < N; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
-    for (int i = 0; i < N; i++) aug[i][N] = part[N * (N + 1) / 2 + i][0];
-    uint32_t ok = 1u;
-    for (int c = 0; c < N && ok; c++) {
-        int piv = c;
-        float pmax = fabsf(aug[c][c]);
-        for (int r = c + 1; r < N; r++)
-            if (fabsf(aug[r][c]) > pmax) pmax = fabsf(aug[r][c]), piv = r;
-        if (pmax == 0.0f) {
-            ok = 0u;
-            break;
-        }
-        if (piv != c)
-            for (int q = 0; q < N + 1; q++) {
-                const float tmp = aug[c][q];
-                aug[c][q] = aug[piv][q];
-                aug[piv][q] = tmp;
-            }
-        for (int r = c + 1; r < N; r++) {
-            const float f = aug[r][c] / aug[c][c];
-            for (int q = c + 1; q < N + 1; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
-        }
-    }
-    if (ok)
-        for (int r = N - 1; r >= 0; r--) {
-            float s = aug[r][N];
-            for (int q = r + 1; q < N; q++) s = s - aug[r][q] * sol[q];
-            sol[r] = s / aug[r][r];
-            if (!isfinite(sol[r])) ok = 0u;
-        }
-    return ok;
-}
-
-// LO-6 on one lane: R <- (I + [omega]x) R, t <- (I + [omega]x) t + delta t, two polar steps of RP-4.  False: a non-finite entry or
-// an invalid polar det.
-__device__ __forceinline__ bool ba_update(const float* sol, float R[9], float t[3]) {
-    const float W[9] = {1.0f, -sol[2], sol[1], sol[2], 1.0f, -sol[0], -sol[1], sol[0], 1.0f};
-    float Rn[9], tn[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) Rn[3 * r + c] = (W[3 * r] * R[c] + W[3 * r + 1] * R[3 + c]) + W[3 * r + 2] * R[6 + c];
-        tn[r] = ((W[3 * r] * t[0] + W[3 * r + 1] * t[1]) + W[3 * r + 2] * t[2]) + sol[3 + r];
-    }
-    bool ok = true;
-#pragma unroll
-    for (int s = 0; s < 2; s++) {
-        float c[9];
-        ba_cof(Rn, c);
-        const float det = (Rn[0] * c[0] + Rn[1] * c[1]) + Rn[2] * c[2];
-        ok = ok && isfinite(det) && det > 0.0f;
-#pragma unroll
-        for (int k = 0; k < 9; k++) Rn[k] = 0.5f * (Rn[k] + c[k] / det);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        ok = ok && isfinite(Rn[k]);
-        R[k] = Rn[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        ok = ok && isfinite(tn[k]);
-        t[k] = tn[k];
-    }
-    return ok;
 }
 
 // BA-7: a cost as it is written
@@ -234,7 +132,7 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_motion(BaArgs a, uint32_t mod
         const float4 Y = a.X[key];
         float u2, v2;
         ba_keypoint(a, g, k, u2, v2);
-        ba_accumulate(acc, R, t, Y, u2, v2, a);
+        acc[27] = acc[27] + loc_accumulate(acc, R, t, Y, u2, v2, a);  // LO-6's 27 sums and the cost
     }
     if (cnt) atomicAdd(&s_count, cnt);
 #pragma unroll
@@ -264,8 +162,8 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_motion(BaArgs a, uint32_t mod
         }
         rec[12] = ba_cost_bits(part[27][0]);
     }
-    uint32_t ok = ba_solve6(part, aug, sol);
-    if (ok) ok = ba_update(sol, R, t) ? 1u : 0u;
+    uint32_t ok = verify_solve_n<6>(part, aug, sol);
+    if (ok) ok = loc_update(sol, R, t) ? 1u : 0u;
     if (ok) {
 #pragma unroll
         for (int e = 0; e < 9; e++) rec[e] = __float_as_uint(R[e]);
@@ -276,12 +174,8 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_motion(BaArgs a, uint32_t mod
     }
 }
 
-// A view of a landmark: camera g's current pose in the segment of origin o (LM-2) and keypoint k of frame g
-struct BaView {
-    float R[9], t[3], u, v;
-};
-
-// BA-3: the views of the participating landmark (p, i) in ascending frame order, `f(view)` on each; p + views <= n_frames
+// BA-3: the views of the participating landmark (p, i) in ascending frame order, `f(view)` on each, as lm_walk's but under camera
+// g's current pose in the segment of origin o (LM-2); p + views <= n_frames
 template <class Fn>
 __device__ __forceinline__ void ba_walk(const BaArgs& a, uint32_t p, uint32_t i, uint32_t views, uint32_t o, Fn&& f) {
     uint32_t k = i;
@@ -290,7 +184,7 @@ __device__ __forceinline__ void ba_walk(const BaArgs& a, uint32_t p, uint32_t i,
         if (k >= ba_nq(a, g)) break;
         const uint32_t* const rec = a.pose + (size_t)g * kBaPoseWords;
         const bool own = g == o;  // the origin's own record belongs to the segment before it
-        BaView w;
+        LmView w;
 #pragma unroll
         for (int q = 0; q < 9; q++) w.R[q] = own ? ((q & 3) == 0 ? 1.0f : 0.0f) : __uint_as_float(rec[q]);
 #pragma unroll
@@ -312,7 +206,7 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_structure(BaArgs a) {
     const uint32_t views = __float_as_uint(hi.x) & 0xffffu, o = __float_as_uint(hi.y);
     // LM-4
     float A00 = 0.0f, A01 = 0.0f, A02 = 0.0f, A11 = 0.0f, A12 = 0.0f, A22 = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
-    ba_walk(a, p, i, views, o, [&](const BaView& w) {
+    ba_walk(a, p, i, views, o, [&](const LmView& w) {
         const float d0 = (w.u - a.cx) / a.fx, d1 = (w.v - a.cy) / a.fy, d2 = 1.0f;
         const float w0 = (w.R[0] * d0 + w.R[3] * d1) + w.R[6] * d2;
         const float w1 = (w.R[1] * d0 + w.R[4] * d1) + w.R[7] * d2;
@@ -338,7 +232,7 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_structure(BaArgs a) {
     });
     const float m[9] = {A00, A01, A02, A01, A11, A12, A02, A12, A22};
     float C[9];
-    ba_cof(m, C);
+    pose_cof(m, C);
     const float det = (A00 * C[0] + A01 * C[1]) + A02 * C[2];
     const float X0 = ((C[0] * b0 + C[1] * b1) + C[2] * b2) / det;
     const float X1 = ((C[3] * b0 + C[4] * b1) + C[5] * b2) / det;
@@ -366,7 +260,7 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_check(BaArgs a) {
     }
     const uint32_t views = __float_as_uint(hi.x) & 0xffffu, o = __float_as_uint(hi.y);
     uint32_t inliers = 0u;
-    ba_walk(a, p, i, views, o, [&](const BaView& w) {  // LM-5
+    ba_walk(a, p, i, views, o, [&](const LmView& w) {  // LM-5
         const float yx = ((w.R[0] * X.x + w.R[1] * X.y) + w.R[2] * X.z) + w.t[0];
         const float yy = ((w.R[3] * X.x + w.R[4] * X.y) + w.R[5] * X.z) + w.t[1];
         const float yz = ((w.R[6] * X.x + w.R[7] * X.y) + w.R[8] * X.z) + w.t[2];

@@ -9,10 +9,10 @@
 // reproduces every bit.
 //
 //   k_br_gather   one workgroup of 256 per frame: the anchor from the frame records (BR-1), the landmark rows of the window in
-//                 order, the hops, the candidate (BR-2), compacted by a wave ballot and a workgroup prefix (as k_loc_gather) and
+//                 order, the hops, the candidate (BR-2), compacted by k_loc_gather's step (loc_compact, loc_candidate) and
 //                 clipped at the capacity; a frame that is no gap end leaves at once with a count of 0
 //   k_loc_score   of orb_kernels_localize.h, as it is, on the bridge's buffers with grid.x = frames (BR-3)
-//   k_br_refine   one workgroup per frame: k_loc_refine's steps through the loc_* functions and GV-6's solver at 6 x 7, the inlier bytes
+//   k_br_refine   one workgroup per frame: k_loc_refine's fit (loc_fit of orb_kernels_localize.h), the inlier bytes
 //                 by keypoint slot, then BR-5: the ratios' bits, the element of rank (m - 1) / 2 by k_traj_joint's radix select on
 //                 uint32 and the consistent count (integer atomics only: no result depends on an order), the per-frame fix record
 //   k_br_chain    one wave, the arithmetic on lane 0 (BR-6 is sequential by definition); all 64 lanes stage the frame and fix
@@ -74,7 +74,7 @@ __device__ __forceinline__ void br_compose(const float Ra[9], const float ta[3],
 __global__ __launch_bounds__(256) void k_br_gather(BrArgs a) {
     __shared__ uint32_t wave_n[4];
     const LocArgs& L = a.loc;
-    const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t g = blockIdx.x, tid = threadIdx.x;
     uint32_t T;
     if (br_anchor(a, g, T) != 2u) {  // uniform
         if (tid == 0u) L.n_cand[g] = 0u;
@@ -88,8 +88,6 @@ __global__ __launch_bounds__(256) void k_br_gather(BrArgs a) {
 #pragma unroll
     for (int k = 0; k < 3; k++) t[k] = __uint_as_float(recT[9 + k]);
     const CornerData* const cg = L.corners + (size_t)g * L.cap;
-    float4* const reca = L.reca + (size_t)g * L.cap;
-    float4* const recb = L.recb + (size_t)g * L.cap;
     const uint32_t first = T > a.window ? T - a.window : 0u;  // BR-2: p + window >= T
     uint32_t base = 0;
     for (uint32_t p = max(o, first); p < T; p++) {
@@ -118,22 +116,9 @@ __global__ __launch_bounds__(256) void k_br_gather(BrArgs a) {
                     }
                 }
             }
-            const unsigned long long bal = __ballot(keep);
-            const uint32_t before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(bal);
-            __syncthreads();
-            uint32_t off = base;
-            for (uint32_t w = 0; w < wave; w++) off += wave_n[w];
-            const uint32_t total = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
-            if (keep && off + before < L.cap) {  // the first `capacity` candidates
-                float x, y, z;
-                loc_transform(R, t, X.x, X.y, X.z, x, y, z);
-                const CornerData c = cg[k];
-                const float s = (float)(1u << (c.octave & 31u));
-                const float u2 = ((float)c.x + 0.5f) * s - 0.5f, v2 = ((float)c.y + 0.5f) * s - 0.5f;
-                reca[off + before] = make_float4(x, y, z, __uint_as_float(k));
-                recb[off + before] = make_float4(u2, v2, (u2 - L.cx) / L.fx, (v2 - L.cy) / L.fy);
-            }
+            uint32_t total;
+            const uint32_t slot = loc_compact(keep, base, wave_n, total);
+            if (keep && slot < L.cap) loc_candidate(L, g, slot, X, R, t, cg[k], __uint_as_float(k));  // the first `capacity` candidates
             base += total;
             __syncthreads();
         }
@@ -141,153 +126,23 @@ __global__ __launch_bounds__(256) void k_br_gather(BrArgs a) {
     if (tid == 0u) L.n_cand[g] = min(base, L.cap);
 }
 
-
-// GV-6's solver at 6 x 7, written out here: a second inlined copy of verify_solve_n<6> in this translation unit changes the register
-// allocation of k_loc_refine, which must stay as it is
-__device__ __forceinline__ uint32_t br_solve6(const float (*part)[256], float (*aug)[7], float* sol) {
-    constexpr int N = 6;
-    for (int i = 0, e = 0; i < N; i++)
-        for (int j = i; j < N; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
-    for (int i = 0; i < N; i++) aug[i][N] = part[N * (N + 1) / 2 + i][0];
-    uint32_t ok = 1u;
-    for (int c = 0; c < N && ok; c++) {
-        int piv = c;
-        float pmax = fabsf(aug[c][c]);
-        for (int r = c + 1; r < N; r++)
-            if (fabsf(aug[r][c]) > pmax) pmax = fabsf(aug[r][c]), piv = r;
-        if (pmax == 0.0f) {
-            ok = 0u;
-            break;
-        }
-        if (piv != c)
-            for (int q = 0; q < N + 1; q++) {
-                const float tmp = aug[c][q];
-                aug[c][q] = aug[piv][q];
-                aug[piv][q] = tmp;
-            }
-        for (int r = c + 1; r < N; r++) {
-            const float f = aug[r][c] / aug[c][c];
-            for (int q = c + 1; q < N + 1; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
-        }
-    }
-    if (ok)
-        for (int r = N - 1; r >= 0; r--) {
-            float s = aug[r][N];
-            for (int q = r + 1; q < N; q++) s = s - aug[r][q] * sol[q];
-            sol[r] = s / aug[r][r];
-            if (!isfinite(sol[r])) ok = 0u;
-        }
-    return ok;
-}
-
 // grid (frames), block 256; the inlier bytes are cleared by a memset before
 __global__ __launch_bounds__(256) void k_br_refine(BrArgs a) {
-    __shared__ float part[kLocSums][256];  // [sum][thread]: conflict-free columns
-    __shared__ float aug[6][7];
-    __shared__ float sol[6];
-    __shared__ float rowbuf[kLocRow];
-    __shared__ float cur[12];  // the model one lane made, for every thread: the winner, then each step's
-    __shared__ unsigned long long wkey[4];
-    __shared__ uint32_t s_ok, s_count;
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_join[2];  // m, consistent
     __shared__ uint32_t s_sel[2];   // the prefix found so far, the rank within it
     const LocArgs& L = a.loc;
-    const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
     uint32_t T;
     const uint32_t kind = br_anchor(a, g, T);  // uniform
     const uint32_t M = kind == 2u ? L.n_cand[g] : 0u;
     const float4* const reca = L.reca + (size_t)g * L.cap;
     const float4* const recb = L.recb + (size_t)g * L.cap;
-    unsigned long long best = 0ull;
-    if (M >= kLocSample)
-        for (uint32_t h = tid; h < L.hyps; h += 256u) best = max(best, L.keys[(size_t)g * kVerifyMaxHyp + h]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) best = max(best, (unsigned long long)__shfl_xor(best, off));
-    if (lane == 0u) wkey[wave] = best;
-    if (tid == 0u) s_count = 0u;
-    if (tid < 2u) s_join[tid] = 0u;
-    __syncthreads();
-    best = max(max(wkey[0], wkey[1]), max(wkey[2], wkey[3]));
-    const bool has_min = best != 0ull;  // uniform
-    const uint32_t h = has_min ? (kVerifyMaxHyp - 1u) - (uint32_t)(best & (kVerifyMaxHyp - 1u)) : 0u;
-    const uint32_t n_min = has_min ? (uint32_t)(best >> 12) - 1u : 0u;
-    float Rm[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, tm[3] = {0.f, 0.f, 0.f};
-    float Rc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, tc[3] = {0.f, 0.f, 0.f};
-    bool keep = false;
-    if (has_min) {
-        if (tid == 0u) {  // the winner rebuilt on one lane through an LDS row (valid: it scored a key)
-            float R[9], t[3];
-            (void)loc_model(reca, recb, M, lowbias32(L.seed_mix ^ g), h, rowbuf, R, t);
-#pragma unroll
-            for (int e = 0; e < 9; e++) cur[e] = R[e];
-#pragma unroll
-            for (int e = 0; e < 3; e++) cur[9 + e] = t[e];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 9; e++) Rc[e] = Rm[e] = cur[e];
-#pragma unroll
-        for (int e = 0; e < 3; e++) tc[e] = tm[e] = cur[9 + e];
-        bool fit = true;
-        for (uint32_t step = 0; step < kLocSteps && fit; step++) {  // LO-6; `fit` is uniform
-            float acc[kLocSums];
-#pragma unroll
-            for (uint32_t e = 0; e < kLocSums; e++) acc[e] = 0.0f;
-            for (uint32_t j = tid; j < M; j += 256u) {  // candidate j into partial sum j mod 256, ascending j; the inlier set is the winner's
-                const float4 Y = reca[j], k = recb[j];
-                if (loc_inlier(Rm, tm, Y.x, Y.y, Y.z, k.x, k.y, L)) loc_accumulate(acc, Rc, tc, Y, k, L);
-            }
-#pragma unroll
-            for (uint32_t e = 0; e < kLocSums; e++) part[e][tid] = acc[e];
-            __syncthreads();
-            for (uint32_t s = 128u; s >= 1u; s >>= 1) {  // pairwise tree, strides 128 .. 1
-                if (tid < s)
-                    for (uint32_t e = 0; e < kLocSums; e++) part[e][tid] = part[e][tid] + part[e][tid + s];
-                __syncthreads();
-            }
-            if (tid == 0u) {
-                uint32_t ok = br_solve6(part, aug, sol);
-                if (ok) {
-                    float R[9], t[3];
-#pragma unroll
-                    for (int e = 0; e < 9; e++) R[e] = Rc[e];
-#pragma unroll
-                    for (int e = 0; e < 3; e++) t[e] = tc[e];
-                    ok = loc_update(sol, R, t) ? 1u : 0u;
-#pragma unroll
-                    for (int e = 0; e < 9; e++) cur[e] = R[e];
-#pragma unroll
-                    for (int e = 0; e < 3; e++) cur[9 + e] = t[e];
-                }
-                s_ok = ok;
-            }
-            __syncthreads();
-            fit = s_ok != 0u;
-            if (fit) {
-#pragma unroll
-                for (int e = 0; e < 9; e++) Rc[e] = cur[e];
-#pragma unroll
-                for (int e = 0; e < 3; e++) tc[e] = cur[9 + e];
-            }
-            __syncthreads();  // s_ok and cur are read before the next step's lane writes them
-        }
-        if (fit) {
-            uint32_t n = 0;
-            for (uint32_t j = tid; j < M; j += 256u) {
-                const float4 Y = reca[j], k = recb[j];
-                n += loc_inlier(Rc, tc, Y.x, Y.y, Y.z, k.x, k.y, L) ? 1u : 0u;
-            }
-            atomicAdd(&s_count, n);
-        }
-        __syncthreads();
-        keep = fit && 16u * s_count >= 15u * n_min;  // GV-6's rule
-    }
-    float Rk[9], tk[3];
-#pragma unroll
-    for (int e = 0; e < 9; e++) Rk[e] = keep ? Rc[e] : Rm[e];
-#pragma unroll
-    for (int e = 0; e < 3; e++) tk[e] = keep ? tc[e] : tm[e];
+    if (tid < 2u) s_join[tid] = 0u;  // published by loc_fit's first barrier
+    const LocFit fit = loc_fit(L, g, M);
+    const bool has_min = fit.has_min, keep = fit.keep;
+    const float* const Rk = fit.R;
+    const float* const tk = fit.t;
     // BR-7: an inlier byte per keypoint slot of frame g (same-value byte stores cannot race)
     uint8_t* const mask = L.mask + (size_t)g * L.cap;
     if (has_min)
@@ -385,19 +240,11 @@ __global__ __launch_bounds__(256) void k_br_refine(BrArgs a) {
     }
     if (tid == 0u) {  // the fix record
         uint32_t* const out = L.fix + (size_t)g * kBrFixWords;
-#pragma unroll
-        for (int e = 0; e < 9; e++) out[e] = has_min ? __float_as_uint(Rk[e]) : 0u;
-#pragma unroll
-        for (int e = 0; e < 3; e++) out[9 + e] = has_min ? __float_as_uint(tk[e]) : 0u;
-        out[12] = has_min ? __float_as_uint(sqrtf((tk[0] * tk[0] + tk[1] * tk[1]) + tk[2] * tk[2])) : 0u;
+        loc_put_pose(out, fit);
         out[13] = has_min ? M : 0u;
-        out[14] = has_min ? (keep ? s_count : n_min) : 0u;
-        out[15] = h;
-        out[16] = kind != 2u ? (uint32_t)ORB_LOCALIZE_NOMAP
-                  : M < kLocSample ? (uint32_t)ORB_LOCALIZE_FEW
-                  : !has_min ? (uint32_t)ORB_LOCALIZE_DEGENERATE
-                  : keep ? (uint32_t)ORB_LOCALIZE_OK
-                         : (uint32_t)ORB_LOCALIZE_MINIMAL;
+        out[14] = fit.inliers;
+        out[15] = fit.h;
+        out[16] = loc_status(kind != 2u, M, has_min, keep);
         out[17] = m;
         out[18] = gam;
         out[19] = consistent;

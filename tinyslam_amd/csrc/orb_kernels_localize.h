@@ -14,9 +14,11 @@
 //                  would send a private array to scratch; the column permutation is twelve nibbles of a register pair); the 64
 //                  poses go through LDS to all four waves; the candidates pass through LDS in tiles of 256 and are read as
 //                  broadcasts, each wave every fourth one; one packed key per hypothesis (LO-5)
-//   k_loc_refine   one workgroup per pair: the best key, the winner rebuilt on one lane, four rounds of the 27 normal-equation sums
-//                  in GV-6's order and tree with GV-6's solve at 6 x 7 and the update on one lane (LO-6), the refit scored and kept
-//                  or not, the inlier bytes and the record (LO-7)
+//   k_loc_refine   one workgroup per pair: loc_fit -- the best key, the winner rebuilt on one lane, four rounds of the 27
+//                  normal-equation sums in GV-6's order and tree with GV-6's solve at 6 x 7 and the update on one lane (LO-6), the
+//                  refit scored and kept or not --, then the inlier bytes and the record (LO-7)
+// The bridge, the loop stage and the adjustment fit poses to 3D-2D correspondences too, and call what is here: k_loc_score as it
+// is, loc_fit, the gathers' loc_compact and loc_candidate, loc_accumulate and loc_update.  LO-6 is stated once.
 #pragma once
 #include "orb_kernels_pose.h"
 
@@ -235,12 +237,13 @@ __device__ __forceinline__ bool loc_inlier(const float R[9], const float t[3], f
     return z > 0.0f && ex * ex + ey * ey <= a.r2 * (z * z);
 }
 
-// LO-6: an inlier's two Jacobian rows in (omega, delta t) under (R, t), added to the 27 sums in GV-6's order
-__device__ __forceinline__ void loc_accumulate(float acc[kLocSums], const float R[9], const float t[3], const float4& Y, const float4& k,
-                                               const LocArgs& g) {
+// LO-6: the two Jacobian rows in (omega, delta t) of point Y seen at (u2, v2) under (R, t), added to the 27 sums in GV-6's order.
+// `g` gives the intrinsics (LocArgs, or the adjustment's BaArgs); returns the squared residual, which only BA-4 sums.
+template <class Intr>
+__device__ __forceinline__ float loc_accumulate(float* acc, const float R[9], const float t[3], const float4& Y, float u2, float v2, const Intr& g) {
     float x, y, z;
     loc_transform(R, t, Y.x, Y.y, Y.z, x, y, z);
-    const float ex = (g.fx * (x / z) + g.cx) - k.x, ey = (g.fy * (y / z) + g.cy) - k.y;
+    const float ex = (g.fx * (x / z) + g.cx) - u2, ey = (g.fy * (y / z) + g.cy) - v2;
     const float a = g.fx / z, b = -((g.fx * x / z) / z), c = g.fy / z, d = -((g.fy * y / z) / z);
     const float J1[6] = {b * y, a * z - b * x, -(a * y), a, 0.0f, b};
     const float J2[6] = {d * y - c * z, -(d * x), c * x, 0.0f, c, d};
@@ -251,6 +254,7 @@ __device__ __forceinline__ void loc_accumulate(float acc[kLocSums], const float 
         for (int j = i; j < 6; j++, e++) acc[e] = acc[e] + (J1[i] * J1[j] + J2[i] * J2[j]);
 #pragma unroll
     for (int i = 0; i < 6; i++) acc[21 + i] = acc[21 + i] + -(J1[i] * ex + J2[i] * ey);
+    return ex * ex + ey * ey;
 }
 
 // LO-6 on one lane: omega and delta t from the solution, R <- (I + [omega]x) R, t <- (I + [omega]x) t + delta t, two polar steps.
@@ -278,10 +282,38 @@ __device__ __forceinline__ bool loc_update(const float* sol, float R[9], float t
     return ok;
 }
 
+// The compaction step of the PnP gathers (k_loc_gather, k_br_gather, k_lc_gather), by all 256 threads on one tile of 256: the
+// slot of a kept candidate -- `base`, the kept ones of the waves below, the kept lanes below in its own wave -- and the tile's
+// total, by a wave ballot and a prefix over wave_n.  Its barrier publishes wave_n; the caller's barrier at the end of the tile
+// keeps the next tile's writes behind these reads.
+__device__ __forceinline__ uint32_t loc_compact(bool keep, uint32_t base, uint32_t wave_n[4], uint32_t& total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(keep);
+    const uint32_t before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t off = base;
+    for (uint32_t w = 0; w < wave; w++) off += wave_n[w];
+    total = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+    return off + before;
+}
+
+// LO-1: candidate `slot` of row `row`: the landmark X under (R, t) with the word w, the keypoint c in level-0 pixels
+// (orb_corner_level0_xy) and its ray
+__device__ __forceinline__ void loc_candidate(const LocArgs& a, uint32_t row, uint32_t slot, const float4& X, const float R[9], const float t[3],
+                                              const CornerData& c, float w) {
+    float x, y, z;
+    loc_transform(R, t, X.x, X.y, X.z, x, y, z);
+    const float s = (float)(1u << (c.octave & 31u));
+    const float u2 = ((float)c.x + 0.5f) * s - 0.5f, v2 = ((float)c.y + 0.5f) * s - 0.5f;
+    a.reca[(size_t)row * a.cap + slot] = make_float4(x, y, z, w);
+    a.recb[(size_t)row * a.cap + slot] = make_float4(u2, v2, (u2 - a.cx) / a.fx, (v2 - a.cy) / a.fy);
+}
+
 // grid (pairs), block 256
 __global__ __launch_bounds__(256) void k_loc_gather(LocArgs a) {
     __shared__ uint32_t wave_n[4];
-    const uint32_t pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t pair = blockIdx.x, tid = threadIdx.x;
     if (loc_nomap(a, pair)) {  // uniform
         if (tid == 0u) a.n_cand[pair] = 0u;
         return;
@@ -292,8 +324,6 @@ __global__ __launch_bounds__(256) void k_loc_gather(LocArgs a) {
     const float4* const pts = a.points + (size_t)(pair - 1u) * a.cap;
     const CornerData* const ct = a.corners + (size_t)(pair + 1u) * a.cap;
     const uint32_t* const pose = a.poses + (size_t)(pair - 1u) * kPoseWords;
-    float4* const reca = a.reca + (size_t)pair * a.cap;
-    float4* const recb = a.recb + (size_t)pair * a.cap;
     uint32_t* const cand_of = a.cand_of + (size_t)pair * a.cap;
     float R[9], t[3];
 #pragma unroll
@@ -316,23 +346,10 @@ __global__ __launch_bounds__(256) void k_loc_gather(LocArgs a) {
                 keep = k != kVerifyNone && k < n2 && d <= a.max_distance && (float)d < a.ratio * (float)second;
             }
         }
-        const unsigned long long bal = __ballot(keep);
-        const uint32_t before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = base;
-        for (uint32_t w = 0; w < wave; w++) off += wave_n[w];
-        const uint32_t total = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
-        if (i < n0) cand_of[i] = keep ? off + before : kVerifyNone;
-        if (keep) {
-            float x, y, z;
-            loc_transform(R, t, X.x, X.y, X.z, x, y, z);
-            const CornerData c = ct[k];
-            const float s = (float)(1u << (c.octave & 31u));
-            const float u2 = ((float)c.x + 0.5f) * s - 0.5f, v2 = ((float)c.y + 0.5f) * s - 0.5f;
-            reca[off + before] = make_float4(x, y, z, 0.0f);
-            recb[off + before] = make_float4(u2, v2, (u2 - a.cx) / a.fx, (v2 - a.cy) / a.fy);
-        }
+        uint32_t total;
+        const uint32_t slot = loc_compact(keep, base, wave_n, total);
+        if (i < n0) cand_of[i] = keep ? slot : kVerifyNone;
+        if (keep) loc_candidate(a, pair, slot, X, R, t, ct[k], 0.0f);
         base += total;
         __syncthreads();
     }
@@ -398,8 +415,39 @@ __global__ __launch_bounds__(256) void k_loc_score(LocArgs a) {
     }
 }
 
-// grid (pairs), block 256
-__global__ __launch_bounds__(256) void k_loc_refine(LocArgs a) {
+// What loc_fit found for one row, the same on every thread
+struct LocFit {
+    bool has_min, keep;   // a hypothesis scored a key; the refit replaced it
+    uint32_t h, n_min;    // the winner and its inlier count (0, 0 without one)
+    uint32_t inliers;     // of the kept model (0 without one)
+    float R[9], t[3];     // the kept model (zeros without one)
+};
+
+// LO-7's status; the bridge and the loop stage write the same five-way choice
+__device__ __forceinline__ uint32_t loc_status(bool nomap, uint32_t M, bool has_min, bool keep) {
+    return nomap ? (uint32_t)ORB_LOCALIZE_NOMAP
+           : M < kLocSample ? (uint32_t)ORB_LOCALIZE_FEW
+           : !has_min ? (uint32_t)ORB_LOCALIZE_DEGENERATE
+           : keep ? (uint32_t)ORB_LOCALIZE_OK
+                  : (uint32_t)ORB_LOCALIZE_MINIMAL;
+}
+
+// The first thirteen words of a fix record: r, t and the step |t| of the kept model, zeros without one
+__device__ __forceinline__ void loc_put_pose(uint32_t* out, const LocFit& f) {
+#pragma unroll
+    for (int e = 0; e < 9; e++) out[e] = f.has_min ? __float_as_uint(f.R[e]) : 0u;
+#pragma unroll
+    for (int e = 0; e < 3; e++) out[9 + e] = f.has_min ? __float_as_uint(f.t[e]) : 0u;
+    out[12] = f.has_min ? __float_as_uint(sqrtf((f.t[0] * f.t[0] + f.t[1] * f.t[1]) + f.t[2] * f.t[2])) : 0u;
+}
+
+// The fit of row `row` with M candidates (0 for a row without a map), called by all 256 threads of the three refine kernels
+// (k_loc_refine, k_br_refine, k_lc_refine) with the row's keys in place: the best key, the winner rebuilt on one lane, LO-6's four
+// rounds -- the 27 sums in GV-6's order and tree, GV-6's solve at 6 x 7 and the update on one lane --, the refit scored and kept
+// under GV-6's rule or not.  The draw stream is lowbias32(seed_mix ^ row), as k_loc_score's.  The shared arrays are the
+// function's own, as verify_refine_body's; its first barrier is unconditional and also publishes what the caller wrote to LDS
+// before the call.
+__device__ __forceinline__ LocFit loc_fit(const LocArgs& a, uint32_t row, uint32_t M) {
     __shared__ float part[kLocSums][256];  // [sum][thread]: conflict-free columns
     __shared__ float aug[6][7];
     __shared__ float sol[6];
@@ -407,14 +455,12 @@ __global__ __launch_bounds__(256) void k_loc_refine(LocArgs a) {
     __shared__ float cur[12];  // the model one lane made, for every thread: the winner, then each step's
     __shared__ unsigned long long wkey[4];
     __shared__ uint32_t s_ok, s_count;
-    const uint32_t pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const bool nomap = loc_nomap(a, pair);
-    const uint32_t M = nomap ? 0u : a.n_cand[pair];
-    const float4* const reca = a.reca + (size_t)pair * a.cap;
-    const float4* const recb = a.recb + (size_t)pair * a.cap;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const float4* const reca = a.reca + (size_t)row * a.cap;
+    const float4* const recb = a.recb + (size_t)row * a.cap;
     unsigned long long best = 0ull;
     if (M >= kLocSample)
-        for (uint32_t h = tid; h < a.hyps; h += 256u) best = max(best, a.keys[(size_t)pair * kVerifyMaxHyp + h]);
+        for (uint32_t h = tid; h < a.hyps; h += 256u) best = max(best, a.keys[(size_t)row * kVerifyMaxHyp + h]);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) best = max(best, (unsigned long long)__shfl_xor(best, off));
     if (lane == 0u) wkey[wave] = best;
@@ -430,7 +476,7 @@ __global__ __launch_bounds__(256) void k_loc_refine(LocArgs a) {
     if (has_min) {
         if (tid == 0u) {  // the winner rebuilt on one lane through an LDS row (valid: it scored a key)
             float R[9], t[3];
-            (void)loc_model(reca, recb, M, lowbias32(a.seed_mix ^ pair), h, rowbuf, R, t);
+            (void)loc_model(reca, recb, M, lowbias32(a.seed_mix ^ row), h, rowbuf, R, t);
 #pragma unroll
             for (int e = 0; e < 9; e++) cur[e] = R[e];
 #pragma unroll
@@ -448,7 +494,7 @@ __global__ __launch_bounds__(256) void k_loc_refine(LocArgs a) {
             for (uint32_t e = 0; e < kLocSums; e++) acc[e] = 0.0f;
             for (uint32_t j = tid; j < M; j += 256u) {  // candidate j into partial sum j mod 256, ascending j; the inlier set is the winner's
                 const float4 Y = reca[j], k = recb[j];
-                if (loc_inlier(Rm, tm, Y.x, Y.y, Y.z, k.x, k.y, a)) loc_accumulate(acc, Rc, tc, Y, k, a);
+                if (loc_inlier(Rm, tm, Y.x, Y.y, Y.z, k.x, k.y, a)) (void)loc_accumulate(acc, Rc, tc, Y, k.x, k.y, a);
             }
 #pragma unroll
             for (uint32_t e = 0; e < kLocSums; e++) part[e][tid] = acc[e];
@@ -495,41 +541,54 @@ __global__ __launch_bounds__(256) void k_loc_refine(LocArgs a) {
         __syncthreads();
         keep = fit && 16u * s_count >= 15u * n_min;  // GV-6's rule: the refit may lose a few marginal inliers, not 1/16 of them
     }
-    float Rk[9], tk[3];
+    LocFit f;
+    f.has_min = has_min;
+    f.keep = keep;
+    f.h = h;
+    f.n_min = n_min;
+    f.inliers = keep ? s_count : n_min;
 #pragma unroll
-    for (int e = 0; e < 9; e++) Rk[e] = keep ? Rc[e] : Rm[e];
+    for (int e = 0; e < 9; e++) f.R[e] = keep ? Rc[e] : Rm[e];
 #pragma unroll
-    for (int e = 0; e < 3; e++) tk[e] = keep ? tc[e] : tm[e];
-    // LO-7: an inlier byte per slot of frame f - 1: one write each
-    const uint32_t n0 = has_min ? min(a.counts[pair - 1u], a.cap) : 0u;  // has_min: the pair is not the first
-    const uint32_t* const cand_of = a.cand_of + (size_t)pair * a.cap;
-    uint8_t* const mask = a.mask + (size_t)pair * a.cap;
-    for (uint32_t i = tid; i < a.cap; i += 256u) {
+    for (int e = 0; e < 3; e++) f.t[e] = keep ? tc[e] : tm[e];
+    return f;
+}
+
+// An inlier byte per slot of row `row` under the kept model: one write each below the capacity, 0 at a slot that is no candidate
+// and at every slot from n on (n: the slots cand_of was written for)
+__device__ __forceinline__ void loc_slot_bytes(const LocArgs& a, uint32_t row, uint32_t n, const LocFit& f) {
+    const float4* const reca = a.reca + (size_t)row * a.cap;
+    const float4* const recb = a.recb + (size_t)row * a.cap;
+    const uint32_t* const cand_of = a.cand_of + (size_t)row * a.cap;
+    uint8_t* const mask = a.mask + (size_t)row * a.cap;
+    for (uint32_t i = threadIdx.x; i < a.cap; i += 256u) {
         uint8_t b = 0;
-        if (i < n0) {
+        if (i < n) {
             const uint32_t j = cand_of[i];
             if (j != kVerifyNone) {
                 const float4 Y = reca[j], k = recb[j];
-                b = loc_inlier(Rk, tk, Y.x, Y.y, Y.z, k.x, k.y, a) ? 1 : 0;
+                b = loc_inlier(f.R, f.t, Y.x, Y.y, Y.z, k.x, k.y, a) ? 1 : 0;
             }
         }
         mask[i] = b;
     }
-    if (tid == 0u) {  // the record
+}
+
+// grid (pairs), block 256
+__global__ __launch_bounds__(256) void k_loc_refine(LocArgs a) {
+    const uint32_t pair = blockIdx.x;
+    const bool nomap = loc_nomap(a, pair);
+    const uint32_t M = nomap ? 0u : a.n_cand[pair];
+    const LocFit f = loc_fit(a, pair, M);
+    // LO-7: an inlier byte per slot of frame f - 1
+    loc_slot_bytes(a, pair, f.has_min ? min(a.counts[pair - 1u], a.cap) : 0u, f);  // has_min: the pair is not the first
+    if (threadIdx.x == 0u) {  // the record
         uint32_t* const out = a.fix + (size_t)pair * kLocFixWords;
-#pragma unroll
-        for (int e = 0; e < 9; e++) out[e] = has_min ? __float_as_uint(Rk[e]) : 0u;
-#pragma unroll
-        for (int e = 0; e < 3; e++) out[9 + e] = has_min ? __float_as_uint(tk[e]) : 0u;
-        out[12] = has_min ? __float_as_uint(sqrtf((tk[0] * tk[0] + tk[1] * tk[1]) + tk[2] * tk[2])) : 0u;
-        out[13] = has_min ? M : 0u;
-        out[14] = has_min ? (keep ? s_count : n_min) : 0u;
-        out[15] = h;
-        out[16] = nomap ? (uint32_t)ORB_LOCALIZE_NOMAP
-                  : M < kLocSample ? (uint32_t)ORB_LOCALIZE_FEW
-                  : !has_min ? (uint32_t)ORB_LOCALIZE_DEGENERATE
-                  : keep ? (uint32_t)ORB_LOCALIZE_OK
-                         : (uint32_t)ORB_LOCALIZE_MINIMAL;
+        loc_put_pose(out, f);
+        out[13] = f.has_min ? M : 0u;
+        out[14] = f.inliers;
+        out[15] = f.h;
+        out[16] = loc_status(nomap, M, f.has_min, f.keep);
         out[17] = out[18] = out[19] = 0u;
     }
 }

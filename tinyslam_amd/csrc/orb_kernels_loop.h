@@ -11,11 +11,11 @@
 //                 walks them and puts its key p * cap + i on every registered one with an integer atomicMin (the owners are set to
 //                 0xffffffff by a memset before: no result depends on an order) (LC-2)
 //   k_lc_gather   one workgroup of 256 per list entry: the entry, its row, the owner of the matched keypoint, the landmark in
-//                 camera T's frame, the query keypoint and its ray (LC-3), compacted in the order of the query's slots by a wave
-//                 ballot and a workgroup prefix (as k_loc_gather), plus the candidate of every slot (or kVerifyNone)
+//                 camera T's frame, the query keypoint and its ray (LC-3), compacted in the order of the query's slots by
+//                 k_loc_gather's step (loc_compact, loc_candidate), plus the candidate of every slot (or kVerifyNone)
 //   k_loc_score   of orb_kernels_localize.h, as it is, on the stage's buffers with grid.x = list entries (LC-4)
-//   k_lc_refine   one workgroup per list entry: k_loc_refine's steps through the loc_* functions and GV-6's solver at 6 x 7, then
-//                 LC-5's compose, the inlier bytes by query slot and the record (LC-6)
+//   k_lc_refine   one workgroup per list entry: k_loc_refine's fit (loc_fit of orb_kernels_localize.h), then LC-5's compose, the
+//                 inlier bytes by query slot (loc_slot_bytes) and the record (LC-6)
 // Kernels are ordered by launch boundaries only.
 #pragma once
 #include "orb_kernels_localize.h"
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kLcThreads) void k_lc_index(LcArgs a) {
 __global__ __launch_bounds__(256) void k_lc_gather(LcArgs a) {
     __shared__ uint32_t wave_n[4];
     const LocArgs& L = a.loc;
-    const uint32_t e = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t e = blockIdx.x, tid = threadIdx.x;
     const uint2 qt = a.list[e];
     const uint32_t q = qt.x, T = qt.y;
     uint32_t o;
@@ -100,8 +100,6 @@ __global__ __launch_bounds__(256) void k_lc_gather(LcArgs a) {
     const MatchRecord* const row = a.rows + (size_t)e * L.cap;
     const uint32_t* const own = a.owner + (size_t)T * L.cap;
     const CornerData* const cq = L.corners + (size_t)q * L.cap;
-    float4* const reca = L.reca + (size_t)e * L.cap;
-    float4* const recb = L.recb + (size_t)e * L.cap;
     uint32_t* const cand_of = L.cand_of + (size_t)e * L.cap;
     uint32_t base = 0;
     for (uint32_t i0 = 0; i0 < nq; i0 += 256u) {
@@ -116,199 +114,39 @@ __global__ __launch_bounds__(256) void k_lc_gather(LcArgs a) {
                 keep = key != kLcNone;
             }
         }
-        const unsigned long long bal = __ballot(keep);
-        const uint32_t before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0u) wave_n[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = base;
-        for (uint32_t w = 0; w < wave; w++) off += wave_n[w];
-        const uint32_t total = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
-        if (i < nq) cand_of[i] = keep ? off + before : kVerifyNone;
-        if (keep) {  // off + before < n_q(q) <= cap
-            const float4 X = a.lms[2u * (size_t)key];
-            float x, y, z;
-            loc_transform(R, t, X.x, X.y, X.z, x, y, z);
-            const CornerData c = cq[i];
-            const float s = (float)(1u << (c.octave & 31u));
-            const float u2 = ((float)c.x + 0.5f) * s - 0.5f, v2 = ((float)c.y + 0.5f) * s - 0.5f;
-            reca[off + before] = make_float4(x, y, z, 0.0f);
-            recb[off + before] = make_float4(u2, v2, (u2 - L.cx) / L.fx, (v2 - L.cy) / L.fy);
-        }
+        uint32_t total;
+        const uint32_t slot = loc_compact(keep, base, wave_n, total);
+        if (i < nq) cand_of[i] = keep ? slot : kVerifyNone;
+        if (keep) loc_candidate(L, e, slot, a.lms[2u * (size_t)key], R, t, cq[i], 0.0f);  // slot < n_q(q) <= cap
         base += total;
         __syncthreads();
     }
     if (tid == 0u) L.n_cand[e] = base;
 }
 
-// GV-6's solver at 6 x 7, written out here: a second inlined copy of verify_solve_n<6> in this translation unit changes the register
-// allocation of k_loc_refine, which must stay as it is
-__device__ __forceinline__ uint32_t lc_solve6(const float (*part)[256], float (*aug)[7], float* sol) {
-    constexpr int N = 6;
-    for (int i = 0, e = 0; i < N; i++)
-        for (int j = i; j < N; j++, e++) aug[i][j] = aug[j][i] = part[e][0];
-    for (int i = 0; i < N; i++) aug[i][N] = part[N * (N + 1) / 2 + i][0];
-    uint32_t ok = 1u;
-    for (int c = 0; c < N && ok; c++) {
-        int piv = c;
-        float pmax = fabsf(aug[c][c]);
-        for (int r = c + 1; r < N; r++)
-            if (fabsf(aug[r][c]) > pmax) pmax = fabsf(aug[r][c]), piv = r;
-        if (pmax == 0.0f) {
-            ok = 0u;
-            break;
-        }
-        if (piv != c)
-            for (int q = 0; q < N + 1; q++) {
-                const float tmp = aug[c][q];
-                aug[c][q] = aug[piv][q];
-                aug[piv][q] = tmp;
-            }
-        for (int r = c + 1; r < N; r++) {
-            const float f = aug[r][c] / aug[c][c];
-            for (int q = c + 1; q < N + 1; q++) aug[r][q] = aug[r][q] - f * aug[c][q];
-        }
-    }
-    if (ok)
-        for (int r = N - 1; r >= 0; r--) {
-            float s = aug[r][N];
-            for (int q = r + 1; q < N; q++) s = s - aug[r][q] * sol[q];
-            sol[r] = s / aug[r][r];
-            if (!isfinite(sol[r])) ok = 0u;
-        }
-    return ok;
-}
-
 // grid (entries), block 256
 __global__ __launch_bounds__(256) void k_lc_refine(LcArgs a) {
-    __shared__ float part[kLocSums][256];  // [sum][thread]: conflict-free columns
-    __shared__ float aug[6][7];
-    __shared__ float sol[6];
-    __shared__ float rowbuf[kLocRow];
-    __shared__ float cur[12];  // the model one lane made, for every thread: the winner, then each step's
-    __shared__ unsigned long long wkey[4];
-    __shared__ uint32_t s_ok, s_count;
     const LocArgs& L = a.loc;
-    const uint32_t e = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t e = blockIdx.x;
     const uint2 qt = a.list[e];
     const uint32_t q = qt.x, T = qt.y;
     uint32_t o;
     float RT[9], tT[3];
     const bool nomap = !lc_target(a, T, o, RT, tT);  // uniform
     const uint32_t M = nomap ? 0u : L.n_cand[e];
-    const float4* const reca = L.reca + (size_t)e * L.cap;
-    const float4* const recb = L.recb + (size_t)e * L.cap;
-    unsigned long long best = 0ull;
-    if (M >= kLocSample)
-        for (uint32_t h = tid; h < L.hyps; h += 256u) best = max(best, L.keys[(size_t)e * kVerifyMaxHyp + h]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) best = max(best, (unsigned long long)__shfl_xor(best, off));
-    if (lane == 0u) wkey[wave] = best;
-    if (tid == 0u) s_count = 0u;
-    __syncthreads();
-    best = max(max(wkey[0], wkey[1]), max(wkey[2], wkey[3]));
-    const bool has_min = best != 0ull;  // uniform
-    const uint32_t h = has_min ? (kVerifyMaxHyp - 1u) - (uint32_t)(best & (kVerifyMaxHyp - 1u)) : 0u;
-    const uint32_t n_min = has_min ? (uint32_t)(best >> 12) - 1u : 0u;
-    float Rm[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, tm[3] = {0.f, 0.f, 0.f};
-    float Rc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, tc[3] = {0.f, 0.f, 0.f};
-    bool keep = false;
-    if (has_min) {
-        if (tid == 0u) {  // the winner rebuilt on one lane through an LDS row (valid: it scored a key)
-            float R[9], t[3];
-            (void)loc_model(reca, recb, M, lowbias32(L.seed_mix ^ e), h, rowbuf, R, t);
-#pragma unroll
-            for (int k = 0; k < 9; k++) cur[k] = R[k];
-#pragma unroll
-            for (int k = 0; k < 3; k++) cur[9 + k] = t[k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 9; k++) Rc[k] = Rm[k] = cur[k];
-#pragma unroll
-        for (int k = 0; k < 3; k++) tc[k] = tm[k] = cur[9 + k];
-        bool fit = true;
-        for (uint32_t step = 0; step < kLocSteps && fit; step++) {  // LO-6; `fit` is uniform
-            float acc[kLocSums];
-#pragma unroll
-            for (uint32_t k = 0; k < kLocSums; k++) acc[k] = 0.0f;
-            for (uint32_t j = tid; j < M; j += 256u) {  // candidate j into partial sum j mod 256, ascending j; the inlier set is the winner's
-                const float4 Y = reca[j], k = recb[j];
-                if (loc_inlier(Rm, tm, Y.x, Y.y, Y.z, k.x, k.y, L)) loc_accumulate(acc, Rc, tc, Y, k, L);
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < kLocSums; k++) part[k][tid] = acc[k];
-            __syncthreads();
-            for (uint32_t s = 128u; s >= 1u; s >>= 1) {  // pairwise tree, strides 128 .. 1
-                if (tid < s)
-                    for (uint32_t k = 0; k < kLocSums; k++) part[k][tid] = part[k][tid] + part[k][tid + s];
-                __syncthreads();
-            }
-            if (tid == 0u) {
-                uint32_t ok = lc_solve6(part, aug, sol);
-                if (ok) {
-                    float R[9], t[3];
-#pragma unroll
-                    for (int k = 0; k < 9; k++) R[k] = Rc[k];
-#pragma unroll
-                    for (int k = 0; k < 3; k++) t[k] = tc[k];
-                    ok = loc_update(sol, R, t) ? 1u : 0u;
-#pragma unroll
-                    for (int k = 0; k < 9; k++) cur[k] = R[k];
-#pragma unroll
-                    for (int k = 0; k < 3; k++) cur[9 + k] = t[k];
-                }
-                s_ok = ok;
-            }
-            __syncthreads();
-            fit = s_ok != 0u;
-            if (fit) {
-#pragma unroll
-                for (int k = 0; k < 9; k++) Rc[k] = cur[k];
-#pragma unroll
-                for (int k = 0; k < 3; k++) tc[k] = cur[9 + k];
-            }
-            __syncthreads();  // s_ok and cur are read before the next step's lane writes them
-        }
-        if (fit) {
-            uint32_t n = 0;
-            for (uint32_t j = tid; j < M; j += 256u) {
-                const float4 Y = reca[j], k = recb[j];
-                n += loc_inlier(Rc, tc, Y.x, Y.y, Y.z, k.x, k.y, L) ? 1u : 0u;
-            }
-            atomicAdd(&s_count, n);
-        }
-        __syncthreads();
-        keep = fit && 16u * s_count >= 15u * n_min;  // GV-6's rule
-    }
-    float Rk[9], tk[3];
-#pragma unroll
-    for (int k = 0; k < 9; k++) Rk[k] = keep ? Rc[k] : Rm[k];
-#pragma unroll
-    for (int k = 0; k < 3; k++) tk[k] = keep ? tc[k] : tm[k];
-    // LC-6: an inlier byte per keypoint slot of frame q: one write each (cand_of is written below n_q(q) of an entry that is not NOMAP)
-    const uint32_t nq = has_min ? lc_nq(a, q) : 0u;
-    const uint32_t* const cand_of = L.cand_of + (size_t)e * L.cap;
-    uint8_t* const mask = L.mask + (size_t)e * L.cap;
-    for (uint32_t i = tid; i < L.cap; i += 256u) {
-        uint8_t b = 0;
-        if (i < nq) {
-            const uint32_t j = cand_of[i];
-            if (j != kVerifyNone) {
-                const float4 Y = reca[j], k = recb[j];
-                b = loc_inlier(Rk, tk, Y.x, Y.y, Y.z, k.x, k.y, L) ? 1 : 0;
-            }
-        }
-        mask[i] = b;
-    }
-    if (tid == 0u) {  // the record
+    const LocFit f = loc_fit(L, e, M);
+    const bool has_min = f.has_min;
+    // LC-6: an inlier byte per keypoint slot of frame q (cand_of is written below n_q(q) of an entry that is not NOMAP)
+    loc_slot_bytes(L, e, has_min ? lc_nq(a, q) : 0u, f);
+    if (threadIdx.x == 0u) {  // the record
         uint32_t* const out = L.fix + (size_t)e * kLcFixWords;
         // LC-5: camera q in segment o's frame, R Rt after one polar step and R tT + t; zeros when an entry is not finite
         float Rp[9], tp[3];
 #pragma unroll
         for (int r = 0; r < 3; r++) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) Rp[3 * r + c] = (Rk[3 * r] * RT[c] + Rk[3 * r + 1] * RT[3 + c]) + Rk[3 * r + 2] * RT[6 + c];
-            tp[r] = ((Rk[3 * r] * tT[0] + Rk[3 * r + 1] * tT[1]) + Rk[3 * r + 2] * tT[2]) + 1.0f * tk[r];
+            for (int c = 0; c < 3; c++) Rp[3 * r + c] = (f.R[3 * r] * RT[c] + f.R[3 * r + 1] * RT[3 + c]) + f.R[3 * r + 2] * RT[6 + c];
+            tp[r] = ((f.R[3 * r] * tT[0] + f.R[3 * r + 1] * tT[1]) + f.R[3 * r + 2] * tT[2]) + 1.0f * f.t[r];
         }
         traj_polar_step(Rp);
         bool fin = has_min;
@@ -316,11 +154,7 @@ __global__ __launch_bounds__(256) void k_lc_refine(LcArgs a) {
         for (int k = 0; k < 9; k++) fin = fin && isfinite(Rp[k]);
 #pragma unroll
         for (int k = 0; k < 3; k++) fin = fin && isfinite(tp[k]);
-#pragma unroll
-        for (int k = 0; k < 9; k++) out[k] = has_min ? __float_as_uint(Rk[k]) : 0u;
-#pragma unroll
-        for (int k = 0; k < 3; k++) out[9 + k] = has_min ? __float_as_uint(tk[k]) : 0u;
-        out[12] = has_min ? __float_as_uint(sqrtf((tk[0] * tk[0] + tk[1] * tk[1]) + tk[2] * tk[2])) : 0u;
+        loc_put_pose(out, f);
 #pragma unroll
         for (int k = 0; k < 9; k++) out[13 + k] = fin ? __float_as_uint(Rp[k]) : 0u;
 #pragma unroll
@@ -328,13 +162,9 @@ __global__ __launch_bounds__(256) void k_lc_refine(LcArgs a) {
         out[25] = has_min ? o : 0u;
         out[26] = has_min ? (q < a.traj_frames ? a.frames[(size_t)q * kLcFrameWords + 14u] : kLcNone) : 0u;
         out[27] = has_min ? M : 0u;
-        out[28] = has_min ? (keep ? s_count : n_min) : 0u;
-        out[29] = h;
-        out[30] = nomap ? (uint32_t)ORB_LOCALIZE_NOMAP
-                  : M < kLocSample ? (uint32_t)ORB_LOCALIZE_FEW
-                  : !has_min ? (uint32_t)ORB_LOCALIZE_DEGENERATE
-                  : keep ? (uint32_t)ORB_LOCALIZE_OK
-                         : (uint32_t)ORB_LOCALIZE_MINIMAL;
+        out[28] = f.inliers;
+        out[29] = f.h;
+        out[30] = loc_status(nomap, M, has_min, f.keep);
         out[31] = 0u;
     }
 }
