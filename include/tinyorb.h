@@ -1036,6 +1036,76 @@ int orb_loop_pairs(OrbProgram *p, uint32_t n_pairs, const OrbLoopParams *params,
  * written -- to the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside its pairs or inliers NULL with
  * n > 0. */
 int orb_loop_pairs_read(OrbProgram *p, uint32_t pair, OrbLoopFix *fix, uint8_t *inliers, size_t n);
+/* For tests: the device address of the OrbLoopFix records [ORB_PAIRS_PER_FRAME * max_batch] that orb_loop_pairs writes and
+ * orb_loop_pairs_read and orb_graph_pairs read.  The caller orders its own writes.  ORB_ESTATE until a loop call has run. */
+int orb_debug_loop_buffer(OrbProgram *p, void **fixes);
+
+/* ---- pose-graph correction from the loop fixes (NOT in the reference; definition PG-1..PG-8 in DESIGN.md section 29) ----
+ * The trajectory chains pair poses, so its error grows along a segment (a run of frames with one origin); an OrbLoopFix measures
+ * camera q relative to camera T without passing through that chain.  orb_graph_pairs takes every segment of the last
+ * orb_trajectory_consecutive as a graph of its own: the nodes are the segment's cameras, the chain edges the relative poses of
+ * consecutive cameras as the trajectory holds them (weight 1), the loop edges the entries 0 .. n_pairs - 1 of the last
+ * orb_loop_pairs that qualify (weight loop_weight, measurement r, t of the fix).  The cost of an edge (a -> b, R_z, t_z, w) is
+ * w (rotation_weight |e_R|^2 + |e_t|^2) with e_R the vector part of the skew part of R_b R_a^T R_z^T and e_t = t_b - R_b R_a^T t_a -
+ * t_z; `rounds` Gauss-Newton rounds, each solved by `cg_iterations` conjugate-gradient iterations preconditioned by the 6 x 6
+ * diagonal blocks, move every camera of the segment but its origin; a round that does not lower the cost is undone and ends the
+ * segment.  SE(3) only: the unit of a segment is carried by the edges' translations and is not corrected.  Binary32 arithmetic in
+ * a fixed order, no fused operations: a CPU restatement gives the same bits.  Nothing is fed back into another stage, and no
+ * other stage's results are written. */
+#define ORB_GRAPH_USE_MINIMAL 1u        /* flags: a fix of status ORB_LOCALIZE_MINIMAL qualifies too */
+#define ORB_GRAPH_HELD 0u               /* an origin, a LOST or ORIGIN frame, a frame outside every segment: the trajectory's r, t; other words 0 */
+#define ORB_GRAPH_UNCHANGED 1u          /* the segment has no USED edge: the poses copied bit for bit */
+#define ORB_GRAPH_REFINED 2u            /* every round lowered the segment's cost */
+#define ORB_GRAPH_STALLED 3u            /* a round did not lower the cost: the poses of before that round */
+#define ORB_GRAPH_FAILED 4u             /* a diagonal block could not be inverted: the poses of before that round */
+#define ORB_GRAPH_INVALID 5u            /* a pose entry of a free camera of the segment is not finite: the poses copied bit for bit */
+#define ORB_GRAPH_EDGE_USED 0u          /* the entry is a loop edge of segment `origin` */
+#define ORB_GRAPH_EDGE_STATUS 1u        /* the fix is not OK (nor MINIMAL under ORB_GRAPH_USE_MINIMAL) */
+#define ORB_GRAPH_EDGE_FEW 2u           /* inliers < min_inliers */
+#define ORB_GRAPH_EDGE_RANGE 3u         /* q or T at or above the trajectory call's frames */
+#define ORB_GRAPH_EDGE_SEGMENT 4u       /* q and T are not cameras of one segment */
+#define ORB_GRAPH_EDGE_NONFINITE 5u     /* an entry of the fix's r, t is not finite */
+#define ORB_GRAPH_EDGE_SEGMENT_INVALID 6u /* the segment is ORB_GRAPH_INVALID */
+typedef struct {            /* zero-initialised = the defaults */
+    uint32_t rounds;        /* Gauss-Newton rounds, 1..16 (0: 4) */
+    uint32_t cg_iterations; /* conjugate-gradient iterations of a round, 1..512 (0: the segment's free cameras, at most 512) */
+    uint32_t min_inliers;   /* a fix qualifies with at least this many inliers (0: 12) */
+    float loop_weight;      /* weight of a loop edge against a chain edge's 1 (0: 1.0); finite, >= 0 */
+    float rotation_weight;  /* weight of |e_R|^2 against |e_t|^2 (0: 1.0); finite, >= 0 */
+    uint32_t flags;         /* ORB_GRAPH_USE_MINIMAL or 0 */
+    uint32_t reserved[2];   /* must be 0 (ORB_EINVAL otherwise) */
+} OrbGraphParams;           /* 32 bytes */
+
+typedef struct {
+    float r[9];             /* row-major R, X_g = R X_origin + t: the camera in its segment's frame, as OrbFramePose */
+    float t[3];
+    float cost_before;      /* the segment's cost under the trajectory's poses; the same in each of its frames */
+    float cost_after;       /* ... under the poses written */
+    uint32_t loops;         /* the segment's USED edges */
+    uint32_t status;        /* ORB_GRAPH_HELD .. ORB_GRAPH_INVALID */
+} OrbGraphPose;             /* 64 bytes */
+
+typedef struct {
+    uint32_t verdict;       /* ORB_GRAPH_EDGE_*: the first of PG-4 that applies */
+    float cost_before;      /* the edge's own cost under the trajectory's poses and under the poses written; 0 unless USED */
+    float cost_after;
+    uint32_t origin;        /* the fix's `origin`, as read */
+} OrbGraphEdge;             /* 16 bytes */
+
+/* ORB_EINVAL for a NULL program, rounds > 16, cg_iterations > 512, a weight that is not finite or negative, an unknown flag or a
+ * reserved word that is not 0 (params NULL: the defaults); then ORB_ESTATE unless the last orb_trajectory_consecutive,
+ * orb_match_pairs and orb_loop_pairs are all of the current batch and output set; then ORB_EINVAL for n_pairs outside 1 .. the
+ * entries of the last orb_loop_pairs.  Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not change it),
+ * ordered behind those three stages' last calls and the last call of its own when they ran on another stream; the three wait for
+ * such a call on another stream before they overwrite what it reads.  Result buffers of its own (allocated by the first call:
+ * about 400 bytes per frame of max_batch). */
+int orb_graph_pairs(OrbProgram *p, uint32_t n_pairs, const OrbGraphParams *params, void *stream);
+/* Copy the record of frame `frame` of the last orb_graph_pairs call to the host (synchronises); ORB_ESTATE before any call,
+ * ORB_EINVAL for a frame outside the frames of the trajectory call it read or pose NULL. */
+int orb_graph_read(OrbProgram *p, uint32_t frame, OrbGraphPose *pose);
+/* Copy the verdicts of entries 0 .. n - 1 of the last orb_graph_pairs call (synchronises); ORB_ESTATE before any call, ORB_EINVAL
+ * for n above its n_pairs or dst NULL with n > 0. */
+int orb_graph_edges(OrbProgram *p, OrbGraphEdge *dst, size_t n);
 
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0

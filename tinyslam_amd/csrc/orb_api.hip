@@ -39,6 +39,7 @@
 #include "orb_kernels_place.h"
 #include "orb_kernels_pairs.h"
 #include "orb_kernels_loop.h"
+#include "orb_kernels_graph.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -74,7 +75,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -118,6 +119,10 @@ constexpr StageInfo kStages[ST_COUNT] = {
      1u << ST_MATCH |     // d_matches: the views of a landmark
      1u << ST_TRAJ |      // d_jframe
      1u << ST_LANDMARK},  // d_mland
+    {"graph_pairs", "graph_read",  // the two refinements side by side: an id carries no order
+     1u << ST_TRAJ |      // d_jframe: the nodes and the chain edges
+     1u << ST_PAIRS |     // d_plist: q and T of an entry
+     1u << ST_LOOP},      // loop.fix: the loop edges
     {"place_frames", "place_read",
      1u << ST_TRACK},     // d_tframe: the keyframe column (ORB_PLACE_KEYFRAMES)
     {"match_pairs", "match_pairs_read", 0u},
@@ -164,6 +169,10 @@ static_assert(sizeof(OrbFramePair) == 8 && offsetof(OrbFramePair, target) == 4, 
 static_assert(sizeof(OrbLoopFix) == kLcFixWords * sizeof(uint32_t) && sizeof(OrbLoopParams) == 64 && offsetof(OrbLoopFix, pose_r) == 13 * sizeof(uint32_t) &&
                   offsetof(OrbLoopFix, origin) == 25 * sizeof(uint32_t) && kLcFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) && sizeof(OrbFramePair) == sizeof(uint2),
               "loop layouts");
+static_assert(sizeof(OrbGraphPose) == kPgPoseWords * sizeof(uint32_t) && sizeof(OrbGraphEdge) == kPgEdgeWords * sizeof(uint32_t) && sizeof(OrbGraphParams) == 32 &&
+                  offsetof(OrbGraphPose, status) == 15 * sizeof(uint32_t) && kPgFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) &&
+                  kPgFixWords * sizeof(uint32_t) == sizeof(OrbLoopFix) && offsetof(OrbLoopFix, status) == 30 * sizeof(uint32_t),
+              "graph layouts");
 
 // The last call of a stage
 struct Stage {
@@ -292,6 +301,13 @@ struct OrbProgram {
     // orb_loop_pairs (orb_kernels_loop.h): fix is [P][32] OrbLoopFix, a row is a list entry, cand the candidate of each slot of its query frame
     PnpState loop;
     uint32_t* d_lowner = nullptr;         // [max_batch][max_features] the owner of every keypoint slot
+    // orb_graph_pairs (orb_kernels_graph.h)
+    uint32_t* d_gpose = nullptr;          // [max_batch][16] OrbGraphPose; the poses of before a round during a call
+    uint32_t* d_gedge = nullptr;          // [P][4] OrbGraphEdge
+    uint32_t* d_grow = nullptr;           // [max_batch + 1] CSR row starts: the USED entries at every frame
+    uint32_t* d_gcol = nullptr;           // [2 P] their list indices, ascending within a row
+    float* d_gwork = nullptr;             // [max_batch][kPgNodeWords] the node words of a segment above kPgLdsNodes free nodes
+    uint32_t graph_pairs = 0;             // n_pairs of the last call (its Stage's extent is the frames)
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -542,6 +558,15 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&l.keys, P * kVerifyMaxHyp * sizeof(unsigned long long));
         add(&l.mask, P * cap);
         add(&p->d_lowner, B * cap * sizeof(uint32_t));
+        break;
+    }
+    case ST_GRAPH: {
+        const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
+        add(&p->d_gpose, B * sizeof(OrbGraphPose));
+        add(&p->d_gedge, P * sizeof(OrbGraphEdge));
+        add(&p->d_grow, (B + 1u) * sizeof(uint32_t));
+        add(&p->d_gcol, 2u * P * sizeof(uint32_t));
+        add(&p->d_gwork, B * kPgNodeWords * sizeof(float));
         break;
     }
     }
@@ -2308,6 +2333,74 @@ int orb_loop_pairs(OrbProgram* p, uint32_t n_pairs, const OrbLoopParams* params,
 
 int orb_loop_pairs_read(OrbProgram* p, uint32_t pair, OrbLoopFix* fix, uint8_t* inliers, size_t n) {
     return p ? read_stage(p, ST_LOOP, pair, fix, p->loop.fix, sizeof(OrbLoopFix), inliers, p->loop.mask, 1, n) : ORB_EINVAL;
+}
+
+int orb_debug_loop_buffer(OrbProgram* p, void** fixes) {
+    if (!p) return ORB_EINVAL;
+    if (!p->stage[ST_LOOP].extent) return fail(p, ORB_ESTATE, "debug_loop_buffer before orb_loop_pairs");
+    if (fixes) *fixes = p->loop.fix;
+    return ORB_OK;
+}
+
+int orb_graph_pairs(OrbProgram* p, uint32_t n_pairs, const OrbGraphParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbGraphParams g{};
+    if (params) g = *params;
+    if (g.reserved[0] | g.reserved[1]) return fail(p, ORB_EINVAL, "graph_pairs: reserved words must be 0");
+    if (g.rounds > 16u || g.cg_iterations > kPgMaxCg || (g.flags & ~ORB_GRAPH_USE_MINIMAL))
+        return fail(p, ORB_EINVAL, "graph_pairs: rounds 0..16, cg_iterations 0..%u, flags ORB_GRAPH_USE_MINIMAL or 0", kPgMaxCg);
+    if (!(std::isfinite(g.loop_weight) && g.loop_weight >= 0.0f) || !(std::isfinite(g.rotation_weight) && g.rotation_weight >= 0.0f))
+        return fail(p, ORB_EINVAL, "graph_pairs: loop_weight and rotation_weight must be finite and >= 0");
+    if (int rc = stages_fresh(p, ST_GRAPH, kStages[ST_GRAPH].reads)) return rc;
+    const Stage* const st = p->stage;
+    if (n_pairs < 1u || n_pairs > st[ST_LOOP].extent) return fail(p, ORB_EINVAL, "graph_pairs: need 1..%u pairs (the last orb_loop_pairs' entries)", st[ST_LOOP].extent);
+    const bool first = !p->d_gpose;
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_GRAPH, stream, kStages[ST_GRAPH].reads, &s)) return rc;
+    if (first)  // k_pg_solve keeps a segment in all of a CU's LDS but the reductions' partials
+        HIP_TRY(p, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pg_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPgLdsBytes));
+    PgArgs a{};
+    a.frames = p->d_jframe;
+    a.list = (const uint2*)p->d_plist;
+    a.fixes = p->loop.fix;
+    a.n_frames = st[ST_TRAJ].extent;  // PG-1: F
+    a.n_pairs = n_pairs;
+    a.min_inliers = g.min_inliers ? g.min_inliers : 12u;
+    a.use_minimal = g.flags & ORB_GRAPH_USE_MINIMAL;
+    a.rounds = g.rounds ? g.rounds : 4u;
+    a.cg_iterations = g.cg_iterations;
+    a.loop_weight = g.loop_weight == 0.0f ? 1.0f : g.loop_weight;
+    a.rotation_weight = g.rotation_weight == 0.0f ? 1.0f : g.rotation_weight;
+    a.edges = p->d_gedge;
+    a.row = p->d_grow;
+    a.col = p->d_gcol;
+    a.out = p->d_gpose;
+    a.work = p->d_gwork;
+    const uint32_t F = a.n_frames;
+    hipLaunchKernelGGL(k_pg_edges, dim3((n_pairs + kPgThreads - 1u) / kPgThreads), dim3(kPgThreads), 0, s, a);
+    hipLaunchKernelGGL(k_pg_index, dim3(1), dim3(kPgThreads), 0, s, a);
+    hipLaunchKernelGGL(k_pg_write, dim3((F + kPgThreads - 1u) / kPgThreads), dim3(kPgThreads), 0, s, a);
+    hipLaunchKernelGGL(k_pg_solve, dim3(F), dim3(kPgThreads), kPgLdsBytes, s, a);
+    if (int rc = stage_end(p, ST_GRAPH, s, F)) return rc;  // p->last_stream stays, as after a guided call
+    p->graph_pairs = n_pairs;
+    return ORB_OK;
+}
+
+int orb_graph_read(OrbProgram* p, uint32_t frame, OrbGraphPose* pose) {
+    if (!p) return ORB_EINVAL;
+    if (p->stage[ST_GRAPH].extent && !pose) return fail(p, ORB_EINVAL, "graph_read: pose is NULL");
+    return read_stage(p, ST_GRAPH, frame, pose, p->d_gpose, sizeof(OrbGraphPose), nullptr, nullptr, 0, 0);
+}
+
+int orb_graph_edges(OrbProgram* p, OrbGraphEdge* dst, size_t n) {
+    if (!p) return ORB_EINVAL;
+    const Stage& last = p->stage[ST_GRAPH];
+    if (!last.extent) return fail(p, ORB_ESTATE, "graph_edges before graph_pairs");
+    if (n > p->graph_pairs || (!dst && n)) return fail(p, ORB_EINVAL, "graph_edges: %zu entries of %u, or the destination is NULL", n, p->graph_pairs);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    if (n) HIP_TRY(p, hipMemcpy(dst, p->d_gedge, n * sizeof(OrbGraphEdge), hipMemcpyDeviceToHost));
+    return ORB_OK;
 }
 
 int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {

@@ -107,6 +107,15 @@ LOOP_FIX_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("step", "<f4
                            ("origin", "<u4"), ("query_origin", "<u4"), ("candidates", "<u4"), ("inliers", "<u4"), ("hypothesis", "<u4"),
                            ("status", "<u4"), ("reserved", "<u4", (1,))])
 ORB_LOOP_NO_ORIGIN = 0xFFFFFFFF
+# pose-graph correction from the loop fixes (orb_graph_pairs): OrbGraphPose (64 B) and its status, OrbGraphEdge
+# (16 B) and its verdict, the flag of OrbGraphParams
+GRAPH_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("cost_before", "<f4"), ("cost_after", "<f4"), ("loops", "<u4"),
+                             ("status", "<u4")])
+GRAPH_EDGE_DTYPE = np.dtype([("verdict", "<u4"), ("cost_before", "<f4"), ("cost_after", "<f4"), ("origin", "<u4")])
+ORB_GRAPH_HELD, ORB_GRAPH_UNCHANGED, ORB_GRAPH_REFINED, ORB_GRAPH_STALLED, ORB_GRAPH_FAILED, ORB_GRAPH_INVALID = 0, 1, 2, 3, 4, 5
+(ORB_GRAPH_EDGE_USED, ORB_GRAPH_EDGE_STATUS, ORB_GRAPH_EDGE_FEW, ORB_GRAPH_EDGE_RANGE, ORB_GRAPH_EDGE_SEGMENT, ORB_GRAPH_EDGE_NONFINITE,
+ ORB_GRAPH_EDGE_SEGMENT_INVALID) = 0, 1, 2, 3, 4, 5, 6
+ORB_GRAPH_USE_MINIMAL = 1
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -135,7 +144,8 @@ EXPORTS = [
     "orb_adjust_consecutive", "orb_adjust_read",
     "orb_place_frames", "orb_place_read", "orb_place_signature",
     "orb_match_pairs", "orb_match_pairs_read", "orb_verify_pairs", "orb_verify_pairs_read",
-    "orb_loop_pairs", "orb_loop_pairs_read",
+    "orb_loop_pairs", "orb_loop_pairs_read", "orb_debug_loop_buffer",
+    "orb_graph_pairs", "orb_graph_read", "orb_graph_edges",
 ]
 
 
@@ -243,6 +253,16 @@ class _LoopParams(ctypes.Structure):
 
 
 OrbLoopParams = _LoopParams
+
+
+class _GraphParams(ctypes.Structure):
+    """OrbGraphParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("rounds", ctypes.c_uint32), ("cg_iterations", ctypes.c_uint32), ("min_inliers", ctypes.c_uint32),
+                ("loop_weight", ctypes.c_float), ("rotation_weight", ctypes.c_float), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+OrbGraphParams = _GraphParams
 
 
 class _PlaceParams(ctypes.Structure):
@@ -364,6 +384,10 @@ def load_library(path=None):
     L.orb_verify_pairs_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_loop_pairs.argtypes = [vp, u32, ctypes.POINTER(_LoopParams), vp]
     L.orb_loop_pairs_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_debug_loop_buffer.argtypes = [vp, ctypes.POINTER(vp)]
+    L.orb_graph_pairs.argtypes = [vp, u32, ctypes.POINTER(_GraphParams), vp]
+    L.orb_graph_read.argtypes = [vp, u32, vp]
+    L.orb_graph_edges.argtypes = [vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -994,6 +1018,36 @@ class OrbProgram:
         mask = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=np.uint8)
         self._check(self._lib.orb_loop_pairs_read(self._handle(), pair, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
         return rec, mask
+
+    def debug_loop_buffer(self):
+        """For tests: the device address of the fix records [ORB_PAIRS_PER_FRAME * max_batch] LOOP_FIX_DTYPE that loop_pairs writes
+        and loop_pairs_read and graph_pairs read.  The caller orders its own writes."""
+        a = ctypes.c_void_p()
+        self._check(self._lib.orb_debug_loop_buffer(self._handle(), ctypes.byref(a)))
+        return a.value
+
+    def graph_pairs(self, n_pairs, rounds=0, cg_iterations=0, min_inliers=0, loop_weight=0.0, rotation_weight=0.0, flags=0, stream=None,
+                    reserved=(0, 0)):
+        """Pose-graph correction of every segment of the last trajectory_consecutive from entries 0 .. n_pairs - 1 of the last
+        loop_pairs (not in the reference): the segment's cameras are the nodes, the relative
+        poses of consecutive cameras the chain edges, the qualifying fixes the loop edges; `rounds` Gauss-Newton rounds, each
+        solved by `cg_iterations` preconditioned conjugate-gradient iterations, move every camera but the segment's origin.  Zero
+        parameters are the defaults.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        prm = _GraphParams(rounds, cg_iterations, min_inliers, float(np.float32(loop_weight)), float(np.float32(rotation_weight)), flags,
+                           (ctypes.c_uint32 * 2)(*reserved))
+        self._check(self._lib.orb_graph_pairs(self._handle(), n_pairs, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def graph_read(self, frame):
+        """The record of GRAPH_POSE_DTYPE of frame `frame` of the last graph_pairs -- synchronises."""
+        rec = np.zeros((), dtype=GRAPH_POSE_DTYPE)
+        self._check(self._lib.orb_graph_read(self._handle(), frame, _ptr(rec)))
+        return rec
+
+    def graph_edges(self, n):
+        """GRAPH_EDGE_DTYPE verdicts of entries 0 .. n - 1 of the last graph_pairs -- synchronises."""
+        out = np.zeros(n, dtype=GRAPH_EDGE_DTYPE)
+        self._check(self._lib.orb_graph_edges(self._handle(), _ptr(out) if n else None, n))
+        return out
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
