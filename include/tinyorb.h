@@ -1107,6 +1107,90 @@ int orb_graph_read(OrbProgram *p, uint32_t frame, OrbGraphPose *pose);
  * for n above its n_pairs or dst NULL with n > 0. */
 int orb_graph_edges(OrbProgram *p, OrbGraphEdge *dst, size_t n);
 
+/* ---- trajectory segments joined through loop fixes (NOT in the reference; definition SJ-1..SJ-7 in DESIGN.md section 30) ----
+ * A LOST frame or a RESTART starts a new segment of the trajectory with its own frame and unit, and orb_graph_pairs refuses a fix
+ * whose query and target lie in different segments.  Such a fix gives the whole similarity between the two: camera q in segment
+ * `origin`'s frame and unit (pose_r, pose_t) and, from the trajectory, in segment `query_origin`'s; an inlier keypoint of q that a
+ * landmark of each segment owns has a depth in each unit, and the lower median of the ratios is the scale (TJ-3, TJ-4 on this
+ * call's parameters).  Every segment takes, among its entries that hold, the one with the most consistent ratios (then the lowest
+ * index) as its link to an EARLIER origin; the links form a forest and are chained, and every frame is written in the frame and
+ * unit of its segment's root.  Binary32 arithmetic in a fixed order, no fused operations: a CPU restatement gives the same bits.
+ * Nothing is fed back into another stage, and no other stage's results are written. */
+#define ORB_JOIN_USE_MINIMAL 1u         /* flags: a fix of status ORB_LOCALIZE_MINIMAL qualifies too */
+#define ORB_JOIN_COPIED 0u              /* the frame's segment is a root: r, t, scale of the trajectory bit for bit, gain 1 */
+#define ORB_JOIN_MOVED 1u               /* the frame in its root's frame and unit */
+#define ORB_JOIN_SEGMENT_NONE 0u        /* the frame is no segment's origin */
+#define ORB_JOIN_SEGMENT_ROOT 1u        /* an origin without a chosen link */
+#define ORB_JOIN_SEGMENT_LINKED 2u      /* an origin joined to an earlier one */
+#define ORB_JOIN_LINK_HOLDS 0u          /* the entry gives a similarity between its two segments */
+#define ORB_JOIN_LINK_STATUS 1u         /* the fix is not OK (nor MINIMAL under ORB_JOIN_USE_MINIMAL) */
+#define ORB_JOIN_LINK_FEW 2u            /* inliers < min_inliers */
+#define ORB_JOIN_LINK_RANGE 3u          /* q or T outside the trajectory's frames, q outside the landmarks', or q without an origin */
+#define ORB_JOIN_LINK_SAME 4u           /* q and T lie in one segment: orb_graph_pairs' business */
+#define ORB_JOIN_LINK_FORWARD 5u        /* origin > query_origin: a link hangs the later origin under the earlier one */
+#define ORB_JOIN_LINK_NONFINITE 6u      /* an entry of pose_r, pose_t, of camera q's record or of the similarity is not finite */
+#define ORB_JOIN_LINK_RATIO_FEW 7u      /* fewer than min_shared ratios */
+#define ORB_JOIN_LINK_RATIO_SPREAD 8u   /* fewer than consistent_permille of them within scale_tolerance of their median */
+typedef struct {            /* zero-initialised = the defaults */
+    uint32_t min_inliers;   /* a fix qualifies with at least this many inliers (0: 12) */
+    uint32_t min_shared;    /* ratios an entry needs (0: 8) */
+    float scale_tolerance;  /* a ratio is consistent within this share of the median (0: 0.1); finite, >= 0 */
+    uint32_t consistent_permille; /* consistent ratios an entry needs, per thousand (0: 500; <= 1000) */
+    uint32_t flags;         /* ORB_JOIN_USE_MINIMAL or 0 */
+    uint32_t reserved[3];   /* must be 0 (ORB_EINVAL otherwise) */
+} OrbJoinParams;            /* 32 bytes */
+
+typedef struct {
+    float r[9];             /* row-major R, X_f = R X_root + t: the camera in its root's frame and unit */
+    float t[3];
+    float scale;            /* gain * the trajectory's scale */
+    float gain;             /* units of the root per unit of the frame's segment; 1 when COPIED */
+    uint32_t root;          /* the origin whose frame this is */
+    uint32_t status;        /* ORB_JOIN_COPIED, ORB_JOIN_MOVED */
+} OrbJoinPose;              /* 64 bytes */
+
+typedef struct {
+    float r[9];             /* sigma X_b = R X_root + t: the root's coordinates in this origin's frame (the identity for a root) */
+    float t[3];
+    float sigma;            /* units of the root per unit of this segment */
+    uint32_t root;
+    uint32_t link;          /* the list index of the chosen entry, 0xffffffff: none */
+    uint32_t status;        /* ORB_JOIN_SEGMENT_* */
+} OrbJoinSegment;           /* 64 bytes */
+
+typedef struct {
+    uint32_t verdict;       /* ORB_JOIN_LINK_*: the first of SJ-3 that applies */
+    uint32_t origin;        /* the fix's words, as read */
+    uint32_t query_origin;
+    uint32_t shared;        /* the entry's ratios; 0 unless HOLDS, RATIO_FEW or RATIO_SPREAD */
+    uint32_t consistent;    /* ... those within scale_tolerance of gamma */
+    float gamma;            /* their lower median: units of `origin` per unit of `query_origin` */
+    uint32_t chosen;        /* 1: this entry is its segment's link */
+    uint32_t reserved;
+} OrbJoinLink;              /* 32 bytes */
+
+/* ORB_EINVAL for a NULL program, a scale_tolerance that is not finite or negative, consistent_permille > 1000, an unknown flag or
+ * a reserved word that is not 0 (params NULL: the defaults); then ORB_ESTATE unless the last orb_match_consecutive,
+ * orb_trajectory_consecutive, orb_landmarks_consecutive, orb_match_pairs and orb_loop_pairs are all of the current batch and output
+ * set; then ORB_EINVAL for n_pairs outside 1 .. the entries of the last orb_loop_pairs, or when the landmarks call's frames *
+ * max_features reaches 2^32 - 1.  Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not change it),
+ * ordered behind those five stages' last calls and the last call of its own when they ran on another stream; the five wait for
+ * such a call on another stream before they overwrite what it reads.  Result buffers of its own (allocated by the first call:
+ * about 4 + 4 ORB_PAIRS_PER_FRAME bytes per keypoint slot of max_batch). */
+int orb_join_pairs(OrbProgram *p, uint32_t n_pairs, const OrbJoinParams *params, void *stream);
+/* Copy the record of frame `frame` of the last orb_join_pairs call to the host (synchronises); ORB_ESTATE before any call,
+ * ORB_EINVAL for a frame outside the frames of the trajectory call it read or pose NULL. */
+int orb_join_read(OrbProgram *p, uint32_t frame, OrbJoinPose *pose);
+/* Copy the segment records of frame slots 0 .. n - 1 of the last orb_join_pairs call (synchronises); ORB_ESTATE before any call,
+ * ORB_EINVAL for n above its frames or dst NULL with n > 0. */
+int orb_join_segments(OrbProgram *p, OrbJoinSegment *dst, size_t n);
+/* Copy the link records of entries 0 .. n - 1 of the last orb_join_pairs call (synchronises); ORB_ESTATE before any call, ORB_EINVAL
+ * for n above its n_pairs or dst NULL with n > 0. */
+int orb_join_links(OrbProgram *p, OrbJoinLink *dst, size_t n);
+/* For tests: the device address of the inlier bytes [ORB_PAIRS_PER_FRAME * max_batch][max_features] that orb_loop_pairs writes and
+ * orb_loop_pairs_read and orb_join_pairs read.  The caller orders its own writes.  ORB_ESTATE until a loop call has run. */
+int orb_debug_loop_mask_buffer(OrbProgram *p, void **mask);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

@@ -40,6 +40,7 @@
 #include "orb_kernels_pairs.h"
 #include "orb_kernels_loop.h"
 #include "orb_kernels_graph.h"
+#include "orb_kernels_join.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -75,7 +76,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_JOIN, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -123,6 +124,12 @@ constexpr StageInfo kStages[ST_COUNT] = {
      1u << ST_TRAJ |      // d_jframe: the nodes and the chain edges
      1u << ST_PAIRS |     // d_plist: q and T of an entry
      1u << ST_LOOP},      // loop.fix: the loop edges
+    {"join_pairs", "join_read",
+     1u << ST_MATCH |     // d_matches: the owners' walk
+     1u << ST_TRAJ |      // d_jframe: the segments and camera q in its own
+     1u << ST_LANDMARK |  // d_mland: the two landmarks of a ratio
+     1u << ST_PAIRS |     // d_plist, d_prows: q, T and the matched keypoint
+     1u << ST_LOOP},      // loop.fix, loop.mask: camera q in the target's segment, the inliers
     {"place_frames", "place_read",
      1u << ST_TRACK},     // d_tframe: the keyframe column (ORB_PLACE_KEYFRAMES)
     {"match_pairs", "match_pairs_read", 0u},
@@ -173,6 +180,12 @@ static_assert(sizeof(OrbGraphPose) == kPgPoseWords * sizeof(uint32_t) && sizeof(
                   offsetof(OrbGraphPose, status) == 15 * sizeof(uint32_t) && kPgFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) &&
                   kPgFixWords * sizeof(uint32_t) == sizeof(OrbLoopFix) && offsetof(OrbLoopFix, status) == 30 * sizeof(uint32_t),
               "graph layouts");
+static_assert(sizeof(OrbJoinPose) == kSjPoseWords * sizeof(uint32_t) && sizeof(OrbJoinSegment) == kSjSegWords * sizeof(uint32_t) &&
+                  sizeof(OrbJoinLink) == kSjLinkWords * sizeof(uint32_t) && sizeof(OrbJoinParams) == 32 && offsetof(OrbJoinPose, root) == 14 * sizeof(uint32_t) &&
+                  offsetof(OrbJoinSegment, sigma) == 12 * sizeof(uint32_t) && offsetof(OrbJoinLink, gamma) == 5 * sizeof(uint32_t) &&
+                  kSjFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) && kSjFixWords * sizeof(uint32_t) == sizeof(OrbLoopFix) &&
+                  offsetof(OrbLoopFix, inliers) == 28 * sizeof(uint32_t) && offsetof(OrbLoopFix, pose_t) == 22 * sizeof(uint32_t),
+              "join layouts");
 
 // The last call of a stage
 struct Stage {
@@ -308,6 +321,14 @@ struct OrbProgram {
     uint32_t* d_gcol = nullptr;           // [2 P] their list indices, ascending within a row
     float* d_gwork = nullptr;             // [max_batch][kPgNodeWords] the node words of a segment above kPgLdsNodes free nodes
     uint32_t graph_pairs = 0;             // n_pairs of the last call (its Stage's extent is the frames)
+    // orb_join_pairs (orb_kernels_join.h)
+    uint32_t* d_sowner = nullptr;         // [max_batch][max_features] the owner of every keypoint slot, of this call's landmarks
+    uint32_t* d_sratio = nullptr;         // [P][max_features] the bits of an entry's ratios
+    uint32_t* d_slink = nullptr;          // [P][8] OrbJoinLink
+    unsigned long long* d_skey = nullptr; // [max_batch] the best entry of every segment
+    uint32_t* d_sseg = nullptr;           // [max_batch][16] OrbJoinSegment
+    uint32_t* d_spose = nullptr;          // [max_batch][16] OrbJoinPose
+    uint32_t join_pairs = 0;              // n_pairs of the last call (its Stage's extent is the frames)
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -567,6 +588,16 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&p->d_grow, (B + 1u) * sizeof(uint32_t));
         add(&p->d_gcol, 2u * P * sizeof(uint32_t));
         add(&p->d_gwork, B * kPgNodeWords * sizeof(float));
+        break;
+    }
+    case ST_JOIN: {
+        const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
+        add(&p->d_sowner, B * cap * sizeof(uint32_t));
+        add(&p->d_sratio, P * cap * sizeof(uint32_t));
+        add(&p->d_slink, P * sizeof(OrbJoinLink));
+        add(&p->d_skey, B * sizeof(unsigned long long));
+        add(&p->d_sseg, B * sizeof(OrbJoinSegment));
+        add(&p->d_spose, B * sizeof(OrbJoinPose));
         break;
     }
     }
@@ -2401,6 +2432,103 @@ int orb_graph_edges(OrbProgram* p, OrbGraphEdge* dst, size_t n) {
     HIP_TRY(p, hipEventSynchronize(last.done));
     if (n) HIP_TRY(p, hipMemcpy(dst, p->d_gedge, n * sizeof(OrbGraphEdge), hipMemcpyDeviceToHost));
     return ORB_OK;
+}
+
+int orb_debug_loop_mask_buffer(OrbProgram* p, void** mask) {
+    if (!p) return ORB_EINVAL;
+    if (!p->stage[ST_LOOP].extent) return fail(p, ORB_ESTATE, "debug_loop_mask_buffer before orb_loop_pairs");
+    if (mask) *mask = p->loop.mask;
+    return ORB_OK;
+}
+
+int orb_join_pairs(OrbProgram* p, uint32_t n_pairs, const OrbJoinParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbJoinParams g{};
+    if (params) g = *params;
+    if (g.reserved[0] | g.reserved[1] | g.reserved[2]) return fail(p, ORB_EINVAL, "join_pairs: reserved words must be 0");
+    if (g.consistent_permille > 1000u || (g.flags & ~ORB_JOIN_USE_MINIMAL))
+        return fail(p, ORB_EINVAL, "join_pairs: consistent_permille 0..1000, flags ORB_JOIN_USE_MINIMAL or 0");
+    if (!(std::isfinite(g.scale_tolerance) && g.scale_tolerance >= 0.0f)) return fail(p, ORB_EINVAL, "join_pairs: scale_tolerance must be finite and >= 0");
+    if (int rc = stages_fresh(p, ST_JOIN, kStages[ST_JOIN].reads)) return rc;
+    const Stage* const st = p->stage;
+    if (n_pairs < 1u || n_pairs > st[ST_LOOP].extent) return fail(p, ORB_EINVAL, "join_pairs: need 1..%u pairs (the last orb_loop_pairs' entries)", st[ST_LOOP].extent);
+    // SJ-1: L is LC-1's, the frames of the last landmarks call (a later matcher or trajectory call of fewer frames lowers it)
+    const uint32_t F = st[ST_TRAJ].extent;
+    const uint32_t L = std::min(st[ST_LANDMARK].extent + 1u, std::min(st[ST_MATCH].extent, F));
+    const size_t cap = p->cfg.max_features;
+    if ((unsigned long long)L * cap >= 0xffffffffull)  // LC-2: a key p * cap + i below the "no owner" word
+        return fail(p, ORB_EINVAL, "join_pairs: the landmarks call's frames * max_features must be below 2^32 - 1");
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_JOIN, stream, kStages[ST_JOIN].reads, &s)) return rc;
+    LcArgs o{};  // SJ-2: k_lc_index reads the capacity, the counters, the consecutive records, the frames, the landmarks, L and the owners
+    o.loc.cap = (uint32_t)cap;
+    o.loc.counts = p->d_counts;
+    o.loc.matches = p->d_matches;
+    o.frames = p->d_jframe;
+    o.lms = p->d_mland;
+    o.n_frames = L;
+    o.traj_frames = F;
+    o.owner = p->d_sowner;
+    SjArgs a{};
+    a.counts = p->d_counts;
+    a.cap = (uint32_t)cap;
+    a.list = (const uint2*)p->d_plist;
+    a.rows = p->d_prows;
+    a.frames = p->d_jframe;
+    a.lms = p->d_mland;
+    a.fixes = p->loop.fix;
+    a.mask = p->loop.mask;
+    a.owner = p->d_sowner;
+    a.n_frames = F;
+    a.map_frames = L;
+    a.n_pairs = n_pairs;
+    a.min_inliers = g.min_inliers ? g.min_inliers : 12u;
+    a.use_minimal = g.flags & ORB_JOIN_USE_MINIMAL;
+    a.min_shared = g.min_shared ? g.min_shared : 8u;
+    a.tol = g.scale_tolerance == 0.0f ? 0.1f : g.scale_tolerance;
+    a.permille = g.consistent_permille ? g.consistent_permille : 500u;
+    a.ratios = p->d_sratio;
+    a.links = p->d_slink;
+    a.keys = p->d_skey;
+    a.segs = p->d_sseg;
+    a.out = p->d_spose;
+    // the owners of all F frames: rows L .. F - 1 have none
+    HIP_TRY(p, hipMemsetAsync(p->d_sowner, 0xff, (size_t)F * cap * sizeof(uint32_t), s));
+    HIP_TRY(p, hipMemsetAsync(p->d_skey, 0, (size_t)F * sizeof(unsigned long long), s));
+    HIP_TRY(p, hipMemsetAsync(p->d_sseg, 0, (size_t)F * sizeof(OrbJoinSegment), s));
+    if (L > 1u) hipLaunchKernelGGL(k_lc_index, dim3(L - 1u, (unsigned)((cap + kLcThreads - 1u) / kLcThreads)), dim3(kLcThreads), 0, s, o);
+    hipLaunchKernelGGL(k_sj_ratio, dim3(n_pairs), dim3(kSjThreads), 0, s, a);
+    hipLaunchKernelGGL(k_sj_chain, dim3(1), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_sj_write, dim3((F + kSjThreads - 1u) / kSjThreads), dim3(kSjThreads), 0, s, a);
+    if (int rc = stage_end(p, ST_JOIN, s, F)) return rc;  // p->last_stream stays, as after a guided call
+    p->join_pairs = n_pairs;
+    return ORB_OK;
+}
+
+int orb_join_read(OrbProgram* p, uint32_t frame, OrbJoinPose* pose) {
+    if (!p) return ORB_EINVAL;
+    if (p->stage[ST_JOIN].extent && !pose) return fail(p, ORB_EINVAL, "join_read: pose is NULL");
+    return read_stage(p, ST_JOIN, frame, pose, p->d_spose, sizeof(OrbJoinPose), nullptr, nullptr, 0, 0);
+}
+
+// The first n records of one of the stage's tables, behind its last call
+static int join_copy(OrbProgram* p, const char* who, void* dst, const void* src, size_t n, size_t have, size_t bytes) {
+    if (!p) return ORB_EINVAL;
+    const Stage& last = p->stage[ST_JOIN];
+    if (!last.extent) return fail(p, ORB_ESTATE, "%s before join_pairs", who);
+    if (n > have || (!dst && n)) return fail(p, ORB_EINVAL, "%s: %zu records of %zu, or the destination is NULL", who, n, have);
+    HIP_TRY(p, hipSetDevice(p->device));
+    HIP_TRY(p, hipEventSynchronize(last.done));
+    if (n) HIP_TRY(p, hipMemcpy(dst, src, n * bytes, hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_join_segments(OrbProgram* p, OrbJoinSegment* dst, size_t n) {
+    return p ? join_copy(p, "join_segments", dst, p->d_sseg, n, p->stage[ST_JOIN].extent, sizeof(OrbJoinSegment)) : ORB_EINVAL;
+}
+
+int orb_join_links(OrbProgram* p, OrbJoinLink* dst, size_t n) {
+    return p ? join_copy(p, "join_links", dst, p->d_slink, n, p->join_pairs, sizeof(OrbJoinLink)) : ORB_EINVAL;
 }
 
 int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {

@@ -116,6 +116,18 @@ ORB_GRAPH_HELD, ORB_GRAPH_UNCHANGED, ORB_GRAPH_REFINED, ORB_GRAPH_STALLED, ORB_G
 (ORB_GRAPH_EDGE_USED, ORB_GRAPH_EDGE_STATUS, ORB_GRAPH_EDGE_FEW, ORB_GRAPH_EDGE_RANGE, ORB_GRAPH_EDGE_SEGMENT, ORB_GRAPH_EDGE_NONFINITE,
  ORB_GRAPH_EDGE_SEGMENT_INVALID) = 0, 1, 2, 3, 4, 5, 6
 ORB_GRAPH_USE_MINIMAL = 1
+# trajectory segments joined through loop fixes (orb_join_pairs): OrbJoinPose (64 B) and its status,
+# OrbJoinSegment (64 B) and its status, OrbJoinLink (32 B) and its verdict, the flag of OrbJoinParams
+JOIN_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4"), ("gain", "<f4"), ("root", "<u4"), ("status", "<u4")])
+JOIN_SEGMENT_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("sigma", "<f4"), ("root", "<u4"), ("link", "<u4"), ("status", "<u4")])
+JOIN_LINK_DTYPE = np.dtype([("verdict", "<u4"), ("origin", "<u4"), ("query_origin", "<u4"), ("shared", "<u4"), ("consistent", "<u4"),
+                            ("gamma", "<f4"), ("chosen", "<u4"), ("reserved", "<u4")])
+ORB_JOIN_COPIED, ORB_JOIN_MOVED = 0, 1
+ORB_JOIN_SEGMENT_NONE, ORB_JOIN_SEGMENT_ROOT, ORB_JOIN_SEGMENT_LINKED = 0, 1, 2
+(ORB_JOIN_LINK_HOLDS, ORB_JOIN_LINK_STATUS, ORB_JOIN_LINK_FEW, ORB_JOIN_LINK_RANGE, ORB_JOIN_LINK_SAME, ORB_JOIN_LINK_FORWARD,
+ ORB_JOIN_LINK_NONFINITE, ORB_JOIN_LINK_RATIO_FEW, ORB_JOIN_LINK_RATIO_SPREAD) = 0, 1, 2, 3, 4, 5, 6, 7, 8
+ORB_JOIN_USE_MINIMAL = 1
+ORB_JOIN_NO_LINK = 0xFFFFFFFF
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -146,6 +158,7 @@ EXPORTS = [
     "orb_match_pairs", "orb_match_pairs_read", "orb_verify_pairs", "orb_verify_pairs_read",
     "orb_loop_pairs", "orb_loop_pairs_read", "orb_debug_loop_buffer",
     "orb_graph_pairs", "orb_graph_read", "orb_graph_edges",
+    "orb_join_pairs", "orb_join_read", "orb_join_segments", "orb_join_links", "orb_debug_loop_mask_buffer",
 ]
 
 
@@ -263,6 +276,15 @@ class _GraphParams(ctypes.Structure):
 
 
 OrbGraphParams = _GraphParams
+
+
+class _JoinParams(ctypes.Structure):
+    """OrbJoinParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("min_inliers", ctypes.c_uint32), ("min_shared", ctypes.c_uint32), ("scale_tolerance", ctypes.c_float),
+                ("consistent_permille", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+OrbJoinParams = _JoinParams
 
 
 class _PlaceParams(ctypes.Structure):
@@ -388,6 +410,11 @@ def load_library(path=None):
     L.orb_graph_pairs.argtypes = [vp, u32, ctypes.POINTER(_GraphParams), vp]
     L.orb_graph_read.argtypes = [vp, u32, vp]
     L.orb_graph_edges.argtypes = [vp, vp, sz]
+    L.orb_join_pairs.argtypes = [vp, u32, ctypes.POINTER(_JoinParams), vp]
+    L.orb_join_read.argtypes = [vp, u32, vp]
+    L.orb_join_segments.argtypes = [vp, vp, sz]
+    L.orb_join_links.argtypes = [vp, vp, sz]
+    L.orb_debug_loop_mask_buffer.argtypes = [vp, ctypes.POINTER(vp)]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -1047,6 +1074,43 @@ class OrbProgram:
         """GRAPH_EDGE_DTYPE verdicts of entries 0 .. n - 1 of the last graph_pairs -- synchronises."""
         out = np.zeros(n, dtype=GRAPH_EDGE_DTYPE)
         self._check(self._lib.orb_graph_edges(self._handle(), _ptr(out) if n else None, n))
+        return out
+
+    def debug_loop_mask_buffer(self):
+        """For tests: the device address of the inlier bytes [ORB_PAIRS_PER_FRAME * max_batch][max_features] that loop_pairs writes
+        and loop_pairs_read and join_pairs read.  The caller orders its own writes."""
+        a = ctypes.c_void_p()
+        self._check(self._lib.orb_debug_loop_mask_buffer(self._handle(), ctypes.byref(a)))
+        return a.value
+
+    def join_pairs(self, n_pairs, min_inliers=0, min_shared=0, scale_tolerance=0.0, consistent_permille=0, flags=0, stream=None,
+                   reserved=(0, 0, 0)):
+        """Joins the segments of the last trajectory_consecutive through entries 0 .. n_pairs - 1 of the last loop_pairs (not in the
+        reference): an entry whose query and target lie in different segments gives the
+        similarity between them, its scale the lower median of the depth ratios of the inlier keypoints that a landmark of each
+        segment owns; every segment takes its most consistent entry as its link to an earlier origin, the links are chained and
+        every frame is written in its root's frame and unit.  Zero parameters are the defaults.  Asynchronous on `stream` (None:
+        as match_guided chooses)."""
+        prm = _JoinParams(min_inliers, min_shared, float(np.float32(scale_tolerance)), consistent_permille, flags,
+                          (ctypes.c_uint32 * 3)(*reserved))
+        self._check(self._lib.orb_join_pairs(self._handle(), n_pairs, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def join_read(self, frame):
+        """The record of JOIN_POSE_DTYPE of frame `frame` of the last join_pairs -- synchronises."""
+        rec = np.zeros((), dtype=JOIN_POSE_DTYPE)
+        self._check(self._lib.orb_join_read(self._handle(), frame, _ptr(rec)))
+        return rec
+
+    def join_segments(self, n):
+        """JOIN_SEGMENT_DTYPE records of frame slots 0 .. n - 1 of the last join_pairs -- synchronises."""
+        out = np.zeros(n, dtype=JOIN_SEGMENT_DTYPE)
+        self._check(self._lib.orb_join_segments(self._handle(), _ptr(out) if n else None, n))
+        return out
+
+    def join_links(self, n):
+        """JOIN_LINK_DTYPE records of entries 0 .. n - 1 of the last join_pairs -- synchronises."""
+        out = np.zeros(n, dtype=JOIN_LINK_DTYPE)
+        self._check(self._lib.orb_join_links(self._handle(), _ptr(out) if n else None, n))
         return out
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
