@@ -97,9 +97,11 @@ def test_constants_defaults_and_the_order_of_the_checks():
     assert [orb.FRAME_POSE_DTYPE.fields[k][1] // 4 for k in ("r", "t", "scale", "origin")] == [0, 9, 12, 14]
     assert [orb.JOIN_SEGMENT_DTYPE.fields[k][1] // 4 for k in ("sigma", "root", "link", "status")] == [12, 13, 14, 15]
     assert [orb.JOIN_LINK_DTYPE.fields[k][1] // 4 for k in ("gamma", "chosen")] == [5, 6]
-    # the owners' kernel and the polar step are section 28's and section 20's: included, not restated; no fused operation
+    # the owners' kernel, the polar step and the compose are section 28's and section 20's: included, not restated (the step once, in
+    # SJ-4; the compose in SJ-6 and in the frames' records); no fused operation
     code = re.sub(r"//[^\n]*", "", kern)
-    assert '#include "orb_kernels_loop.h"' in kern and "k_lc_index" not in code and code.count("traj_polar_step(") == 2
+    assert '#include "orb_kernels_loop.h"' in kern and "k_lc_index" not in code
+    assert code.count("traj_polar_step(") == 1 and code.count("traj_compose(") == 2
     assert "fmaf" not in code and "__fmaf" not in code and "atomicAdd(&g." not in code  # the only global atomics are integer atomicMax
     assert code.count("atomicMax(") == 2 and "float" not in "".join(re.findall(r"atomic\w+\(([^;]*);", code))
     # the order of the checks: the parameters, then the state, then n_pairs and the owners' key
@@ -129,3 +131,15 @@ def test_constants_defaults_and_the_order_of_the_checks():
     # the mask buffer's address is refused until a loop call has run
     dbg = api[api.index("int orb_debug_loop_mask_buffer("):api.index("int orb_join_pairs(")]
     assert "!p->stage[ST_LOOP].extent" in dbg and "ORB_ESTATE" in dbg and "p->loop.mask" in dbg
+
+
+def test_the_consensus_and_the_compose_are_stated_once():
+    """TJ-3/TJ-4's select and BR-4's compose live in orb_kernels_traj.h; the stages after it call them and hold no copy."""
+    code = {n: re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "orb_kernels_%s.h" % n)).read()) for n in ("traj", "bridge", "join", "loop")}
+    for n in ("bridge", "join", "loop"):
+        assert "hist[" not in code[n] and "__shfl_up" not in code[n], n
+        assert "_compose(" not in code[n].replace("traj_compose(", ""), n
+    assert code["bridge"].count("traj_consensus<") == 1 and code["join"].count("traj_consensus<") == 1
+    # a definition has its return type in front of the name; a call does not
+    assert len(re.findall(r"\bTrajConsensus traj_consensus\(", code["traj"])) == 1
+    assert len(re.findall(r"\bvoid traj_compose\(", code["traj"])) == 1

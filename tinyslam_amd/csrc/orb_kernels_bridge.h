@@ -13,10 +13,10 @@
 //                 clipped at the capacity; a frame that is no gap end leaves at once with a count of 0
 //   k_loc_score   of orb_kernels_localize.h, as it is, on the bridge's buffers with grid.x = frames (BR-3)
 //   k_br_refine   one workgroup per frame: k_loc_refine's fit (loc_fit of orb_kernels_localize.h), the inlier bytes
-//                 by keypoint slot, then BR-5: the ratios' bits, the element of rank (m - 1) / 2 by k_traj_joint's radix select on
-//                 uint32 and the consistent count (integer atomics only: no result depends on an order), the per-frame fix record
-//   k_br_chain    one wave, the arithmetic on lane 0 (BR-6 is sequential by definition); all 64 lanes stage the frame and fix
-//                 records of the next 64 frames in LDS
+//                 by keypoint slot, then BR-5 on the candidates: traj_consensus and traj_verdict of orb_kernels_traj.h (integer
+//                 atomics only: no result depends on an order), the per-frame fix record
+//   k_br_chain    one wave, the arithmetic on lane 0 (BR-6 is sequential by definition; BR-4 is traj_compose); all 64 lanes stage
+//                 the frame and fix records of the next 64 frames in LDS
 #pragma once
 #include "orb_kernels_localize.h"
 #include "orb_kernels_traj.h"
@@ -58,18 +58,6 @@ __device__ __forceinline__ uint32_t br_anchor(const BrArgs& a, uint32_t g, uint3
     return 1u;  // g - T > max_hops
 }
 
-// BR-4: R = Ra Rb after one polar step of RP-4 (the product itself when its det is not finite or not > 0), t = Ra tb + s ta
-__device__ __forceinline__ void br_compose(const float Ra[9], const float ta[3], float s, const float Rb[9], const float tb[3], float R[9],
-                                           float t[3]) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) R[3 * r + c] = (Ra[3 * r] * Rb[c] + Ra[3 * r + 1] * Rb[3 + c]) + Ra[3 * r + 2] * Rb[6 + c];
-        t[r] = ((Ra[3 * r] * tb[0] + Ra[3 * r + 1] * tb[1]) + Ra[3 * r + 2] * tb[2]) + s * ta[r];
-    }
-    traj_polar_step(R);
-}
-
 // grid (frames), block 256
 __global__ __launch_bounds__(256) void k_br_gather(BrArgs a) {
     __shared__ uint32_t wave_n[4];
@@ -83,10 +71,7 @@ __global__ __launch_bounds__(256) void k_br_gather(BrArgs a) {
     const uint32_t* const recT = a.frames + (size_t)T * kBrFrameWords;
     const uint32_t o = recT[14];
     float R[9], t[3];
-#pragma unroll
-    for (int k = 0; k < 9; k++) R[k] = __uint_as_float(recT[k]);
-#pragma unroll
-    for (int k = 0; k < 3; k++) t[k] = __uint_as_float(recT[9 + k]);
+    traj_load_pose(recT, R, t);
     const CornerData* const cg = L.corners + (size_t)g * L.cap;
     const uint32_t first = T > a.window ? T - a.window : 0u;  // BR-2: p + window >= T
     uint32_t base = 0;
@@ -128,17 +113,14 @@ __global__ __launch_bounds__(256) void k_br_gather(BrArgs a) {
 
 // grid (frames), block 256; the inlier bytes are cleared by a memset before
 __global__ __launch_bounds__(256) void k_br_refine(BrArgs a) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t s_join[2];  // m, consistent
-    __shared__ uint32_t s_sel[2];   // the prefix found so far, the rank within it
+    __shared__ TrajSelectLds lds;
     const LocArgs& L = a.loc;
-    const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t g = blockIdx.x, tid = threadIdx.x;
     uint32_t T;
     const uint32_t kind = br_anchor(a, g, T);  // uniform
     const uint32_t M = kind == 2u ? L.n_cand[g] : 0u;
     const float4* const reca = L.reca + (size_t)g * L.cap;
     const float4* const recb = L.recb + (size_t)g * L.cap;
-    if (tid < 2u) s_join[tid] = 0u;  // published by loc_fit's first barrier
     const LocFit fit = loc_fit(L, g, M);
     const bool has_min = fit.has_min, keep = fit.keep;
     const float* const Rk = fit.R;
@@ -150,93 +132,24 @@ __global__ __launch_bounds__(256) void k_br_refine(BrArgs a) {
             const float4 Y = reca[j], k = recb[j];
             if (loc_inlier(Rk, tk, Y.x, Y.y, Y.z, k.x, k.y, L)) mask[__float_as_uint(Y.w)] = 1u;
         }
-    // BR-5
+    // BR-5; join is the same in every thread, as traj_consensus's barriers need
     const bool join = keep && g + 2u <= a.n_frames && a.frames[(size_t)(g + 1u) * kBrFrameWords + 17u] == ORB_TRAJ_START;  // uniform
-    uint32_t m = 0u, gam = 0u, consistent = 0u, verdict = kTrajFew;
+    TrajConsensus c = {0u, 0u, 0u};
+    uint32_t verdict = kTrajFew;
     if (join) {
-        uint32_t* const row = a.ratios + (size_t)g * L.cap;
         const float4* const pts = L.points + (size_t)g * L.cap;
-        const bool first = lane == 0u;
-        // A: the ratio's bits of every candidate (0: none)
-        for (uint32_t j0 = 0u; j0 < M; j0 += 256u) {  // uniform trip count: the ballots see whole waves
-            const uint32_t j = j0 + tid;
-            uint32_t bits = 0u;
-            if (j < M) {
-                const float4 Y = reca[j], k = recb[j];
-                if (loc_inlier(Rk, tk, Y.x, Y.y, Y.z, k.x, k.y, L)) {
-                    const float4 P = pts[__float_as_uint(Y.w)];
-                    if ((__float_as_uint(P.w) & ORB_POINT_GOOD) != 0u) {
-                        float x, y, z;
-                        loc_transform(Rk, tk, Y.x, Y.y, Y.z, x, y, z);
-                        const float rho = z / P.z;
-                        bits = isfinite(rho) && rho > 0.0f ? __float_as_uint(rho) : 0u;
-                    }
-                }
-                row[j] = bits;
-            }
-            const uint32_t n = (uint32_t)__popcll(__ballot(bits != 0u));
-            if (first && n) atomicAdd(&s_join[0], n);
-        }
-        __syncthreads();  // every thread reads back its own stores only; the barrier publishes the count
-        m = s_join[0];
-        if (m) {  // uniform
-            // B: the element of rank (m - 1) / 2 in ascending order of the bits (k_traj_joint's radix select)
-            if (tid == 0u) {
-                s_sel[0] = 0u;
-                s_sel[1] = (m - 1u) / 2u;
-            }
-#pragma unroll 1
-            for (int shift = 24; shift >= 0; shift -= 8) {
-                hist[tid] = 0u;
-                __syncthreads();
-                const uint32_t prefix = s_sel[0];
-                for (uint32_t j = tid; j < M; j += 256u) {
-                    const uint32_t bits = row[j];
-                    const bool in = bits != 0u && (shift == 24 || (bits >> (shift + 8)) == prefix);
-                    if (in) atomicAdd(&hist[bits >> shift & 255u], 1u);
-                }
-                __syncthreads();
-                if (tid < 64u) {  // lane l owns bins 4 l .. 4 l + 3
-                    const uint32_t k = s_sel[1];
-                    const uint32_t h0 = hist[4u * tid], h1 = hist[4u * tid + 1u], h2 = hist[4u * tid + 2u], h3 = hist[4u * tid + 3u];
-                    const uint32_t sum = (h0 + h1) + (h2 + h3);
-                    uint32_t incl = sum;
-#pragma unroll
-                    for (int d = 1; d < 64; d <<= 1) {
-                        const uint32_t up = __shfl_up(incl, d);
-                        if ((int)tid >= d) incl += up;
-                    }
-                    uint32_t lo = incl - sum;  // ratios in the bins below this lane's
-                    if (k >= lo && k < incl) {  // one lane
-                        uint32_t bin = 4u * tid;
-                        const uint32_t hh[3] = {h0, h1, h2};
-                        bool past = true;
-#pragma unroll
-                        for (int q = 0; q < 3; q++) {
-                            past = past && k >= lo + hh[q];
-                            lo += past ? hh[q] : 0u;
-                            bin += past ? 1u : 0u;
-                        }
-                        s_sel[0] = prefix << 8 | bin;
-                        s_sel[1] = k - lo;
-                    }
-                }
-                __syncthreads();
-            }
-            gam = s_sel[0];
-            // C
-            const float gf = __uint_as_float(gam), tg = a.tol * gf;
-            for (uint32_t j0 = 0u; j0 < M; j0 += 256u) {
-                const uint32_t j = j0 + tid;
-                const uint32_t bits = j < M ? row[j] : 0u;
-                const bool in = bits != 0u && fabsf(__uint_as_float(bits) - gf) <= tg;
-                const uint32_t n = (uint32_t)__popcll(__ballot(in));
-                if (first && n) atomicAdd(&s_join[1], n);
-            }
-            __syncthreads();
-            consistent = s_join[1];
-        }
-        verdict = m < a.min_shared ? kTrajFew : (1000ull * consistent < (unsigned long long)a.permille * m ? kTrajSpread : kTrajHolds);
+        // the ratio of candidate j: an inlier whose keypoint has a GOOD point of pair g, its depth after the fix over that point's
+        c = traj_consensus<256u>(lds, a.ratios + (size_t)g * L.cap, M, a.tol, [&](uint32_t j) {
+            const float4 Y = reca[j], k = recb[j];
+            if (!loc_inlier(Rk, tk, Y.x, Y.y, Y.z, k.x, k.y, L)) return 0u;
+            const float4 P = pts[__float_as_uint(Y.w)];
+            if ((__float_as_uint(P.w) & ORB_POINT_GOOD) == 0u) return 0u;
+            float x, y, z;
+            loc_transform(Rk, tk, Y.x, Y.y, Y.z, x, y, z);
+            const float rho = z / P.z;
+            return isfinite(rho) && rho > 0.0f ? __float_as_uint(rho) : 0u;
+        });
+        verdict = traj_verdict(c.m, c.consistent, a.min_shared, a.permille);
     }
     if (tid == 0u) {  // the fix record
         uint32_t* const out = L.fix + (size_t)g * kBrFixWords;
@@ -245,9 +158,9 @@ __global__ __launch_bounds__(256) void k_br_refine(BrArgs a) {
         out[14] = fit.inliers;
         out[15] = fit.h;
         out[16] = loc_status(kind != 2u, M, has_min, keep);
-        out[17] = m;
-        out[18] = gam;
-        out[19] = consistent;
+        out[17] = c.m;
+        out[18] = c.g;
+        out[19] = c.consistent;
         out[20] = join && verdict == kTrajHolds ? 1u : 0u;
         out[21] = out[22] = out[23] = 0u;
     }
@@ -296,10 +209,7 @@ __global__ __launch_bounds__(64) void k_br_chain(BrArgs a) {
             const uint32_t* const P = s_frame + (f - base) * kBrFrameWords;
             const uint32_t* const X = s_fix + (f - base) * kBrFixWords;
             float R[9], t[3];
-#pragma unroll
-            for (int k = 0; k < 9; k++) R[k] = __uint_as_float(P[k]);
-#pragma unroll
-            for (int k = 0; k < 3; k++) t[k] = __uint_as_float(P[9 + k]);
+            traj_load_pose(P, R, t);
             float scale = __uint_as_float(P[12]), gain = 0.0f;
             uint32_t root = f, status, anchor = 0u;
             if (P[17] != ORB_TRAJ_LOST) {
@@ -319,7 +229,7 @@ __global__ __launch_bounds__(64) void k_br_chain(BrArgs a) {
                 } else {
                     status = ORB_BRIDGE_MOVED;
                     float Rn[9], tn[3];
-                    br_compose(R, t, sigma, A, av, Rn, tn);
+                    traj_compose(R, t, sigma, A, av, Rn, tn);
 #pragma unroll
                     for (int k = 0; k < 9; k++) R[k] = Rn[k];
 #pragma unroll
@@ -333,15 +243,12 @@ __global__ __launch_bounds__(64) void k_br_chain(BrArgs a) {
                 if (X[16] == ORB_LOCALIZE_OK) {
                     float Rx[9], tx[3], Rg[9], tg[3], A[9], av[3], sigma;
                     uint32_t ro;
-#pragma unroll
-                    for (int k = 0; k < 9; k++) Rx[k] = __uint_as_float(X[k]);
-#pragma unroll
-                    for (int k = 0; k < 3; k++) tx[k] = __uint_as_float(X[9 + k]);
-                    br_compose(Rx, tx, 1.0f, RT, tT, Rg, tg);  // BR-4: camera g in segment oT
+                    traj_load_pose(X, Rx, tx);
+                    traj_compose(Rx, tx, 1.0f, RT, tT, Rg, tg);  // BR-4: camera g in segment oT
                     br_similarity(a.out, oT, f, A, av, sigma, ro);
                     if (ro != oT) {
                         float Rn[9], tn[3];
-                        br_compose(Rg, tg, sigma, A, av, Rn, tn);
+                        traj_compose(Rg, tg, sigma, A, av, Rn, tn);
 #pragma unroll
                         for (int k = 0; k < 9; k++) Rg[k] = Rn[k];
 #pragma unroll
@@ -350,12 +257,7 @@ __global__ __launch_bounds__(64) void k_br_chain(BrArgs a) {
                     const float sc = sigma * __uint_as_float(X[12]);
                     const bool joined = X[20] != 0u;
                     const float sg = joined ? sigma * __uint_as_float(X[18]) : 0.0f;
-                    bool fin = isfinite(sc) && isfinite(sg);
-#pragma unroll
-                    for (int k = 0; k < 9; k++) fin = fin && isfinite(Rg[k]);
-#pragma unroll
-                    for (int k = 0; k < 3; k++) fin = fin && isfinite(tg[k]);
-                    if (fin) {
+                    if (isfinite(sc) && isfinite(sg) && traj_pose_finite(Rg, tg)) {
                         status = joined ? ORB_BRIDGE_JOINED : ORB_BRIDGE_FIXED;
 #pragma unroll
                         for (int k = 0; k < 9; k++) R[k] = Rg[k];
@@ -369,10 +271,7 @@ __global__ __launch_bounds__(64) void k_br_chain(BrArgs a) {
             }
             const bool gap = P[17] == ORB_TRAJ_LOST;
             uint32_t* const out = a.out + (size_t)f * kBrOutWords;
-#pragma unroll
-            for (int k = 0; k < 9; k++) out[k] = __float_as_uint(R[k]);
-#pragma unroll
-            for (int k = 0; k < 3; k++) out[9 + k] = __float_as_uint(t[k]);
+            traj_store_pose(out, R, t);
             out[12] = __float_as_uint(scale);
             out[13] = __float_as_uint(gain);
             out[14] = root;

@@ -8,16 +8,12 @@
 // (tests/join_ref.py) reproduces every bit.
 //
 //   k_lc_index   of orb_kernels_loop.h, as it is, on an LcArgs of this stage's owner buffer (set to 0xffffffff by a memset) (SJ-2)
-//   k_sj_ratio   one workgroup of 256 per list entry: SJ-3's verdict (uniform), then
-//                A  a query slot per thread, strided over the capacity: the ratio's bits (0: none) to global memory, their number
-//                   through wave ballots and one LDS add per wave
-//                B  the ratio of rank (m - 1) / 2 by a radix select from the most significant byte down: four passes, each a
-//                   256-bin LDS histogram of the ratios that share the prefix found so far, and a prefix over the bins by one wave
-//                C  the ratios within tol g of it, counted like A
-//                then, on one lane, SJ-4, the link record and SJ-5's atomicMax on the segment's 64-bit key
-//                (k_traj_joint's phases, written again here: see section 30); integer atomics only, no result depends on an order
+//   k_sj_ratio   one workgroup of 256 per list entry: SJ-3's verdict (uniform), then traj_consensus of orb_kernels_traj.h over the
+//                query's slots (sj_ratio), then, on one lane, traj_verdict as a link verdict, SJ-4, the link record and SJ-5's
+//                atomicMax on the segment's 64-bit key; integer atomics only, no result depends on an order
 //   k_sj_chain   one wave: the lanes mark the origins, lane 0 walks the frame slots in ascending order and writes SJ-6's table
-//   k_sj_write   a thread per frame: the OrbJoinPose records
+//                (traj_compose)
+//   k_sj_write   a thread per frame: the OrbJoinPose records (traj_compose)
 // Kernels are ordered by launch boundaries only.
 #pragma once
 #include "orb_kernels_loop.h"
@@ -78,17 +74,6 @@ __device__ __forceinline__ bool sj_camera(const uint32_t* rec, bool own, float R
     return fin;
 }
 
-// BR-4's compose(Ra, ta, s; Rb, tb): Ra Rb after one polar step, Ra tb + s ta
-__device__ __forceinline__ void sj_compose(const float Ra[9], const float ta[3], float s, const float Rb[9], const float tb[3], float R[9], float t[3]) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) R[3 * r + c] = (Ra[3 * r] * Rb[c] + Ra[3 * r + 1] * Rb[3 + c]) + Ra[3 * r + 2] * Rb[6 + c];
-        t[r] = ((Ra[3 * r] * tb[0] + Ra[3 * r + 1] * tb[1]) + Ra[3 * r + 2] * tb[2]) + s * ta[r];
-    }
-    traj_polar_step(R);
-}
-
 // SJ-4: coordinates of segment o -> camera b's frame, one unit of b = gamma units of o; false when an entry is not finite
 __device__ __forceinline__ bool sj_similarity(const float P[9], const float p[3], const float Rq[9], const float tq[3], float gamma, float A[9], float a[3]) {
     const float v0 = p[0] - gamma * tq[0], v1 = p[1] - gamma * tq[1], v2 = p[2] - gamma * tq[2];
@@ -99,12 +84,7 @@ __device__ __forceinline__ bool sj_similarity(const float P[9], const float p[3]
         for (int c = 0; c < 3; c++) A[3 * r + c] = (Rq[r] * P[c] + Rq[3 + r] * P[3 + c]) + Rq[6 + r] * P[6 + c];
     }
     traj_polar_step(A);
-    bool fin = isfinite(gamma);
-#pragma unroll
-    for (int k = 0; k < 9; k++) fin = fin && isfinite(A[k]);
-#pragma unroll
-    for (int k = 0; k < 3; k++) fin = fin && isfinite(a[k]);
-    return fin;
+    return isfinite(gamma) && traj_pose_finite(A, a);
 }
 
 // SJ-3: the bits of slot a's ratio of entry e = (q, T), 0 when it has none
@@ -124,9 +104,7 @@ __device__ __forceinline__ uint32_t sj_ratio(const SjArgs& g, uint32_t e, uint32
 
 // grid n_pairs, block kSjThreads
 __global__ __launch_bounds__(kSjThreads) void k_sj_ratio(SjArgs g) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t s_count[2];  // m, consistent
-    __shared__ uint32_t s_sel[2];    // the prefix found so far, the rank within it
+    __shared__ TrajSelectLds lds;
     const uint32_t e = blockIdx.x, tid = threadIdx.x, cap = g.cap;
     const uint2 qt = g.list[e];
     const uint32_t q = qt.x, T = qt.y;
@@ -142,113 +120,36 @@ __global__ __launch_bounds__(kSjThreads) void k_sj_ratio(SjArgs g) {
     else if (o > b) verdict = kSjForward;
     float P[9], p[3], Rq[9], tq[3];
     if (verdict == kSjHolds) {
-        bool fin = sj_camera(g.frames + (size_t)q * kSjFrameWords, q == b, Rq, tq);
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            P[k] = __uint_as_float(fix[13 + k]);
-            fin = fin && isfinite(P[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            p[k] = __uint_as_float(fix[22 + k]);
-            fin = fin && isfinite(p[k]);
-        }
-        if (!fin) verdict = kSjNonfinite;
+        const bool fin = sj_camera(g.frames + (size_t)q * kSjFrameWords, q == b, Rq, tq);
+        traj_load_pose(fix + 13, P, p);  // OrbLoopFix's pose of camera q in segment o
+        if (!fin || !traj_pose_finite(P, p)) verdict = kSjNonfinite;
     }
     if (verdict != kSjHolds) {
         if (tid < kSjLinkWords) link[tid] = tid == 0u ? verdict : (tid == 1u ? o : (tid == 2u ? b : 0u));
         return;
     }
     const uint32_t nq = min(g.counts[q], cap), nt = min(g.counts[T], cap);
-    uint32_t* const row = g.ratios + (size_t)e * cap;
-    const bool first = (tid & 63u) == 0u;
-    if (tid < 2u) s_count[tid] = 0u;
-    __syncthreads();
-    // A
-    for (uint32_t base = 0u; base < cap; base += kSjThreads) {  // uniform trip count: the ballots see whole waves
-        const uint32_t a = base + tid;
-        const uint32_t bits = a < cap ? sj_ratio(g, e, q, T, a, nq, nt, P + 6, p[2], Rq + 6, tq[2]) : 0u;
-        if (a < cap) row[a] = bits;
-        const uint32_t n = (uint32_t)__popcll(__ballot(bits != 0u));
-        if (first && n) atomicAdd(&s_count[0], n);
-    }
-    __syncthreads();  // every thread reads back its own stores only; the barrier publishes the count
-    const uint32_t m = s_count[0];
-    uint32_t gb = 0u;
-    if (m) {  // uniform
-        // B: the element of rank (m - 1) / 2 in ascending order of the bits
-        if (tid == 0u) {
-            s_sel[0] = 0u;
-            s_sel[1] = (m - 1u) / 2u;
-        }
-#pragma unroll 1
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            hist[tid] = 0u;
-            __syncthreads();
-            const uint32_t prefix = s_sel[0];
-            for (uint32_t i = tid; i < cap; i += kSjThreads) {
-                const uint32_t bits = row[i];
-                const bool in = bits != 0u && (shift == 24 || (bits >> (shift + 8)) == prefix);
-                if (in) atomicAdd(&hist[bits >> shift & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid < 64u) {  // lane l owns bins 4 l .. 4 l + 3
-                const uint32_t k = s_sel[1];
-                const uint32_t h0 = hist[4u * tid], h1 = hist[4u * tid + 1u], h2 = hist[4u * tid + 2u], h3 = hist[4u * tid + 3u];
-                const uint32_t sum = (h0 + h1) + (h2 + h3);
-                uint32_t incl = sum;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t up = __shfl_up(incl, d);
-                    if ((int)tid >= d) incl += up;
-                }
-                uint32_t lo = incl - sum;  // ratios in the bins below this lane's
-                if (k >= lo && k < incl) {  // one lane: 0 <= k < the ratios that share the prefix
-                    uint32_t bin = 4u * tid;
-                    const uint32_t h[3] = {h0, h1, h2};
-                    bool past = true;  // k lies past every bin so far
-#pragma unroll
-                    for (int c = 0; c < 3; c++) {
-                        past = past && k >= lo + h[c];
-                        lo += past ? h[c] : 0u;
-                        bin += past ? 1u : 0u;
-                    }
-                    s_sel[0] = prefix << 8 | bin;
-                    s_sel[1] = k - lo;
-                }
-            }
-            __syncthreads();
-        }
-        gb = s_sel[0];
-        // C
-        const float gf = __uint_as_float(gb), tg = g.tol * gf;
-        for (uint32_t base = 0u; base < cap; base += kSjThreads) {
-            const uint32_t i = base + tid;
-            const uint32_t bits = i < cap ? row[i] : 0u;
-            const bool in = bits != 0u && fabsf(__uint_as_float(bits) - gf) <= tg;
-            const uint32_t n = (uint32_t)__popcll(__ballot(in));
-            if (first && n) atomicAdd(&s_count[1], n);
-        }
-        __syncthreads();
-    }
+    const TrajConsensus c = traj_consensus<kSjThreads>(lds, g.ratios + (size_t)e * cap, cap, g.tol, [&](uint32_t a) {
+        return sj_ratio(g, e, q, T, a, nq, nt, P + 6, p[2], Rq + 6, tq[2]);
+    });
     if (tid == 0u) {
-        const uint32_t consistent = s_count[1];
-        verdict = m < g.min_shared ? kSjRatioFew : (1000ull * consistent < (unsigned long long)g.permille * m ? kSjRatioSpread : kSjHolds);
+        const uint32_t tv = traj_verdict(c.m, c.consistent, g.min_shared, g.permille);
+        verdict = tv == kTrajFew ? kSjRatioFew : (tv == kTrajSpread ? kSjRatioSpread : kSjHolds);
         if (verdict == kSjHolds) {  // SJ-4; SJ-6 forms it again from the same words
             float A[9], a[3];
-            if (!sj_similarity(P, p, Rq, tq, __uint_as_float(gb), A, a)) verdict = kSjNonfinite;
+            if (!sj_similarity(P, p, Rq, tq, __uint_as_float(c.g), A, a)) verdict = kSjNonfinite;
         }
         const bool nf = verdict == kSjNonfinite;
         link[0] = verdict;
         link[1] = o;
         link[2] = b;
-        link[3] = nf ? 0u : m;
-        link[4] = nf ? 0u : consistent;
-        link[5] = nf ? 0u : gb;
+        link[3] = nf ? 0u : c.m;
+        link[4] = nf ? 0u : c.consistent;
+        link[5] = nf ? 0u : c.g;
         link[6] = 0u;
         link[7] = 0u;
         // SJ-5: the most consistent ratios, then the lowest index (b < F: RANGE otherwise)
-        if (verdict == kSjHolds) atomicMax(&g.keys[b], (unsigned long long)consistent << 32 | (unsigned long long)(kSjNone - e));
+        if (verdict == kSjHolds) atomicMax(&g.keys[b], (unsigned long long)c.consistent << 32 | (unsigned long long)(kSjNone - e));
     }
 }
 
@@ -278,27 +179,16 @@ __global__ __launch_bounds__(64) void k_sj_chain(SjArgs g) {
             const float gamma = __uint_as_float(g.links[(size_t)e * kSjLinkWords + 5u]);
             float P[9], p[3], Rq[9], tq[3], Al[9], al[3];
             sj_camera(g.frames + (size_t)q * kSjFrameWords, q == b, Rq, tq);
-#pragma unroll
-            for (int k = 0; k < 9; k++) P[k] = __uint_as_float(fix[13 + k]);
-#pragma unroll
-            for (int k = 0; k < 3; k++) p[k] = __uint_as_float(fix[22 + k]);
+            traj_load_pose(fix + 13, P, p);
             sj_similarity(P, p, Rq, tq, gamma, Al, al);
             const uint32_t* const So = g.segs + (size_t)o * kSjSegWords;
             float Ao[9], ao[3];
-#pragma unroll
-            for (int k = 0; k < 9; k++) Ao[k] = __uint_as_float(So[k]);
-#pragma unroll
-            for (int k = 0; k < 3; k++) ao[k] = __uint_as_float(So[9 + k]);
+            traj_load_pose(So, Ao, ao);
             const float so = __uint_as_float(So[12]);
             float An[9], an[3];
-            sj_compose(Al, al, so, Ao, ao, An, an);
+            traj_compose(Al, al, so, Ao, ao, An, an);
             const float sn = so * gamma;
-            bool fin = isfinite(sn);
-#pragma unroll
-            for (int k = 0; k < 9; k++) fin = fin && isfinite(An[k]);
-#pragma unroll
-            for (int k = 0; k < 3; k++) fin = fin && isfinite(an[k]);
-            if (fin) {
+            if (isfinite(sn) && traj_pose_finite(An, an)) {
 #pragma unroll
                 for (int k = 0; k < 9; k++) A[k] = An[k];
 #pragma unroll
@@ -309,10 +199,7 @@ __global__ __launch_bounds__(64) void k_sj_chain(SjArgs g) {
                 g.links[(size_t)e * kSjLinkWords + 6u] = 1u;
             }
         }
-#pragma unroll
-        for (int k = 0; k < 9; k++) S[k] = __float_as_uint(A[k]);
-#pragma unroll
-        for (int k = 0; k < 3; k++) S[9 + k] = __float_as_uint(a[k]);
+        traj_store_pose(S, A, a);
         S[12] = __float_as_uint(sigma);
         S[13] = root;
         S[14] = linked;
@@ -339,16 +226,10 @@ __global__ __launch_bounds__(kSjThreads) void k_sj_write(SjArgs g) {
     }
     float R[9], t[3], A[9], a[3], Rn[9], tn[3];
     sj_camera(rec, f == b, R, t);
-#pragma unroll
-    for (int k = 0; k < 9; k++) A[k] = __uint_as_float(S[k]);
-#pragma unroll
-    for (int k = 0; k < 3; k++) a[k] = __uint_as_float(S[9 + k]);
+    traj_load_pose(S, A, a);
     const float sigma = __uint_as_float(S[12]);
-    sj_compose(R, t, sigma, A, a, Rn, tn);
-#pragma unroll
-    for (int k = 0; k < 9; k++) out[k] = __float_as_uint(Rn[k]);
-#pragma unroll
-    for (int k = 0; k < 3; k++) out[9 + k] = __float_as_uint(tn[k]);
+    traj_compose(R, t, sigma, A, a, Rn, tn);
+    traj_store_pose(out, Rn, tn);
     out[12] = __float_as_uint(sigma * __uint_as_float(rec[12]));
     out[13] = __float_as_uint(sigma);
     out[14] = root;

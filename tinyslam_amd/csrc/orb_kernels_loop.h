@@ -14,8 +14,8 @@
 //                 camera T's frame, the query keypoint and its ray (LC-3), compacted in the order of the query's slots by
 //                 k_loc_gather's step (loc_compact, loc_candidate), plus the candidate of every slot (or kVerifyNone)
 //   k_loc_score   of orb_kernels_localize.h, as it is, on the stage's buffers with grid.x = list entries (LC-4)
-//   k_lc_refine   one workgroup per list entry: k_loc_refine's fit (loc_fit of orb_kernels_localize.h), then LC-5's compose, the
-//                 inlier bytes by query slot (loc_slot_bytes) and the record (LC-6)
+//   k_lc_refine   one workgroup per list entry: k_loc_refine's fit (loc_fit of orb_kernels_localize.h), then LC-5's compose
+//                 (traj_compose of orb_kernels_traj.h with s = 1), the inlier bytes by query slot (loc_slot_bytes) and the record (LC-6)
 // Kernels are ordered by launch boundaries only.
 #pragma once
 #include "orb_kernels_localize.h"
@@ -142,18 +142,8 @@ __global__ __launch_bounds__(256) void k_lc_refine(LcArgs a) {
         uint32_t* const out = L.fix + (size_t)e * kLcFixWords;
         // LC-5: camera q in segment o's frame, R Rt after one polar step and R tT + t; zeros when an entry is not finite
         float Rp[9], tp[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) Rp[3 * r + c] = (f.R[3 * r] * RT[c] + f.R[3 * r + 1] * RT[3 + c]) + f.R[3 * r + 2] * RT[6 + c];
-            tp[r] = ((f.R[3 * r] * tT[0] + f.R[3 * r + 1] * tT[1]) + f.R[3 * r + 2] * tT[2]) + 1.0f * f.t[r];
-        }
-        traj_polar_step(Rp);
-        bool fin = has_min;
-#pragma unroll
-        for (int k = 0; k < 9; k++) fin = fin && isfinite(Rp[k]);
-#pragma unroll
-        for (int k = 0; k < 3; k++) fin = fin && isfinite(tp[k]);
+        traj_compose(f.R, f.t, 1.0f, RT, tT, Rp, tp);
+        const bool fin = has_min && traj_pose_finite(Rp, tp);
         loc_put_pose(out, f);
 #pragma unroll
         for (int k = 0; k < 9; k++) out[13 + k] = fin ? __float_as_uint(Rp[k]) : 0u;

@@ -7,14 +7,9 @@
 // (tests/trajectory_ref.py) reproduces every bit.
 //
 //   k_traj_joint   one workgroup of 1024 threads per joint f = 1 .. n_frames - 2 (it leaves at once unless both pairs are OK):
-//                  A  a query of pair f - 1 per thread, strided over the capacity: the ratio's bits (0: none) to global memory, their
-//                     number through wave ballots and one LDS add per wave
-//                  B  the ratio of rank (m - 1) / 2 by a radix select from the most significant byte down: four passes, each a
-//                     256-bin LDS histogram of the ratios that share the prefix found so far, and a prefix over the bins by one wave
-//                  C  the ratios within tol g of it, counted like A
-//                  integer atomics only: no result depends on an order
-//   k_traj_chain   one wave, the arithmetic on lane 0 (TJ-5 is sequential by definition); all 64 lanes stage the pose and joint
-//                  records of the next 64 frames in LDS
+//                  traj_consensus over the queries of pair f - 1 (traj_ratio), then the joint record with traj_verdict
+//   k_traj_chain   one wave, the arithmetic on lane 0 (TJ-5 is sequential by definition: traj_compose); all 64 lanes stage the pose
+//                  and joint records of the next 64 frames in LDS
 //   k_traj_map     grid (pairs, ceil(cap / 1024)): the points of pair f in the frame and unit of frame f + 1's origin, one
 //                  16-byte store per slot
 #pragma once
@@ -62,53 +57,63 @@ __device__ __forceinline__ uint32_t traj_ratio(const TrajArgs& a, uint32_t f, ui
     return isfinite(rho) && rho > 0.0f ? __float_as_uint(rho) : 0u;
 }
 
-// grid n_frames - 2 (joint f = blockIdx.x + 1), block kTrajThreads
-__global__ __launch_bounds__(kTrajThreads) void k_traj_joint(TrajArgs a) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t s_count[2];  // m, consistent
-    __shared__ uint32_t s_sel[2];    // the prefix found so far, the rank within it
-    const uint32_t f = blockIdx.x + 1u, tid = threadIdx.x;
-    const uint32_t* const pa = a.poses + (size_t)(f - 1u) * kPoseWords;
-    if (pa[15] != ORB_POSE_OK || a.poses[(size_t)f * kPoseWords + 15] != ORB_POSE_OK) return;  // uniform
-    const uint32_t nq_prev = min(a.counts[f - 1u], a.cap), nq = min(a.counts[f], a.cap);
-    const float r[3] = {__uint_as_float(pa[6]), __uint_as_float(pa[7]), __uint_as_float(pa[8])};
-    const float t2 = __uint_as_float(pa[11]);
-    uint32_t* const row = a.ratios + (size_t)f * a.cap;
+// What the stages after this one take from it (bridge, loop, join): the consensus, the compose and the twelve pose words.
+
+struct TrajSelectLds {  // declared __shared__ by the kernel
+    uint32_t hist[256];
+    uint32_t count[2];  // m, consistent
+    uint32_t sel[2];    // the prefix found so far, the rank within it
+};
+struct TrajConsensus {
+    uint32_t m, g, consistent;  // the ratios, the bits of their lower median (0: m == 0), the ratios within tol g of it
+};
+
+// TJ-3/TJ-4 on the n slots of `row`, by a workgroup of kThreads: ratio_bits(i), i < n, gives slot i's ratio as bits (0: none).
+// Every thread of the workgroup must make the call (it holds barriers): call sites are workgroup-uniform.
+//   A  a slot per thread, strided over n: the bits to global memory, their number through wave ballots and one LDS add per wave
+//   B  the ratio of rank (m - 1) / 2 by a radix select from the most significant byte down: four passes, each a 256-bin LDS
+//      histogram of the ratios that share the prefix found so far, and a prefix over the bins by one wave
+//   C  the ratios within tol g of it, counted like A
+// Integer atomics only: no result depends on an order.
+template <uint32_t kThreads, class Ratio>
+__device__ __forceinline__ TrajConsensus traj_consensus(TrajSelectLds& s, uint32_t* row, uint32_t n, float tol, Ratio ratio_bits) {
+    static_assert(kThreads >= 256u && kThreads % 64u == 0u, "a thread per bin, whole waves");
+    const uint32_t tid = threadIdx.x;
     const bool first = (tid & 63u) == 0u;
-    if (tid < 2u) s_count[tid] = 0u;
+    if (tid < 2u) s.count[tid] = 0u;
     __syncthreads();
     // A
-    for (uint32_t base = 0u; base < a.cap; base += kTrajThreads) {  // uniform trip count: the ballots see whole waves
+    for (uint32_t base = 0u; base < n; base += kThreads) {  // uniform trip count: the ballots see whole waves
         const uint32_t i = base + tid;
-        const uint32_t bits = i < a.cap ? traj_ratio(a, f, i, nq_prev, nq, r, t2) : 0u;
-        if (i < a.cap) row[i] = bits;
-        const uint32_t n = (uint32_t)__popcll(__ballot(bits != 0u));
-        if (first && n) atomicAdd(&s_count[0], n);
+        const uint32_t bits = i < n ? ratio_bits(i) : 0u;
+        if (i < n) row[i] = bits;
+        const uint32_t c = (uint32_t)__popcll(__ballot(bits != 0u));
+        if (first && c) atomicAdd(&s.count[0], c);
     }
     __syncthreads();  // every thread reads back its own stores only; the barrier publishes the count
-    const uint32_t m = s_count[0];
+    const uint32_t m = s.count[0];
     uint32_t g = 0u;
     if (m) {  // uniform
         // B: the element of rank (m - 1) / 2 in ascending order of the bits
         if (tid == 0u) {
-            s_sel[0] = 0u;
-            s_sel[1] = (m - 1u) / 2u;
+            s.sel[0] = 0u;
+            s.sel[1] = (m - 1u) / 2u;
         }
 #pragma unroll 1
         for (int shift = 24; shift >= 0; shift -= 8) {
-            if (tid < 256u) hist[tid] = 0u;
+            if (kThreads == 256u || tid < 256u) s.hist[tid] = 0u;
             __syncthreads();
-            const uint32_t prefix = s_sel[0];
-            for (uint32_t i = tid; i < a.cap; i += kTrajThreads) {
+            const uint32_t prefix = s.sel[0];
+            for (uint32_t i = tid; i < n; i += kThreads) {
                 const uint32_t bits = row[i];
                 // shift 24: every ratio shares the empty prefix (a shift by 32 is not one)
                 const bool in = bits != 0u && (shift == 24 || (bits >> (shift + 8)) == prefix);
-                if (in) atomicAdd(&hist[bits >> shift & 255u], 1u);
+                if (in) atomicAdd(&s.hist[bits >> shift & 255u], 1u);
             }
             __syncthreads();
             if (tid < 64u) {  // lane l owns bins 4 l .. 4 l + 3
-                const uint32_t k = s_sel[1];
-                const uint32_t h0 = hist[4u * tid], h1 = hist[4u * tid + 1u], h2 = hist[4u * tid + 2u], h3 = hist[4u * tid + 3u];
+                const uint32_t k = s.sel[1];
+                const uint32_t h0 = s.hist[4u * tid], h1 = s.hist[4u * tid + 1u], h2 = s.hist[4u * tid + 2u], h3 = s.hist[4u * tid + 3u];
                 const uint32_t sum = (h0 + h1) + (h2 + h3);
                 uint32_t incl = sum;
 #pragma unroll
@@ -127,31 +132,49 @@ __global__ __launch_bounds__(kTrajThreads) void k_traj_joint(TrajArgs a) {
                         lo += past ? h[q] : 0u;
                         bin += past ? 1u : 0u;
                     }
-                    s_sel[0] = prefix << 8 | bin;
-                    s_sel[1] = k - lo;
+                    s.sel[0] = prefix << 8 | bin;
+                    s.sel[1] = k - lo;
                 }
             }
             __syncthreads();
         }
-        g = s_sel[0];
+        g = s.sel[0];
         // C
-        const float gf = __uint_as_float(g), tg = a.tol * gf;
-        for (uint32_t base = 0u; base < a.cap; base += kTrajThreads) {
+        const float gf = __uint_as_float(g), tg = tol * gf;
+        for (uint32_t base = 0u; base < n; base += kThreads) {
             const uint32_t i = base + tid;
-            const uint32_t bits = i < a.cap ? row[i] : 0u;
+            const uint32_t bits = i < n ? row[i] : 0u;
             const bool in = bits != 0u && fabsf(__uint_as_float(bits) - gf) <= tg;
-            const uint32_t n = (uint32_t)__popcll(__ballot(in));
-            if (first && n) atomicAdd(&s_count[1], n);
+            const uint32_t c = (uint32_t)__popcll(__ballot(in));
+            if (first && c) atomicAdd(&s.count[1], c);
         }
         __syncthreads();
     }
-    if (tid == 0u) {
-        const uint32_t consistent = s_count[1];
+    return {m, g, s.count[1]};
+}
+
+// TJ-4
+__device__ __forceinline__ uint32_t traj_verdict(uint32_t m, uint32_t consistent, uint32_t min_shared, uint32_t permille) {
+    return m < min_shared ? kTrajFew : (1000ull * consistent < (unsigned long long)permille * m ? kTrajSpread : kTrajHolds);
+}
+
+// grid n_frames - 2 (joint f = blockIdx.x + 1), block kTrajThreads
+__global__ __launch_bounds__(kTrajThreads) void k_traj_joint(TrajArgs a) {
+    __shared__ TrajSelectLds lds;
+    const uint32_t f = blockIdx.x + 1u;
+    const uint32_t* const pa = a.poses + (size_t)(f - 1u) * kPoseWords;
+    if (pa[15] != ORB_POSE_OK || a.poses[(size_t)f * kPoseWords + 15] != ORB_POSE_OK) return;  // uniform
+    const uint32_t nq_prev = min(a.counts[f - 1u], a.cap), nq = min(a.counts[f], a.cap);
+    const float r[3] = {__uint_as_float(pa[6]), __uint_as_float(pa[7]), __uint_as_float(pa[8])};
+    const float t2 = __uint_as_float(pa[11]);
+    const TrajConsensus c = traj_consensus<kTrajThreads>(lds, a.ratios + (size_t)f * a.cap, a.cap, a.tol,
+                                                         [&](uint32_t i) { return traj_ratio(a, f, i, nq_prev, nq, r, t2); });
+    if (threadIdx.x == 0u) {
         uint32_t* const out = a.joints + (size_t)f * kTrajJointWords;
-        out[0] = m;
-        out[1] = g;
-        out[2] = consistent;
-        out[3] = m < a.min_shared ? kTrajFew : (1000ull * consistent < (unsigned long long)a.permille * m ? kTrajSpread : kTrajHolds);
+        out[0] = c.m;
+        out[1] = c.g;
+        out[2] = c.consistent;
+        out[3] = traj_verdict(c.m, c.consistent, a.min_shared, a.permille);
     }
 }
 
@@ -166,6 +189,42 @@ __device__ __forceinline__ void traj_polar_step(float r[9]) {
         const float s = 0.5f * (r[k] + c[k] / det);
         r[k] = ok ? s : r[k];
     }
+}
+
+// TJ-5 / BR-4: R = Ra Rb after one polar step (the product itself when its det is not finite or not > 0), t = Ra tb + s ta
+__device__ __forceinline__ void traj_compose(const float Ra[9], const float ta[3], float s, const float Rb[9], const float tb[3], float R[9],
+                                             float t[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) R[3 * r + c] = (Ra[3 * r] * Rb[c] + Ra[3 * r + 1] * Rb[3 + c]) + Ra[3 * r + 2] * Rb[6 + c];
+        t[r] = ((Ra[3 * r] * tb[0] + Ra[3 * r + 1] * tb[1]) + Ra[3 * r + 2] * tb[2]) + s * ta[r];
+    }
+    traj_polar_step(R);
+}
+
+// the twelve pose words of a record: R[9], t[3]
+__device__ __forceinline__ void traj_load_pose(const uint32_t* w, float R[9], float t[3]) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) R[k] = __uint_as_float(w[k]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) t[k] = __uint_as_float(w[9 + k]);
+}
+
+__device__ __forceinline__ void traj_store_pose(uint32_t* w, const float R[9], const float t[3]) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) w[k] = __float_as_uint(R[k]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) w[9 + k] = __float_as_uint(t[k]);
+}
+
+__device__ __forceinline__ bool traj_pose_finite(const float R[9], const float t[3]) {
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 9; k++) fin = fin && isfinite(R[k]);
+#pragma unroll
+    for (int k = 0; k < 3; k++) fin = fin && isfinite(t[k]);
+    return fin;
 }
 
 // grid 1, block 64
@@ -209,10 +268,7 @@ __global__ __launch_bounds__(64) void k_traj_chain(TrajArgs a) {
             const uint32_t* const P = s_pose + (f - base) * kPoseWords;
             const uint32_t* const J = s_joint + (f - base) * kTrajJointWords;
             float pr[9], pt[3];
-#pragma unroll
-            for (int k = 0; k < 9; k++) pr[k] = __uint_as_float(P[k]);
-#pragma unroll
-            for (int k = 0; k < 3; k++) pt[k] = __uint_as_float(P[9 + k]);
+            traj_load_pose(P, pr, pt);
             const bool ok = P[15] == ORB_POSE_OK;
             uint32_t status, shared = 0u, consistent = 0u;
             float step = 0.0f;
@@ -230,13 +286,7 @@ __global__ __launch_bounds__(64) void k_traj_chain(TrajArgs a) {
             if (status == ORB_TRAJ_CHAINED) {
                 scale = scale * step;
                 float M[9], u[3];
-#pragma unroll
-                for (int r = 0; r < 3; r++) {
-#pragma unroll
-                    for (int c = 0; c < 3; c++) M[3 * r + c] = (pr[3 * r] * R[c] + pr[3 * r + 1] * R[3 + c]) + pr[3 * r + 2] * R[6 + c];
-                    u[r] = ((pr[3 * r] * t[0] + pr[3 * r + 1] * t[1]) + pr[3 * r + 2] * t[2]) + scale * pt[r];
-                }
-                traj_polar_step(M);
+                traj_compose(pr, pt, scale, R, t, M, u);  // TJ-5
 #pragma unroll
                 for (int k = 0; k < 9; k++) R[k] = M[k];
 #pragma unroll
@@ -252,10 +302,7 @@ __global__ __launch_bounds__(64) void k_traj_chain(TrajArgs a) {
             }
             prev_ok = ok;
             uint32_t* const out = a.frames + (size_t)f * kTrajFrameWords;
-#pragma unroll
-            for (int k = 0; k < 9; k++) out[k] = __float_as_uint(R[k]);
-#pragma unroll
-            for (int k = 0; k < 3; k++) out[9 + k] = __float_as_uint(t[k]);
+            traj_store_pose(out, R, t);
             out[12] = __float_as_uint(scale);
             out[13] = __float_as_uint(step);
             out[14] = origin;
