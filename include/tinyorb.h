@@ -1191,6 +1191,54 @@ int orb_join_links(OrbProgram *p, OrbJoinLink *dst, size_t n);
  * orb_loop_pairs_read and orb_join_pairs read.  The caller orders its own writes.  ORB_ESTATE until a loop call has run. */
 int orb_debug_loop_mask_buffer(OrbProgram *p, void **mask);
 
+/* ---- corrected poses and landmarks in one root frame (NOT in the reference; definition RM-1..RM-6 in DESIGN.md section 31) ----
+ * orb_graph_pairs leaves corrected cameras per segment and orb_join_pairs every segment's similarity to its root; neither moves a
+ * landmark.  This stage hands out one corrected map: every frame's camera -- the graph's where the graph moved it, else the
+ * trajectory's -- composed with its segment's similarity, and every GOOD landmark of orb_landmarks_consecutive carried along: with
+ * the camera of its first view from where the trajectory had it to where the graph put it, then through the similarity into the
+ * root's frame and unit.  Nothing is triangulated again.  Binary32 arithmetic in a fixed order, no fused operations: a CPU
+ * restatement gives the same bits.  Nothing is fed back into another stage, and no other stage's results are written. */
+#define ORB_REMAP_GRAPH 1u              /* flags: the last orb_graph_pairs is a source */
+#define ORB_REMAP_JOIN 2u               /* flags: the last orb_join_pairs is a source; flags 0: both */
+#define ORB_REMAP_FROM_GRAPH 1u         /* status bit: r, t start from the graph's record (REFINED, STALLED or FAILED) */
+#define ORB_REMAP_MOVED 2u              /* status bit: the frame's segment is LINKED: the frame in its root's frame and unit */
+typedef struct {            /* zero-initialised = the defaults */
+    uint32_t flags;         /* ORB_REMAP_GRAPH | ORB_REMAP_JOIN; 0: both */
+    uint32_t reserved[7];   /* must be 0 (ORB_EINVAL otherwise) */
+} OrbRemapParams;           /* 32 bytes */
+
+typedef struct {
+    float r[9];             /* row-major R, X_f = R X_root + t */
+    float t[3];
+    float scale;            /* gain * the trajectory's scale */
+    float gain;             /* units of the root per unit of the frame's segment; 1 unless MOVED */
+    uint32_t root;          /* the origin whose frame this is */
+    uint32_t status;        /* ORB_REMAP_FROM_GRAPH | ORB_REMAP_MOVED */
+} OrbRemapPose;             /* 64 bytes */
+
+typedef struct {
+    uint32_t good;          /* records with ORB_POINT_GOOD among the pair's max_features slots */
+    uint32_t moved;         /* of them, those written through at least one step with finite coordinates */
+    uint32_t dropped;       /* of them, those a step left with a coordinate that is not finite: written with x, y, z, flags 0 */
+    uint32_t root;          /* the root of the pair's segment; the landmark row's origin when it has none (0xffffffff as it is) */
+} OrbRemapRow;              /* 16 bytes */
+
+/* ORB_EINVAL for a NULL program, an unknown flag or a reserved word that is not 0 (params NULL: the defaults); then ORB_ESTATE
+ * unless the last orb_trajectory_consecutive, orb_landmarks_consecutive and every named source are all of the current batch and
+ * output set; then ORB_ESTATE when a named source covered another number of frames than the last trajectory call (it was computed
+ * from an earlier one).  Asynchronous on `stream` (NULL: as orb_match_guided chooses; the call does not change it), ordered behind
+ * those stages' last calls and the last call of its own when they ran on another stream; they wait for such a call on another
+ * stream before they overwrite what it reads.  Result buffers of its own (allocated by the first call: 32 bytes per keypoint slot
+ * of max_batch). */
+int orb_remap_frames(OrbProgram *p, const OrbRemapParams *params, void *stream);
+/* Copy the record of frame `frame` of the last orb_remap_frames call to the host (synchronises); ORB_ESTATE before any call,
+ * ORB_EINVAL for a frame outside the frames of the trajectory call it read or pose NULL. */
+int orb_remap_read(OrbProgram *p, uint32_t frame, OrbRemapPose *pose);
+/* Copy the row of pair `pair` of the last orb_remap_frames call (row may be NULL) and its first n landmark records (indexed as
+ * orb_landmarks_read) to the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside the pairs it covered
+ * (the landmarks call's, at most the trajectory call's frames - 1) or landmarks NULL with n > 0. */
+int orb_remap_landmarks(OrbProgram *p, uint32_t pair, OrbRemapRow *row, OrbLandmark *landmarks, size_t n);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

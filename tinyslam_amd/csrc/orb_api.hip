@@ -41,6 +41,7 @@
 #include "orb_kernels_loop.h"
 #include "orb_kernels_graph.h"
 #include "orb_kernels_join.h"
+#include "orb_kernels_remap.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -76,7 +77,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_JOIN, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_JOIN, ST_REMAP, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -130,6 +131,11 @@ constexpr StageInfo kStages[ST_COUNT] = {
      1u << ST_LANDMARK |  // d_mland: the two landmarks of a ratio
      1u << ST_PAIRS |     // d_plist, d_prows: q, T and the matched keypoint
      1u << ST_LOOP},      // loop.fix, loop.mask: camera q in the target's segment, the inliers
+    {"remap_frames", "remap_read",  // a call waits for the sources its flags name
+     1u << ST_TRAJ |      // d_jframe: the cameras and their segments
+     1u << ST_LANDMARK |  // d_mland, d_mrow: the records it moves
+     1u << ST_GRAPH |     // d_gpose (ORB_REMAP_GRAPH)
+     1u << ST_JOIN},      // d_sseg (ORB_REMAP_JOIN)
     {"place_frames", "place_read",
      1u << ST_TRACK},     // d_tframe: the keyframe column (ORB_PLACE_KEYFRAMES)
     {"match_pairs", "match_pairs_read", 0u},
@@ -186,6 +192,14 @@ static_assert(sizeof(OrbJoinPose) == kSjPoseWords * sizeof(uint32_t) && sizeof(O
                   kSjFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) && kSjFixWords * sizeof(uint32_t) == sizeof(OrbLoopFix) &&
                   offsetof(OrbLoopFix, inliers) == 28 * sizeof(uint32_t) && offsetof(OrbLoopFix, pose_t) == 22 * sizeof(uint32_t),
               "join layouts");
+static_assert(sizeof(OrbRemapPose) == kRmPoseWords * sizeof(uint32_t) && sizeof(OrbRemapRow) == kRmRowWords * sizeof(uint32_t) && sizeof(OrbRemapParams) == 32 &&
+                  sizeof(OrbLandmarkRow) == kRmRowWords * sizeof(uint32_t) && offsetof(OrbLandmarkRow, origin) == 3 * sizeof(uint32_t) &&
+                  offsetof(OrbLandmark, origin) == 5 * sizeof(uint32_t) && offsetof(OrbLandmark, views) == 4 * sizeof(uint32_t) &&
+                  kRmFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) && kRmGraphWords * sizeof(uint32_t) == sizeof(OrbGraphPose) &&
+                  kRmSegWords * sizeof(uint32_t) == sizeof(OrbJoinSegment) && offsetof(OrbJoinSegment, root) == 13 * sizeof(uint32_t) &&
+                  kRmFromGraph == ORB_REMAP_FROM_GRAPH && kRmMoved == ORB_REMAP_MOVED && kRmSegLinked == ORB_JOIN_SEGMENT_LINKED &&
+                  kRmGraphRefined == ORB_GRAPH_REFINED && kRmGraphFailed == ORB_GRAPH_FAILED && ORB_GRAPH_STALLED == 3u,
+              "remap layouts");
 
 // The last call of a stage
 struct Stage {
@@ -329,6 +343,12 @@ struct OrbProgram {
     uint32_t* d_sseg = nullptr;           // [max_batch][16] OrbJoinSegment
     uint32_t* d_spose = nullptr;          // [max_batch][16] OrbJoinPose
     uint32_t join_pairs = 0;              // n_pairs of the last call (its Stage's extent is the frames)
+    // orb_remap_frames (orb_kernels_remap.h)
+    uint32_t* d_rpose = nullptr;          // [max_batch][16] OrbRemapPose
+    uint32_t* d_rrow = nullptr;           // [max_batch][4] OrbRemapRow
+    float4* d_rland = nullptr;            // [max_batch][max_features][2] OrbLandmark
+    uint32_t remap_pairs = 0;             // the pairs of the last call (its Stage's extent is the frames)
+    int remap_slots = 0;                  // slots per thread of k_rm_land: two (TINYORB_REMAP_SLOTS=1: one); 0 until the first call
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -600,6 +620,11 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&p->d_spose, B * sizeof(OrbJoinPose));
         break;
     }
+    case ST_REMAP:
+        add(&p->d_rpose, B * sizeof(OrbRemapPose));
+        add(&p->d_rrow, B * sizeof(OrbRemapRow));
+        add(&p->d_rland, B * cap * sizeof(OrbLandmark));
+        break;
     }
     return l;
 }
@@ -2529,6 +2554,69 @@ int orb_join_segments(OrbProgram* p, OrbJoinSegment* dst, size_t n) {
 
 int orb_join_links(OrbProgram* p, OrbJoinLink* dst, size_t n) {
     return p ? join_copy(p, "join_links", dst, p->d_slink, n, p->join_pairs, sizeof(OrbJoinLink)) : ORB_EINVAL;
+}
+
+int orb_remap_frames(OrbProgram* p, const OrbRemapParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbRemapParams g{};
+    if (params) g = *params;
+    for (uint32_t w : g.reserved)
+        if (w) return fail(p, ORB_EINVAL, "remap_frames: reserved words must be 0");
+    if (g.flags & ~(ORB_REMAP_GRAPH | ORB_REMAP_JOIN)) return fail(p, ORB_EINVAL, "remap_frames: flags ORB_REMAP_GRAPH, ORB_REMAP_JOIN or 0");
+    const uint32_t sources = g.flags ? g.flags : (ORB_REMAP_GRAPH | ORB_REMAP_JOIN);
+    const bool graph = sources & ORB_REMAP_GRAPH, join = sources & ORB_REMAP_JOIN;
+    // RM-1: the part of the stage's row that the flags name
+    const uint32_t reads = 1u << ST_TRAJ | 1u << ST_LANDMARK | (graph ? 1u << ST_GRAPH : 0u) | (join ? 1u << ST_JOIN : 0u);
+    if (int rc = stages_fresh(p, ST_REMAP, reads)) return rc;
+    const Stage* const st = p->stage;
+    const uint32_t F = st[ST_TRAJ].extent;
+    if ((graph && st[ST_GRAPH].extent != F) || (join && st[ST_JOIN].extent != F))
+        return fail(p, ORB_ESTATE, "remap_frames: a source covered another number of frames than the last trajectory call's %u", F);
+    const uint32_t pairs = std::min(st[ST_LANDMARK].extent, F - 1u);  // P_l
+    const size_t cap = p->cfg.max_features;
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_REMAP, stream, reads, &s)) return rc;
+    if (!p->remap_slots) {
+        const char* const e = getenv("TINYORB_REMAP_SLOTS");
+        p->remap_slots = e && atoi(e) == 1 ? 1 : 2;  // two measured faster
+    }
+    RmArgs a{};
+    a.frames = p->d_jframe;
+    a.gposes = graph ? p->d_gpose : nullptr;
+    a.segs = join ? p->d_sseg : nullptr;
+    a.lms = p->d_mland;
+    a.lrows = p->d_mrow;
+    a.cap = (uint32_t)cap;
+    a.n_frames = F;
+    a.n_pairs = pairs;
+    a.poses = p->d_rpose;
+    a.rows = p->d_rrow;
+    a.out = p->d_rland;
+    const uint32_t per_wg = kRmThreads * (uint32_t)p->remap_slots;
+    const dim3 grid((unsigned)((cap + per_wg - 1u) / per_wg), pairs);
+    hipLaunchKernelGGL(k_rm_pose, dim3((F + kRmThreads - 1u) / kRmThreads), dim3(kRmThreads), 0, s, a);
+    if (pairs) {
+        if (p->remap_slots == 2)
+            hipLaunchKernelGGL(k_rm_land<2u>, grid, dim3(kRmThreads), 0, s, a);
+        else
+            hipLaunchKernelGGL(k_rm_land<1u>, grid, dim3(kRmThreads), 0, s, a);
+    }
+    if (int rc = stage_end(p, ST_REMAP, s, F)) return rc;  // p->last_stream stays, as after a guided call
+    p->remap_pairs = pairs;
+    return ORB_OK;
+}
+
+int orb_remap_read(OrbProgram* p, uint32_t frame, OrbRemapPose* pose) {
+    if (!p) return ORB_EINVAL;
+    if (p->stage[ST_REMAP].extent && !pose) return fail(p, ORB_EINVAL, "remap_read: pose is NULL");
+    return read_stage(p, ST_REMAP, frame, pose, p->d_rpose, sizeof(OrbRemapPose), nullptr, nullptr, 0, 0);
+}
+
+int orb_remap_landmarks(OrbProgram* p, uint32_t pair, OrbRemapRow* row, OrbLandmark* landmarks, size_t n) {
+    if (!p) return ORB_EINVAL;
+    // the stage's extent is the frames; the pairs it covered are kept beside it
+    if (p->stage[ST_REMAP].extent && pair >= p->remap_pairs) return fail(p, ORB_EINVAL, "remap_landmarks: pair %u of %u", pair, p->remap_pairs);
+    return read_stage(p, ST_REMAP, pair, row, p->d_rrow, sizeof(OrbRemapRow), landmarks, p->d_rland, sizeof(OrbLandmark), n);
 }
 
 int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {

@@ -128,6 +128,12 @@ ORB_JOIN_SEGMENT_NONE, ORB_JOIN_SEGMENT_ROOT, ORB_JOIN_SEGMENT_LINKED = 0, 1, 2
  ORB_JOIN_LINK_NONFINITE, ORB_JOIN_LINK_RATIO_FEW, ORB_JOIN_LINK_RATIO_SPREAD) = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ORB_JOIN_USE_MINIMAL = 1
 ORB_JOIN_NO_LINK = 0xFFFFFFFF
+# corrected poses and landmarks in one root frame (orb_remap_frames): OrbRemapPose (64 B) and its status bits,
+# OrbRemapRow (16 B), the source flags of OrbRemapParams; the landmarks come back as LANDMARK_DTYPE
+REMAP_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4"), ("gain", "<f4"), ("root", "<u4"), ("status", "<u4")])
+REMAP_ROW_DTYPE = np.dtype([("good", "<u4"), ("moved", "<u4"), ("dropped", "<u4"), ("root", "<u4")])
+ORB_REMAP_GRAPH, ORB_REMAP_JOIN = 1, 2
+ORB_REMAP_FROM_GRAPH, ORB_REMAP_MOVED = 1, 2
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -159,6 +165,7 @@ EXPORTS = [
     "orb_loop_pairs", "orb_loop_pairs_read", "orb_debug_loop_buffer",
     "orb_graph_pairs", "orb_graph_read", "orb_graph_edges",
     "orb_join_pairs", "orb_join_read", "orb_join_segments", "orb_join_links", "orb_debug_loop_mask_buffer",
+    "orb_remap_frames", "orb_remap_read", "orb_remap_landmarks",
 ]
 
 
@@ -285,6 +292,14 @@ class _JoinParams(ctypes.Structure):
 
 
 OrbJoinParams = _JoinParams
+
+
+class _RemapParams(ctypes.Structure):
+    """OrbRemapParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7)]
+
+
+OrbRemapParams = _RemapParams
 
 
 class _PlaceParams(ctypes.Structure):
@@ -415,6 +430,9 @@ def load_library(path=None):
     L.orb_join_segments.argtypes = [vp, vp, sz]
     L.orb_join_links.argtypes = [vp, vp, sz]
     L.orb_debug_loop_mask_buffer.argtypes = [vp, ctypes.POINTER(vp)]
+    L.orb_remap_frames.argtypes = [vp, ctypes.POINTER(_RemapParams), vp]
+    L.orb_remap_read.argtypes = [vp, u32, vp]
+    L.orb_remap_landmarks.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -1112,6 +1130,28 @@ class OrbProgram:
         out = np.zeros(n, dtype=JOIN_LINK_DTYPE)
         self._check(self._lib.orb_join_links(self._handle(), _ptr(out) if n else None, n))
         return out
+
+    def remap_frames(self, flags=0, stream=None, reserved=(0, 0, 0, 0, 0, 0, 0)):
+        """The corrected map in one root frame (not in the reference): every frame's camera, the last
+        graph_pairs' where it moved it (ORB_REMAP_GRAPH), composed with its segment's similarity of the last join_pairs
+        (ORB_REMAP_JOIN), and every GOOD landmark of the last landmarks_consecutive carried along with the camera of its first view
+        and through the similarity.  flags 0: both sources.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        prm = _RemapParams(flags, (ctypes.c_uint32 * 7)(*reserved))
+        self._check(self._lib.orb_remap_frames(self._handle(), ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def remap_read(self, frame):
+        """The record of REMAP_POSE_DTYPE of frame `frame` of the last remap_frames -- synchronises."""
+        rec = np.zeros((), dtype=REMAP_POSE_DTYPE)
+        self._check(self._lib.orb_remap_read(self._handle(), frame, _ptr(rec)))
+        return rec
+
+    def remap_landmarks(self, pair, n=None):
+        """(row of REMAP_ROW_DTYPE, LANDMARK_DTYPE[min(n, max_features)]; n None: max_features) of pair `pair` of the last
+        remap_frames, indexed as landmarks_read -- synchronises."""
+        row = np.zeros((), dtype=REMAP_ROW_DTYPE)
+        out = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=LANDMARK_DTYPE)
+        self._check(self._lib.orb_remap_landmarks(self._handle(), pair, _ptr(row), _ptr(out) if len(out) else None, len(out)))
+        return row, out
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
