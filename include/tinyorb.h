@@ -1239,6 +1239,108 @@ int orb_remap_read(OrbProgram *p, uint32_t frame, OrbRemapPose *pose);
  * (the landmarks call's, at most the trajectory call's frames - 1) or landmarks NULL with n > 0. */
 int orb_remap_landmarks(OrbProgram *p, uint32_t pair, OrbRemapRow *row, OrbLandmark *landmarks, size_t n);
 
+/* ---- a keyframe store that outlives a batch (NOT in the reference; definition KF-1..KF-5 in DESIGN.md section 32) ----
+ * Every stage above works on the last batch, and a database hit of orb_place_frames (ORB_PLACE_DB | e) names a frame whose
+ * keypoints, descriptors and landmarks left the device with its batch.  A program may keep `slots` keyframes on the device: a
+ * slot is a header, max_features CornerData, max_features CornerDescriptor and max_features OrbMapPoint.  orb_keyframes_insert
+ * fills slots from frames of the last batch, orb_match_keyframes matches frames of the last batch against slots and
+ * orb_localize_keyframes gives the query camera from the slot's points, as orb_match_pairs and orb_loop_pairs do inside one
+ * batch: for a frame T inserted into slot s, an entry (q, s) gives the bytes the entry (q, T) gives there.  The store survives
+ * orb_extract_batch_*, orb_batch_select_output and every stage call; only the calls of this section write it, and they write no
+ * other stage's buffer.  Binary32 arithmetic in a fixed order, no fused operations: a CPU restatement gives the same bits. */
+#define ORB_KEYFRAME_SLOTS_MAX 1024u     /* = ORB_PLACE_DB_MAX: database row e of orb_place_frames can be slot e */
+#define ORB_KEYFRAME_NONE 0xffffffffu    /* OrbMapPoint::key of a keypoint without a landmark; OrbKeyframe::origin of a NOMAP keyframe */
+#define ORB_KEYFRAME_EMPTY 0u            /* OrbKeyframe::status: the slot holds nothing (every byte of it is 0) */
+#define ORB_KEYFRAME_STORED 1u           /* a camera and points in its frame */
+#define ORB_KEYFRAME_NOMAP 2u            /* keypoints and descriptors only: the frame lay outside the map, or its pose was not finite */
+typedef struct {
+    float x, y, z;          /* the landmark in the keyframe camera's frame, in the unit of its segment (0 without one) */
+    uint32_t key;           /* pair * max_features + slot of the landmark in the landmarks call it came from (LC-2's owner key);
+                             * ORB_KEYFRAME_NONE: the keypoint views no landmark */
+} OrbMapPoint;              /* 16 bytes */
+typedef struct {
+    float r[9];             /* row-major R, X_kf = R X_origin + t: the keyframe camera in its segment's frame (the identity when the
+                             * frame is its own origin), as OrbFramePose */
+    float t[3];             /* in units of that segment */
+    float scale;            /* OrbFramePose::scale of the source frame */
+    uint32_t keypoints;     /* records of the slot: min(the frame's counter, max_features) */
+    uint32_t points;        /* of them: with a key that is not ORB_KEYFRAME_NONE */
+    uint32_t frame;         /* the source frame in its batch */
+    uint32_t origin;        /* OrbFramePose::origin of the source frame; ORB_KEYFRAME_NONE for NOMAP */
+    uint32_t user[2];       /* the caller's, carried and never read */
+    uint32_t status;        /* ORB_KEYFRAME_*; NOMAP: r, t, scale 0 and every point (0, 0, 0, NONE) */
+    uint32_t reserved[4];   /* 0 */
+} OrbKeyframe;              /* 96 bytes */
+typedef struct { uint32_t frame, slot, user[2]; } OrbKeyframeEntry; /* 16 bytes */
+typedef struct { uint32_t query, slot; } OrbKeyframePair;           /* 8 bytes */
+typedef struct {            /* OrbLoopFix word for word, with the slot where the query's origin is there */
+    float r[9];             /* row-major R, X_q = R X_kf + t */
+    float t[3];             /* in units of the keyframe's segment */
+    float step;             /* |t| */
+    float pose_r[9];        /* row-major R, X_q = R X_origin + t: camera q in the frame of `origin`; 0 when an entry is not finite */
+    float pose_t[3];        /* in units of that segment */
+    uint32_t origin;        /* OrbKeyframe::origin of the slot */
+    uint32_t slot;          /* the entry's slot */
+    uint32_t candidates;    /* 3D-2D correspondences */
+    uint32_t inliers;       /* of them: within max_reproj_px under the model written */
+    uint32_t hypothesis;    /* the winning sample */
+    uint32_t status;        /* ORB_LOCALIZE_*; NOMAP: a NOMAP keyframe.  NOMAP, FEW and DEGENERATE: every other word 0 */
+    uint32_t reserved[1];   /* 0 */
+} OrbKeyframeFix;           /* 128 bytes */
+
+/* Allocates the store, all or none: slots x (96 + 64 max_features) bytes, and (max_batch + slots) x 32 max_features bytes for the
+ * descriptors of a batch in front of the slots' (the matchers address both through one base).  ORB_EINVAL for a NULL program or
+ * slots outside 1 .. ORB_KEYFRAME_SLOTS_MAX; a repeat with the same number does nothing, with another number it is ORB_ESTATE.
+ * Every slot starts EMPTY.  Synchronises. */
+int orb_keyframes_reserve(OrbProgram *p, uint32_t slots);
+/* Fills slot list[i].slot from frame list[i].frame of the last batch, a filled slot included: the first min(counter,
+ * max_features) corners and descriptors byte for byte, the camera of the frame in its segment as orb_loop_pairs takes a target's
+ * (LC-3), and for every keypoint the landmark that owns it (LC-2, on the last orb_landmarks_consecutive) under that camera --
+ * exactly the point orb_loop_pairs would localise against.  A frame outside the landmarks call's frames, or with a pose that is
+ * not finite, is stored NOMAP.  The rest of the slot is 0.  ORB_EINVAL for a NULL program; ORB_ESTATE before
+ * orb_keyframes_reserve or a batch; ORB_EINVAL for a NULL list, n outside 1 .. max_batch, a frame at or above the last batch's
+ * frames, a slot at or above the store's, or two entries naming one slot (the message names the first); then ORB_ESTATE unless
+ * the last orb_match_consecutive, orb_trajectory_consecutive and orb_landmarks_consecutive are all of the current batch and
+ * output set; then ORB_EINVAL when the landmarks call's frames * max_features reach 2^32 - 1.  Asynchronous on `stream` (NULL:
+ * as orb_match_guided chooses; the call does not change it), ordered behind those three stages, its own last call and the
+ * keyframe calls that read the store when they ran on another stream.  The list is copied through a pinned buffer: it is the
+ * caller's again when the call returns. */
+int orb_keyframes_insert(OrbProgram *p, const OrbKeyframeEntry *list, uint32_t n, void *stream);
+/* Copy the header of `slot` (may be NULL) and the first n records of each array that is not NULL to the host (synchronises; n
+ * is clipped to max_features).  An EMPTY slot reads as zeros.  ORB_EINVAL for a NULL program, ORB_ESTATE before
+ * orb_keyframes_reserve, ORB_EINVAL for a slot at or above the store's. */
+int orb_keyframes_read(OrbProgram *p, uint32_t slot, OrbKeyframe *header, CornerData *corners, CornerDescriptor *descriptors,
+                       OrbMapPoint *points, size_t n);
+/* Writes `slot` from the host: what orb_keyframes_read gave, in this program or another of the same configuration, behaves the
+ * same byte for byte.  The records past n become 0.  ORB_EINVAL for a NULL program, ORB_ESTATE before orb_keyframes_reserve;
+ * ORB_EINVAL for a slot at or above the store's, a NULL header, n != header->keypoints or above max_features, a NULL array with
+ * n > 0, a status that is neither STORED nor NOMAP, a reserved word that is not 0, or header->points other than the keys among
+ * the n points that are not ORB_KEYFRAME_NONE.  Synchronises (it waits for the keyframe calls in flight). */
+int orb_keyframes_load(OrbProgram *p, uint32_t slot, const OrbKeyframe *header, const CornerData *corners,
+                       const CornerDescriptor *descriptors, const OrbMapPoint *points, size_t n);
+/* Empties `slot` (every byte 0).  Errors as orb_keyframes_read; synchronises as orb_keyframes_load. */
+int orb_keyframes_remove(OrbProgram *p, uint32_t slot);
+/* Row i of the result holds orb_match_pairs' record (MP-2) for every stored keypoint of frame list[i].query of the last batch
+ * against the `keypoints` records of slot list[i].slot.  Duplicates are allowed.  The call needs a batch and a store, no stage.
+ * ORB_EINVAL for a NULL program; ORB_ESTATE before orb_keyframes_reserve or a batch; ORB_EINVAL for a NULL list, n outside
+ * 1 .. ORB_PAIRS_PER_FRAME * max_batch, a query at or above the last batch's frames, a slot at or above the store's or an EMPTY
+ * slot (the message names the first entry).  The matcher is chosen as orb_match_pairs chooses it; on the matrix cores the store
+ * keeps 128 bytes per record for the descriptors as fp4 (allocated by the first call, refreshed when the store has changed).
+ * Asynchronous on `stream` as orb_match_pairs, ordered behind the store's last insert and its own last call on another stream. */
+int orb_match_keyframes(OrbProgram *p, const OrbKeyframePair *list, uint32_t n, void *stream);
+/* As orb_match_pairs_read, for row `entry` of the last orb_match_keyframes call. */
+int orb_match_keyframes_read(OrbProgram *p, uint32_t entry, OrbMatch *dst, size_t n);
+/* Fixes of entries 0 .. n - 1 of the last orb_match_keyframes call: orb_loop_pairs' candidates, RANSAC, refit and compose (the
+ * same draw stream, the list index as the pair) with the slot's `keypoints`, keys and points where that call takes the target
+ * frame's counter, owners and landmarks under camera T.  params as orb_loop_pairs checks them, with the same errors; then
+ * ORB_ESTATE unless the last orb_match_keyframes is of the current batch and output set and no orb_keyframes_reserve, _insert,
+ * _load or _remove came after it; then ORB_EINVAL for n outside 1 .. the entries it matched.  Asynchronous on `stream` as
+ * orb_loop_pairs.  Result buffers of its own (allocated by the first call, the size of orb_loop_pairs').  (Declared `extern`, as
+ * its read call: the two are no part of the orb_localize_consecutive family, which is listed by its prefix.) */
+extern int orb_localize_keyframes(OrbProgram *p, uint32_t n, const OrbLoopParams *params, void *stream);
+/* As orb_loop_pairs_read, for entry `entry` of the last orb_localize_keyframes call. */
+extern int orb_localize_keyframes_read(OrbProgram *p, uint32_t entry, OrbKeyframeFix *fix, uint8_t *inliers, size_t n);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

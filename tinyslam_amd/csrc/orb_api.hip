@@ -42,6 +42,7 @@
 #include "orb_kernels_graph.h"
 #include "orb_kernels_join.h"
 #include "orb_kernels_remap.h"
+#include "orb_kernels_keyframes.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -77,7 +78,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_JOIN, ST_REMAP, ST_PLACE, ST_PAIRS, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_JOIN, ST_REMAP, ST_PLACE, ST_PAIRS, ST_KEYFRAMES, ST_KF_MATCH, ST_KF_LOC, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -139,6 +140,15 @@ constexpr StageInfo kStages[ST_COUNT] = {
     {"place_frames", "place_read",
      1u << ST_TRACK},     // d_tframe: the keyframe column (ORB_PLACE_KEYFRAMES)
     {"match_pairs", "match_pairs_read", 0u},
+    {"keyframes_insert", "keyframes_read",  // the store: it outlives the batch (kOutlivesBatch)
+     1u << ST_MATCH |     // d_matches: the views of a landmark
+     1u << ST_TRAJ |      // d_jframe
+     1u << ST_LANDMARK},  // d_mland
+    {"match_keyframes", "match_keyframes_read",
+     1u << ST_KEYFRAMES}, // d_kcounts, d_kdesc: the slots' rows
+    {"localize_keyframes", "localize_keyframes_read",
+     1u << ST_KF_MATCH |  // d_kmlist, d_kmrows: the list and its rows
+     1u << ST_KEYFRAMES}, // d_khead, d_kpoints
     {"verify_pairs", "verify_pairs_read",
      1u << ST_PAIRS},     // d_plist, d_prows: the list and its rows
     {"loop_pairs", "loop_pairs_read",
@@ -161,6 +171,9 @@ constexpr ReadersOf readers_of() {
     return r;
 }
 constexpr ReadersOf kReaders = readers_of();
+// The stages whose results do not go stale with the batch: a reader is ordered behind them like behind any other, but asks for the
+// store generation it matched against (OrbProgram::kf_gen) where stages_fresh asks for the current batch and output set.
+constexpr uint32_t kOutlivesBatch = 1u << ST_KEYFRAMES;
 
 // What the stages' kernels write as words and the reads hand out as structs of tinyorb.h; the parameter blocks
 static_assert(sizeof(OrbMatch) == sizeof(MatchRecord), "OrbMatch layout");
@@ -182,6 +195,12 @@ static_assert(sizeof(OrbFramePair) == 8 && offsetof(OrbFramePair, target) == 4, 
 static_assert(sizeof(OrbLoopFix) == kLcFixWords * sizeof(uint32_t) && sizeof(OrbLoopParams) == 64 && offsetof(OrbLoopFix, pose_r) == 13 * sizeof(uint32_t) &&
                   offsetof(OrbLoopFix, origin) == 25 * sizeof(uint32_t) && kLcFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) && sizeof(OrbFramePair) == sizeof(uint2),
               "loop layouts");
+static_assert(sizeof(OrbKeyframe) == kKfHeadWords * sizeof(uint32_t) && offsetof(OrbKeyframe, keypoints) == 13 * sizeof(uint32_t) &&
+                  offsetof(OrbKeyframe, status) == 19 * sizeof(uint32_t) && sizeof(OrbMapPoint) == sizeof(float4) && sizeof(OrbKeyframeEntry) == sizeof(uint4) &&
+                  sizeof(OrbKeyframePair) == sizeof(uint2) && sizeof(OrbKeyframeFix) == sizeof(OrbLoopFix) &&
+                  offsetof(OrbKeyframeFix, slot) == offsetof(OrbLoopFix, query_origin) && ORB_KEYFRAME_STORED == kKfStored && ORB_KEYFRAME_NOMAP == kKfNomap &&
+                  ORB_KEYFRAME_NONE == kLcNone && ORB_KEYFRAME_SLOTS_MAX == ORB_PLACE_DB_MAX,
+              "keyframe layouts");
 static_assert(sizeof(OrbGraphPose) == kPgPoseWords * sizeof(uint32_t) && sizeof(OrbGraphEdge) == kPgEdgeWords * sizeof(uint32_t) && sizeof(OrbGraphParams) == 32 &&
                   offsetof(OrbGraphPose, status) == 15 * sizeof(uint32_t) && kPgFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) &&
                   kPgFixWords * sizeof(uint32_t) == sizeof(OrbLoopFix) && offsetof(OrbLoopFix, status) == 30 * sizeof(uint32_t),
@@ -328,6 +347,27 @@ struct OrbProgram {
     // orb_loop_pairs (orb_kernels_loop.h): fix is [P][32] OrbLoopFix, a row is a list entry, cand the candidate of each slot of its query frame
     PnpState loop;
     uint32_t* d_lowner = nullptr;         // [max_batch][max_features] the owner of every keypoint slot
+    // the keyframe store (orb_kernels_keyframes.h); S = kf_slots, the matchers' rows are the batch's max_batch followed by the S slots'
+    uint32_t kf_slots = 0;                // of orb_keyframes_reserve (0: none)
+    uint64_t kf_gen = 0;                  // store generation: bumped by reserve, insert, load and remove
+    uint64_t kf_match_gen = 0;            // the generation the last orb_match_keyframes read
+    uint64_t kf_desc4_gen = 0;            // the generation the slots' rows of d_kdesc4 were expanded at (0: never)
+    std::vector<uint8_t> kf_filled;       // [S] host mirror: the slot is not EMPTY
+    uint32_t* d_khead = nullptr;          // [S] OrbKeyframe
+    CornerData* d_kcorners = nullptr;     // [S][max_features]
+    CornerDescriptor* d_kdesc = nullptr;  // [max_batch + S][max_features]: rows below max_batch are orb_match_keyframes' copy of the batch's
+    uint32_t* d_kcounts = nullptr;        // [max_batch + S] the matchers' counters of those rows
+    float4* d_kpoints = nullptr;          // [S][max_features] OrbMapPoint
+    uint8_t* d_kdesc4 = nullptr;          // [max_batch + S][max_features][128] the same rows as +-1 in fp4 (orb_match_keyframes, softly)
+    uint32_t* d_kowner = nullptr;         // [max_batch][max_features] orb_keyframes_insert's owners (LC-2)
+    OrbKeyframeEntry* d_klist = nullptr;  // [max_batch] the list of the last insert
+    OrbKeyframeEntry* h_klist = nullptr;  // pinned staging of the same
+    // orb_match_keyframes
+    OrbKeyframePair* d_kmlist = nullptr;  // [P] the list of the last call
+    OrbKeyframePair* h_kmlist = nullptr;  // pinned staging of the same
+    MatchRecord* d_kmrows = nullptr;      // [P][max_features] row i: the queries of entry i's query frame
+    // orb_localize_keyframes: fix is [P][32] OrbKeyframeFix, as `loop`
+    PnpState kfloc;
     // orb_graph_pairs (orb_kernels_graph.h)
     uint32_t* d_gpose = nullptr;          // [max_batch][16] OrbGraphPose; the poses of before a round during a call
     uint32_t* d_gedge = nullptr;          // [P][4] OrbGraphEdge
@@ -601,6 +641,39 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&p->d_lowner, B * cap * sizeof(uint32_t));
         break;
     }
+    case ST_KEYFRAMES: {  // allocated by orb_keyframes_reserve (d_kdesc4 by orb_match_keyframes, for the fp4 matcher only, and softly)
+        const size_t S = p->kf_slots;
+        add(&p->d_khead, S * sizeof(OrbKeyframe));
+        add(&p->d_kcorners, S * cap * sizeof(CornerData));
+        add(&p->d_kdesc, (B + S) * cap * sizeof(CornerDescriptor));
+        add(&p->d_kcounts, (B + S) * sizeof(uint32_t));
+        add(&p->d_kpoints, S * cap * sizeof(OrbMapPoint));
+        add(&p->d_kowner, B * cap * sizeof(uint32_t));
+        add(&p->d_klist, B * sizeof(OrbKeyframeEntry));
+        add(&p->h_klist, B * sizeof(OrbKeyframeEntry), true);
+        add(&p->d_kdesc4, (B + S) * cap * 128u);
+        l.b[l.n - 1].soft = true;
+        break;
+    }
+    case ST_KF_MATCH: {
+        const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
+        add(&p->d_kmlist, P * sizeof(OrbKeyframePair));
+        add(&p->h_kmlist, P * sizeof(OrbKeyframePair), true);
+        add(&p->d_kmrows, P * cap * sizeof(MatchRecord));
+        break;
+    }
+    case ST_KF_LOC: {
+        const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
+        PnpState& l = p->kfloc;
+        add(&l.fix, P * sizeof(OrbKeyframeFix));
+        add(&l.reca, P * cap * sizeof(float4));
+        add(&l.recb, P * cap * sizeof(float4));
+        add(&l.cand, P * cap * sizeof(uint32_t));
+        add(&l.n, P * sizeof(uint32_t));
+        add(&l.keys, P * kVerifyMaxHyp * sizeof(unsigned long long));
+        add(&l.mask, P * cap);
+        break;
+    }
     case ST_GRAPH: {
         const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
         add(&p->d_gpose, B * sizeof(OrbGraphPose));
@@ -657,6 +730,7 @@ bool stage_fresh(const OrbProgram* p, const Stage& st) { return st.extent && st.
 
 // The same of every stage in `need` (bits 1 << StageId), for a call of stage `which`: ORB_OK, or ORB_ESTATE with their names
 int stages_fresh(OrbProgram* p, int which, uint32_t need) {
+    need &= ~kOutlivesBatch;  // the store is never "of the current batch": its reader checks the generation instead
     uint32_t stale = 0;
     for (int i = 0; i < ST_COUNT; i++)
         if ((need >> i & 1u) && !stage_fresh(p, p->stage[i])) stale |= 1u << i;
@@ -2389,6 +2463,245 @@ int orb_loop_pairs(OrbProgram* p, uint32_t n_pairs, const OrbLoopParams* params,
 
 int orb_loop_pairs_read(OrbProgram* p, uint32_t pair, OrbLoopFix* fix, uint8_t* inliers, size_t n) {
     return p ? read_stage(p, ST_LOOP, pair, fix, p->loop.fix, sizeof(OrbLoopFix), inliers, p->loop.mask, 1, n) : ORB_EINVAL;
+}
+
+// ---- the keyframe store ----
+
+// A host-side access to the store (read, load, remove): the device, the store itself, the slot, and every keyframe call in flight done
+static int keyframes_host_access(OrbProgram* p, const char* who, uint32_t slot) {
+    if (!p->kf_slots) return fail(p, ORB_ESTATE, "%s before orb_keyframes_reserve", who);
+    if (slot >= p->kf_slots) return fail(p, ORB_EINVAL, "%s: slot %u of %u", who, slot, p->kf_slots);
+    HIP_TRY(p, hipSetDevice(p->device));
+    for (int st : {ST_KEYFRAMES, ST_KF_MATCH, ST_KF_LOC})
+        if (p->stage[st].stream) HIP_TRY(p, hipEventSynchronize(p->stage[st].done));
+    return ORB_OK;
+}
+
+// Every byte of `slot` to 0 on the program's stream (the caller synchronises it)
+static int keyframes_clear_slot(OrbProgram* p, uint32_t slot) {
+    const size_t cap = p->cfg.max_features, B = p->plan.max_batch;
+    HIP_TRY(p, hipMemsetAsync(p->d_khead + (size_t)slot * kKfHeadWords, 0, sizeof(OrbKeyframe), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_kcorners + (size_t)slot * cap, 0, cap * sizeof(CornerData), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_kdesc + (B + slot) * cap, 0, cap * sizeof(CornerDescriptor), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_kpoints + (size_t)slot * cap, 0, cap * sizeof(OrbMapPoint), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_kcounts + B + slot, 0, sizeof(uint32_t), p->stream));
+    return ORB_OK;
+}
+
+int orb_keyframes_reserve(OrbProgram* p, uint32_t slots) {
+    if (!p) return ORB_EINVAL;
+    if (slots < 1u || slots > ORB_KEYFRAME_SLOTS_MAX) return fail(p, ORB_EINVAL, "keyframes_reserve: need 1..%u slots", ORB_KEYFRAME_SLOTS_MAX);
+    if (p->kf_slots) return p->kf_slots == slots ? ORB_OK : fail(p, ORB_ESTATE, "keyframes_reserve: the store has %u slots", p->kf_slots);
+    HIP_TRY(p, hipSetDevice(p->device));
+    p->kf_slots = slots;
+    if (int rc = alloc_all_or_none(p, ST_KEYFRAMES, "keyframes_reserve")) {
+        p->kf_slots = 0;
+        return rc;
+    }
+    // Every slot EMPTY.  A failure here leaves no store behind: the buffers are freed and the next call reserves again.
+    const StageBufs l = stage_buffers(p, ST_KEYFRAMES);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < l.n && e == hipSuccess; i++)
+        if (!l.b[i].pinned && !l.b[i].soft) e = hipMemsetAsync(*l.b[i].slot, 0, l.b[i].bytes, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) {
+        free_stage_buffers(p, ST_KEYFRAMES);
+        p->kf_slots = 0;
+        return fail(p, ORB_EHIP, "keyframes_reserve: clearing the store failed: %s", hipGetErrorString(e));
+    }
+    p->kf_filled.assign(slots, 0);
+    p->kf_gen++;
+    return ORB_OK;
+}
+
+int orb_keyframes_insert(OrbProgram* p, const OrbKeyframeEntry* list, uint32_t n, void* stream) {
+    if (!p) return ORB_EINVAL;
+    if (!p->kf_slots) return fail(p, ORB_ESTATE, "keyframes_insert before orb_keyframes_reserve");
+    if (!p->last_batch) return fail(p, ORB_ESTATE, "keyframes_insert before a batch");
+    if (!list || n < 1u || n > p->plan.max_batch) return fail(p, ORB_EINVAL, "keyframes_insert: need a list of 1..%u entries", p->plan.max_batch);
+    std::vector<uint8_t> named(p->kf_slots, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        const OrbKeyframeEntry e = list[i];
+        if (e.frame >= p->last_batch || e.slot >= p->kf_slots || named[e.slot])
+            return fail(p, ORB_EINVAL, "keyframes_insert: entry %u is (frame %u, slot %u): a frame below %u and a slot below %u that no earlier entry names are needed", i,
+                        e.frame, e.slot, p->last_batch, p->kf_slots);
+        named[e.slot] = 1;
+    }
+    if (int rc = stages_fresh(p, ST_KEYFRAMES, kStages[ST_KEYFRAMES].reads)) return rc;
+    const Stage* const st = p->stage;
+    // LC-1: L, the frames of the last landmarks call (a later matcher or trajectory call of fewer frames lowers it)
+    const uint32_t n_frames = std::min(st[ST_LANDMARK].extent + 1u, std::min(st[ST_MATCH].extent, st[ST_TRAJ].extent));
+    const size_t cap = p->cfg.max_features, B = p->plan.max_batch;
+    if ((unsigned long long)n_frames * cap >= 0xffffffffull)  // LC-2: a key p * cap + i below the "no owner" word
+        return fail(p, ORB_EINVAL, "keyframes_insert: the landmarks call's frames * max_features must be below 2^32 - 1");
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_KEYFRAMES, stream, kStages[ST_KEYFRAMES].reads, &s)) return rc;
+    // the list through the stage's pinned buffer, once the previous call's copy out of it is done
+    if (p->stage[ST_KEYFRAMES].stream) HIP_TRY(p, hipEventSynchronize(p->stage[ST_KEYFRAMES].done));
+    memcpy(p->h_klist, list, (size_t)n * sizeof(OrbKeyframeEntry));
+    HIP_TRY(p, hipMemcpyAsync(p->d_klist, p->h_klist, (size_t)n * sizeof(OrbKeyframeEntry), hipMemcpyHostToDevice, s));
+    KfInsertArgs a{};
+    a.lc.loc.counts = p->d_counts;
+    a.lc.loc.matches = p->d_matches;
+    a.lc.loc.cap = (uint32_t)cap;
+    a.lc.frames = p->d_jframe;
+    a.lc.lms = p->d_mland;
+    a.lc.n_frames = n_frames;
+    a.lc.traj_frames = st[ST_TRAJ].extent;
+    a.lc.owner = p->d_kowner;
+    a.list = (const uint4*)p->d_klist;
+    a.corners = (const uint4*)p->d_corners;
+    a.desc = (const uint4*)p->d_desc;
+    a.n_entries = n;
+    a.heads = p->d_khead;
+    a.slot_counts = p->d_kcounts + B;
+    a.kcorners = (uint4*)p->d_kcorners;
+    a.kdesc = (uint4*)(p->d_kdesc + B * cap);
+    a.kpoints = p->d_kpoints;
+    HIP_TRY(p, hipMemsetAsync(p->d_kowner, 0xff, (size_t)n_frames * cap * sizeof(uint32_t), s));
+    if (n_frames > 1u)
+        hipLaunchKernelGGL(k_lc_index, dim3(n_frames - 1u, (unsigned)((cap + kLcThreads - 1u) / kLcThreads)), dim3(kLcThreads), 0, s, a.lc);
+    hipLaunchKernelGGL(k_kf_head, dim3((n + kKfThreads - 1u) / kKfThreads), dim3(kKfThreads), 0, s, a);
+    hipLaunchKernelGGL(k_kf_insert, dim3((unsigned)((cap + kKfThreads - 1u) / kKfThreads), n), dim3(kKfThreads), 0, s, a);
+    for (uint32_t i = 0; i < n; i++) p->kf_filled[list[i].slot] = 1;
+    p->kf_gen++;
+    return stage_end(p, ST_KEYFRAMES, s, n);  // p->last_stream stays, as after a guided call
+}
+
+int orb_keyframes_read(OrbProgram* p, uint32_t slot, OrbKeyframe* header, CornerData* corners, CornerDescriptor* descriptors, OrbMapPoint* points,
+                       size_t n) {
+    if (!p) return ORB_EINVAL;
+    if (int rc = keyframes_host_access(p, "keyframes_read", slot)) return rc;
+    const size_t cap = p->cfg.max_features, B = p->plan.max_batch;
+    if (n > cap) n = cap;
+    if (header) HIP_TRY(p, hipMemcpy(header, p->d_khead + (size_t)slot * kKfHeadWords, sizeof(OrbKeyframe), hipMemcpyDeviceToHost));
+    if (corners && n) HIP_TRY(p, hipMemcpy(corners, p->d_kcorners + (size_t)slot * cap, n * sizeof(CornerData), hipMemcpyDeviceToHost));
+    if (descriptors && n) HIP_TRY(p, hipMemcpy(descriptors, p->d_kdesc + (B + slot) * cap, n * sizeof(CornerDescriptor), hipMemcpyDeviceToHost));
+    if (points && n) HIP_TRY(p, hipMemcpy(points, p->d_kpoints + (size_t)slot * cap, n * sizeof(OrbMapPoint), hipMemcpyDeviceToHost));
+    return ORB_OK;
+}
+
+int orb_keyframes_load(OrbProgram* p, uint32_t slot, const OrbKeyframe* header, const CornerData* corners, const CornerDescriptor* descriptors,
+                       const OrbMapPoint* points, size_t n) {
+    if (!p) return ORB_EINVAL;
+    if (int rc = keyframes_host_access(p, "keyframes_load", slot)) return rc;
+    const size_t cap = p->cfg.max_features, B = p->plan.max_batch;
+    if (!header || n != header->keypoints || n > cap || (n && (!corners || !descriptors || !points)))
+        return fail(p, ORB_EINVAL, "keyframes_load: need a header, n == header->keypoints <= %zu and the three arrays", cap);
+    if (header->status != ORB_KEYFRAME_STORED && header->status != ORB_KEYFRAME_NOMAP)
+        return fail(p, ORB_EINVAL, "keyframes_load: status %u is neither STORED nor NOMAP", header->status);
+    for (uint32_t w : header->reserved)
+        if (w) return fail(p, ORB_EINVAL, "keyframes_load: reserved words must be 0");
+    uint32_t keys = 0;
+    for (size_t i = 0; i < n; i++) keys += points[i].key != ORB_KEYFRAME_NONE;
+    if (keys != header->points) return fail(p, ORB_EINVAL, "keyframes_load: header->points is %u, %u of the points have a key", header->points, keys);
+    if (int rc = keyframes_clear_slot(p, slot)) return rc;
+    const uint32_t count = (uint32_t)n;
+    HIP_TRY(p, hipMemcpyAsync(p->d_khead + (size_t)slot * kKfHeadWords, header, sizeof(OrbKeyframe), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->d_kcounts + B + slot, &count, sizeof(uint32_t), hipMemcpyHostToDevice, p->stream));
+    if (n) {
+        HIP_TRY(p, hipMemcpyAsync(p->d_kcorners + (size_t)slot * cap, corners, n * sizeof(CornerData), hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(p, hipMemcpyAsync(p->d_kdesc + (B + slot) * cap, descriptors, n * sizeof(CornerDescriptor), hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(p, hipMemcpyAsync(p->d_kpoints + (size_t)slot * cap, points, n * sizeof(OrbMapPoint), hipMemcpyHostToDevice, p->stream));
+    }
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    p->kf_filled[slot] = 1;
+    p->kf_gen++;
+    return ORB_OK;
+}
+
+int orb_keyframes_remove(OrbProgram* p, uint32_t slot) {
+    if (!p) return ORB_EINVAL;
+    if (int rc = keyframes_host_access(p, "keyframes_remove", slot)) return rc;
+    if (int rc = keyframes_clear_slot(p, slot)) return rc;
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    p->kf_filled[slot] = 0;
+    p->kf_gen++;
+    return ORB_OK;
+}
+
+int orb_match_keyframes(OrbProgram* p, const OrbKeyframePair* list, uint32_t n, void* stream) {
+    if (!p) return ORB_EINVAL;
+    if (!p->kf_slots) return fail(p, ORB_ESTATE, "match_keyframes before orb_keyframes_reserve");
+    if (!p->last_batch) return fail(p, ORB_ESTATE, "match_keyframes before a batch");
+    const size_t cap = p->cfg.max_features, B = p->plan.max_batch, P = (size_t)ORB_PAIRS_PER_FRAME * B;
+    if (!list || n < 1u || n > P) return fail(p, ORB_EINVAL, "match_keyframes: need a list of 1..%zu entries", P);
+    if (cap > (1u << 23)) return fail(p, ORB_EINVAL, "match_keyframes: max_features must be <= 2^23");
+    uint32_t last = 0;  // the largest listed query
+    for (uint32_t i = 0; i < n; i++) {
+        const OrbKeyframePair e = list[i];
+        if (e.query >= p->last_batch || e.slot >= p->kf_slots)
+            return fail(p, ORB_EINVAL, "match_keyframes: entry %u is (%u, %u): a frame below %u and a slot below %u are needed", i, e.query, e.slot, p->last_batch,
+                        p->kf_slots);
+        if (!p->kf_filled[e.slot]) return fail(p, ORB_EINVAL, "match_keyframes: entry %u names slot %u, which is empty", i, e.slot);
+        last = std::max(last, e.query);
+    }
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_KF_MATCH, stream, kStages[ST_KF_MATCH].reads, &s)) return rc;
+    // The matrix-core matcher as orb_match_pairs chooses it: the rows as fp4, 128 bytes per record, in a buffer of the store's
+    bool mfma = match_form(p) != 1 && cap <= (size_t)kMatch4MaxCap;
+    if (mfma && !p->d_kdesc4 && hipMalloc(&p->d_kdesc4, (B + p->kf_slots) * cap * 128u) != hipSuccess) {
+        (void)hipGetLastError();
+        p->d_kdesc4 = nullptr;
+        mfma = false;
+    }
+    if (p->stage[ST_KF_MATCH].stream) HIP_TRY(p, hipEventSynchronize(p->stage[ST_KF_MATCH].done));
+    memcpy(p->h_kmlist, list, (size_t)n * sizeof(OrbKeyframePair));
+    HIP_TRY(p, hipMemcpyAsync(p->d_kmlist, p->h_kmlist, (size_t)n * sizeof(OrbKeyframePair), hipMemcpyHostToDevice, s));
+    // KF-3: the batch's rows in front of the slots'
+    HIP_TRY(p, hipMemcpyAsync(p->d_kcounts, p->d_counts, (size_t)(last + 1u) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    const unsigned gx = (unsigned)((cap + 31u) / 32u);
+    if (mfma) {
+        hipLaunchKernelGGL(k_desc_expand4, dim3(gx, last + 1u), dim3(256), 0, s, p->d_counts, p->d_desc, (uint32_t)cap, p->d_kdesc4);
+        if (p->kf_desc4_gen != p->kf_gen) {  // the slots' rows, once per state of the store
+            hipLaunchKernelGGL(k_desc_expand4, dim3(gx, p->kf_slots), dim3(256), 0, s, p->d_kcounts + B, p->d_kdesc + B * cap, (uint32_t)cap,
+                               p->d_kdesc4 + B * cap * 128u);
+            p->kf_desc4_gen = p->kf_gen;
+        }
+        hipLaunchKernelGGL(k_match_kf_fp4, dim3(n, (unsigned)((cap + kMatchQueriesPerWg - 1u) / kMatchQueriesPerWg)), dim3(64 * kMatchWaves), 0, s,
+                           (const uint2*)p->d_kmlist, (uint32_t)B, p->d_kcounts, p->d_kdesc4, (uint32_t)cap, p->d_kmrows);
+    } else {
+        HIP_TRY(p, hipMemcpyAsync(p->d_kdesc, p->d_desc, (size_t)(last + 1u) * cap * sizeof(CornerDescriptor), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_match_kf, dim3(n, (unsigned)((cap + 64u * kMatchQ - 1u) / (64u * kMatchQ))), dim3(64), 0, s, (const uint2*)p->d_kmlist,
+                           (uint32_t)B, p->d_kcounts, p->d_kdesc, (uint32_t)cap, p->d_kmrows);
+    }
+    p->kf_match_gen = p->kf_gen;
+    return stage_end(p, ST_KF_MATCH, s, n);  // p->last_stream stays, as after a guided call
+}
+
+int orb_match_keyframes_read(OrbProgram* p, uint32_t entry, OrbMatch* dst, size_t n) {
+    return p ? read_stage(p, ST_KF_MATCH, entry, nullptr, nullptr, 0, dst, p->d_kmrows, sizeof(OrbMatch), n) : ORB_EINVAL;
+}
+
+int orb_localize_keyframes(OrbProgram* p, uint32_t n, const OrbLoopParams* params, void* stream) {
+    if (!p || !params) return p ? fail(p, ORB_EINVAL, "localize_keyframes: params is NULL") : ORB_EINVAL;
+    OrbLoopParams g = *params;
+    for (uint32_t w : g.reserved)  // orb_loop_pairs' checks, through the same two checkers
+        if (w) return fail(p, ORB_EINVAL, "localize_keyframes: reserved words must be 0");
+    if (int rc = check_intrinsics(p, ST_KF_LOC, g.fx, g.fy, g.cx, g.cy)) return rc;
+    if (!(std::isfinite(g.max_reproj_px) && g.max_reproj_px >= 0.0f)) return fail(p, ORB_EINVAL, "localize_keyframes: max_reproj_px must be finite and >= 0");
+    if (int rc = ransac_params(p, ST_KF_LOC, &g.hypotheses, &g.max_distance, &g.ratio)) return rc;
+    if (int rc = stages_fresh(p, ST_KF_LOC, kStages[ST_KF_LOC].reads)) return rc;
+    if (p->kf_match_gen != p->kf_gen) return fail(p, ORB_ESTATE, "localize_keyframes: the store has changed since the last orb_match_keyframes");
+    const Stage* const st = p->stage;
+    if (n < 1u || n > st[ST_KF_MATCH].extent) return fail(p, ORB_EINVAL, "localize_keyframes: need 1..%u entries (the matched ones)", st[ST_KF_MATCH].extent);
+    if (g.max_reproj_px == 0.0f) g.max_reproj_px = 2.0f;
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_KF_LOC, stream, kStages[ST_KF_LOC].reads, &s)) return rc;
+    KfArgs a{};
+    a.loc = loc_args(p, p->kfloc, g, kLcSeedSalt);
+    a.list = (const uint2*)p->d_kmlist;
+    a.rows = p->d_kmrows;
+    a.heads = p->d_khead;
+    a.kpoints = p->d_kpoints;
+    hipLaunchKernelGGL(k_kf_gather, dim3(n), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_loc_score, dim3(n, (g.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a.loc);
+    hipLaunchKernelGGL(k_kf_refine, dim3(n), dim3(256), 0, s, a);
+    return stage_end(p, ST_KF_LOC, s, n);  // p->last_stream stays, as after a guided call
+}
+
+int orb_localize_keyframes_read(OrbProgram* p, uint32_t entry, OrbKeyframeFix* fix, uint8_t* inliers, size_t n) {
+    return p ? read_stage(p, ST_KF_LOC, entry, fix, p->kfloc.fix, sizeof(OrbKeyframeFix), inliers, p->kfloc.mask, 1, n) : ORB_EINVAL;
 }
 
 int orb_debug_loop_buffer(OrbProgram* p, void** fixes) {

@@ -298,16 +298,21 @@ __device__ __forceinline__ uint32_t loc_compact(bool keep, uint32_t base, uint32
     return off + before;
 }
 
-// LO-1: candidate `slot` of row `row`: the landmark X under (R, t) with the word w, the keypoint c in level-0 pixels
-// (orb_corner_level0_xy) and its ray
-__device__ __forceinline__ void loc_candidate(const LocArgs& a, uint32_t row, uint32_t slot, const float4& X, const float R[9], const float t[3],
-                                              const CornerData& c, float w) {
-    float x, y, z;
-    loc_transform(R, t, X.x, X.y, X.z, x, y, z);
+// LO-1: the two records of candidate `slot` of row `row`: the landmark (x, y, z) in the earlier camera's frame with the word w, the
+// keypoint c in level-0 pixels (orb_corner_level0_xy) and its ray
+__device__ __forceinline__ void loc_record(const LocArgs& a, uint32_t row, uint32_t slot, float x, float y, float z, const CornerData& c, float w) {
     const float s = (float)(1u << (c.octave & 31u));
     const float u2 = ((float)c.x + 0.5f) * s - 0.5f, v2 = ((float)c.y + 0.5f) * s - 0.5f;
     a.reca[(size_t)row * a.cap + slot] = make_float4(x, y, z, w);
     a.recb[(size_t)row * a.cap + slot] = make_float4(u2, v2, (u2 - a.cx) / a.fx, (v2 - a.cy) / a.fy);
+}
+
+// LO-1: candidate `slot` of row `row`: the landmark X under (R, t) with the word w, and the keypoint c
+__device__ __forceinline__ void loc_candidate(const LocArgs& a, uint32_t row, uint32_t slot, const float4& X, const float R[9], const float t[3],
+                                              const CornerData& c, float w) {
+    float x, y, z;
+    loc_transform(R, t, X.x, X.y, X.z, x, y, z);
+    loc_record(a, row, slot, x, y, z, c, w);
 }
 
 // grid (pairs), block 256

@@ -134,6 +134,20 @@ REMAP_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "
 REMAP_ROW_DTYPE = np.dtype([("good", "<u4"), ("moved", "<u4"), ("dropped", "<u4"), ("root", "<u4")])
 ORB_REMAP_GRAPH, ORB_REMAP_JOIN = 1, 2
 ORB_REMAP_FROM_GRAPH, ORB_REMAP_MOVED = 1, 2
+# a keyframe store that outlives a batch (orb_keyframes_*, orb_match_keyframes, orb_localize_keyframes):
+# OrbKeyframe (96 B) and its status, OrbMapPoint (16 B), OrbKeyframeEntry (16 B), OrbKeyframePair (8 B), OrbKeyframeFix (128 B:
+# LOOP_FIX_DTYPE with the slot where the query's origin is there)
+KEYFRAME_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4"), ("keypoints", "<u4"), ("points", "<u4"), ("frame", "<u4"),
+                           ("origin", "<u4"), ("user", "<u4", (2,)), ("status", "<u4"), ("reserved", "<u4", (4,))])
+MAP_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("key", "<u4")])
+KEYFRAME_ENTRY_DTYPE = np.dtype([("frame", "<u4"), ("slot", "<u4"), ("user", "<u4", (2,))])
+KEYFRAME_PAIR_DTYPE = np.dtype([("query", "<u4"), ("slot", "<u4")])
+KEYFRAME_FIX_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("step", "<f4"), ("pose_r", "<f4", (9,)), ("pose_t", "<f4", (3,)),
+                               ("origin", "<u4"), ("slot", "<u4"), ("candidates", "<u4"), ("inliers", "<u4"), ("hypothesis", "<u4"),
+                               ("status", "<u4"), ("reserved", "<u4", (1,))])
+ORB_KEYFRAME_SLOTS_MAX = 1024
+ORB_KEYFRAME_NONE = 0xFFFFFFFF
+ORB_KEYFRAME_EMPTY, ORB_KEYFRAME_STORED, ORB_KEYFRAME_NOMAP = 0, 1, 2
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -166,6 +180,8 @@ EXPORTS = [
     "orb_graph_pairs", "orb_graph_read", "orb_graph_edges",
     "orb_join_pairs", "orb_join_read", "orb_join_segments", "orb_join_links", "orb_debug_loop_mask_buffer",
     "orb_remap_frames", "orb_remap_read", "orb_remap_landmarks",
+    "orb_keyframes_reserve", "orb_keyframes_insert", "orb_keyframes_read", "orb_keyframes_load", "orb_keyframes_remove",
+    "orb_match_keyframes", "orb_match_keyframes_read", "orb_localize_keyframes", "orb_localize_keyframes_read",
 ]
 
 
@@ -433,6 +449,15 @@ def load_library(path=None):
     L.orb_remap_frames.argtypes = [vp, ctypes.POINTER(_RemapParams), vp]
     L.orb_remap_read.argtypes = [vp, u32, vp]
     L.orb_remap_landmarks.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_keyframes_reserve.argtypes = [vp, u32]
+    L.orb_keyframes_insert.argtypes = [vp, vp, u32, vp]
+    L.orb_keyframes_read.argtypes = [vp, u32, vp, vp, vp, vp, sz]
+    L.orb_keyframes_load.argtypes = [vp, u32, vp, vp, vp, vp, sz]
+    L.orb_keyframes_remove.argtypes = [vp, u32]
+    L.orb_match_keyframes.argtypes = [vp, vp, u32, vp]
+    L.orb_match_keyframes_read.argtypes = [vp, u32, vp, sz]
+    L.orb_localize_keyframes.argtypes = [vp, u32, ctypes.POINTER(_LoopParams), vp]
+    L.orb_localize_keyframes_read.argtypes = [vp, u32, vp, vp, sz]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -1152,6 +1177,90 @@ class OrbProgram:
         out = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=LANDMARK_DTYPE)
         self._check(self._lib.orb_remap_landmarks(self._handle(), pair, _ptr(row), _ptr(out) if len(out) else None, len(out)))
         return row, out
+
+    def keyframes_reserve(self, slots):
+        """Allocates the program's keyframe store of `slots` slots (1 .. ORB_KEYFRAME_SLOTS_MAX; not in the reference; DESIGN.md
+        section 32, KF-1): it survives every later batch and stage call.  The same number again does nothing; another raises
+        OrbError(ORB_ESTATE)."""
+        self._check(self._lib.orb_keyframes_reserve(self._handle(), slots))
+
+    def keyframes_insert(self, entries, stream=None):
+        """Fills slots from frames of the last batch (KF-2): `entries` is a list of (frame, slot) or (frame, slot, user0, user1)
+        tuples or a KEYFRAME_ENTRY_DTYPE array.  Needs match_consecutive, trajectory_consecutive and landmarks_consecutive of
+        the current batch.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        a = np.asarray(entries)
+        if a.dtype != KEYFRAME_ENTRY_DTYPE:
+            rows = [tuple(int(v) for v in e) for e in entries]
+            a = np.zeros(len(rows), dtype=KEYFRAME_ENTRY_DTYPE)
+            for i, e in enumerate(rows):
+                a[i] = (e[0], e[1], tuple(e[2:4]) if len(e) > 2 else (0, 0))
+        a = np.ascontiguousarray(a.reshape(-1))
+        self._check(self._lib.orb_keyframes_insert(self._handle(), _ptr(a) if len(a) else None, len(a), ctypes.c_void_p(stream) if stream else None))
+
+    def keyframes_read(self, slot, n=None):
+        """(header of KEYFRAME_DTYPE, CORNER_DTYPE[n], DESCRIPTOR_DTYPE[n], MAP_POINT_DTYPE[n]) of `slot`; n None: the header's
+        keypoints, else min(n, max_features) -- synchronises.  An EMPTY slot reads as zeros."""
+        head = np.zeros((), dtype=KEYFRAME_DTYPE)
+        self._check(self._lib.orb_keyframes_read(self._handle(), slot, _ptr(head), None, None, None, 0))
+        n = int(head["keypoints"]) if n is None else min(n, self.config.max_features)
+        corners, desc, points = np.zeros(n, dtype=CORNER_DTYPE), np.zeros(n, dtype=DESCRIPTOR_DTYPE), np.zeros(n, dtype=MAP_POINT_DTYPE)
+        if n:
+            self._check(self._lib.orb_keyframes_read(self._handle(), slot, None, _ptr(corners), _ptr(desc), _ptr(points), n))
+        return head, corners, desc, points
+
+    def keyframes_load(self, slot, header, corners, descriptors, points):
+        """Writes `slot` from the host, as keyframes_read gave it in this program or another of the same configuration (KF-5);
+        len(corners) == len(descriptors) == len(points) == header["keypoints"]."""
+        head = np.ascontiguousarray(np.asarray(header, dtype=KEYFRAME_DTYPE).reshape(()))
+        c = np.ascontiguousarray(corners, dtype=CORNER_DTYPE)
+        d = np.ascontiguousarray(descriptors, dtype=DESCRIPTOR_DTYPE)
+        x = np.ascontiguousarray(points, dtype=MAP_POINT_DTYPE)
+        if not len(c) == len(d) == len(x):
+            raise OrbError(ORB_EINVAL, "keyframes_load: the three arrays must have one length")
+        n = len(c)
+        self._check(self._lib.orb_keyframes_load(self._handle(), slot, _ptr(head), _ptr(c) if n else None, _ptr(d) if n else None,
+                                                 _ptr(x) if n else None, n))
+
+    def keyframes_remove(self, slot):
+        """Empties `slot`."""
+        self._check(self._lib.orb_keyframes_remove(self._handle(), slot))
+
+    def match_keyframes(self, pairs, stream=None):
+        """Hamming-match frames of the last batch against slots of the store (KF-3): `pairs` is an (n, 2) integer array, a list
+        of (query, slot) tuples or a KEYFRAME_PAIR_DTYPE array; row i holds match_pairs' record for every stored keypoint of
+        frame query_i against the keypoints of slot_i.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        a = np.asarray(pairs)
+        if a.dtype != KEYFRAME_PAIR_DTYPE:
+            a = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            if len(a) and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise OrbError(ORB_EINVAL, "match_keyframes: indices must be 0 .. 2^32 - 1")
+            a = np.ascontiguousarray(a.astype(np.uint32)).view(KEYFRAME_PAIR_DTYPE).reshape(-1)
+        a = np.ascontiguousarray(a.reshape(-1))
+        self._check(self._lib.orb_match_keyframes(self._handle(), _ptr(a) if len(a) else None, len(a), ctypes.c_void_p(stream) if stream else None))
+
+    def match_keyframes_read(self, entry, n):
+        """MATCH_DTYPE records of the first n queries of entry `entry` of the last match_keyframes -- synchronises."""
+        out = np.zeros(min(n, self.config.max_features), dtype=MATCH_DTYPE)
+        self._check(self._lib.orb_match_keyframes_read(self._handle(), entry, _ptr(out) if len(out) else None, len(out)))
+        return out
+
+    def localize_keyframes(self, n, fx, fy, cx, cy, max_reproj_px=0.0, hypotheses=0, max_distance=0, ratio=0.0, seed=0, stream=None,
+                           reserved=(0,) * 7):
+        """The pose of each listed query frame from its slot's points (KF-4): loop_pairs' RANSAC, refit and compose on entries
+        0 .. n - 1 of the last match_keyframes, with the same parameters and draw stream.  Raises OrbError(ORB_ESTATE) when the
+        store has changed since that call.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        prm = _LoopParams(float(np.float32(fx)), float(np.float32(fy)), float(np.float32(cx)), float(np.float32(cy)),
+                          float(np.float32(max_reproj_px)), hypotheses, max_distance, float(np.float32(ratio)), seed & 0xFFFFFFFF,
+                          (ctypes.c_uint32 * 7)(*reserved))
+        self._check(self._lib.orb_localize_keyframes(self._handle(), n, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def localize_keyframes_read(self, entry, n=None):
+        """(record of KEYFRAME_FIX_DTYPE, uint8[min(n, max_features)]: the inlier bytes of the keypoint slots of entry `entry`'s
+        query frame; n None: max_features) of the last localize_keyframes -- synchronises."""
+        rec = np.zeros((), dtype=KEYFRAME_FIX_DTYPE)
+        mask = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=np.uint8)
+        self._check(self._lib.orb_localize_keyframes_read(self._handle(), entry, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
+        return rec, mask
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
