@@ -44,11 +44,12 @@ def design_rows(rec):
     return np.stack([u2 * u, u2 * v, u2, v2 * u, v2 * v, v2, u, v, np.ones_like(u)], -1).astype(F)
 
 
-def null_vectors(A):
+def null_vectors(A, trace=None):
     """EP-3 on (n, 8, 9) matrices: complete pivoting (the first maximal |a| of the remaining block in row-major order; the row and
     the column are swapped into place), elimination `f = a[q][r] / a[r][r]`, `a[q][c] = a[q][c] - f a[r][c]` for c > r, the one
     unpivoted column set to 1, back substitution `s = s - a[r][q] x[q]` over ascending q starting from s = 0, `x[r] = s / a[r][r]`,
-    the columns put back, and the result divided by its first entry of largest magnitude.  Returns (F (n, 9), m (n,), ok (n,))."""
+    the columns put back, and the result divided by its first entry of largest magnitude.  Returns (F (n, 9), m (n,), ok (n,)).
+    `trace`: a dict that receives `unpivoted` (n,), the original column each matrix left unpivoted."""
     A = np.array(A, dtype=F, copy=True)
     n = len(A)
     rows = np.arange(n)
@@ -87,6 +88,8 @@ def null_vectors(A):
         m = np.argmax(np.abs(Fm), 1)
         Fm = Fm / Fm[rows, m][:, None]
     Fm[~ok] = F(0)
+    if trace is not None:
+        trace.update(unpivoted=perm[:, 8].copy())
     return Fm, m, ok
 
 
@@ -135,18 +138,25 @@ def refit(rec, inl, m):
     return Fr
 
 
-def to_pixels(Fn, cx, cy, k):
-    """EP-6: T^T (F T), every entry (a0 b0 + a1 b1) + a2 b2, divided by its first entry of largest magnitude."""
+def to_pixels(Fn, cx, cy, k, trace=None):
+    """EP-6: T^T (F T), every entry (a0 b0 + a1 b1) + a2 b2, divided by its first entry of largest magnitude (`trace`: a dict that
+    receives its index as `pixel_m`)."""
     T = np.array([[k, 0, -(cx * k), 0, k, -(cy * k), 0, 0, 1]], dtype=F)
     Tt = np.array([[k, 0, 0, 0, k, 0, -(cx * k), -(cy * k), 1]], dtype=F)
     P = vr.mat3(Tt, vr.mat3(Fn[None], T))[0]
     m = int(np.argmax(np.abs(P)))
+    if trace is not None:
+        trace.update(pixel_m=m)
     with np.errstate(all="ignore"):
         return P / P[m]
 
 
-def verify_points(x0, y0, x1, y1, W, H, pair=0, **params):
-    """EP-1..EP-6 on candidate correspondences (level-0 pixel coordinates, float32, in candidate order).
+def verify_points(x0, y0, x1, y1, W, H, pair=0, trace=None, **params):
+    """EP-1..EP-6 on candidate correspondences (level-0 pixel coordinates, float32, in candidate order).  `trace`: a dict that
+    receives, of a pair with eight candidates or more, `sampled` (the hypotheses whose EP-2 draws gave eight distinct indices) and
+    `valid` (those that are not degenerate either, and score a key), and, once one is valid, `m` (the winner's entry of largest
+    magnitude, the one EP-5 fixes), `unpivoted` (the original column EP-3 left unpivoted for the winner), `n_min`, `fit` (whether
+    the solver returned), `n_fit` (the refit's inliers, 0 without a fit) and `pixel_m` (EP-6's normalising index).
     Returns (record of VERIFY_MODEL_DTYPE, per-candidate inlier flags)."""
     p = defaults(**params)
     cx, cy, k = vr.normalise(W, H)
@@ -163,10 +173,13 @@ def verify_points(x0, y0, x1, y1, W, H, pair=0, **params):
         out["status"] = VERIFY_FEW
         return out, mask
     hyps = p["hypotheses"]
-    J, ok = sample(p["seed"], pair, M, hyps)
-    Fs, ms, okm = null_vectors(design_rows(rec[J]))
-    ok = ok & okm
+    J, oks = sample(p["seed"], pair, M, hyps)
+    nt = {}
+    Fs, ms, okm = null_vectors(design_rows(rec[J]), trace=nt)
+    ok = oks & okm
     Fs[~ok] = F(0)
+    if trace is not None:
+        trace.update(sampled=int(oks.sum()), valid=int(ok.sum()))
     if not ok.any():
         out["status"] = VERIFY_DEGENERATE
         return out, mask
@@ -185,7 +198,10 @@ def verify_points(x0, y0, x1, y1, W, H, pair=0, **params):
         inl_r = inliers(Fr, rec, t2)[0]
         keep = 16 * int(inl_r.sum()) >= 15 * n_min
     Fk, mask = (Fr, inl_r) if keep else (Fm, inl_m)
-    out["h"] = to_pixels(Fk, cx, cy, k)
+    if trace is not None:
+        trace.update(m=m, unpivoted=int(nt["unpivoted"][h]), n_min=n_min, fit=Fr is not None,
+                     n_fit=int(inl_r.sum()) if Fr is not None else 0)
+    out["h"] = to_pixels(Fk, cx, cy, k, trace=trace)
     out["inliers"] = int(mask.sum())
     out["hypothesis"] = h
     out["status"] = VERIFY_OK if keep else VERIFY_MINIMAL
@@ -277,14 +293,14 @@ def scene(rng, motion, W=640, H=480, focal=500.0, n=600, outlier_share=0.3, zmin
     return dict(corners=[c0, c1], desc=[d[order0], d1], F=Ft, correct=correct[order0], planted=planted[order0])
 
 
-def verify_pair(q_corners, t_corners, matches, W, H, pair, cap=None, **params):
-    """EP-1..EP-6 for one pair from the stored records of frames f and f + 1 and the matches of frame f's stored queries.
-    Returns (record, inlier bytes of the queries: cap of them when cap is given, else len(matches))."""
+def verify_pair(q_corners, t_corners, matches, W, H, pair, cap=None, trace=None, **params):
+    """EP-1..EP-6 for one pair from the stored records of frames f and f + 1 and the matches of frame f's stored queries (`trace`:
+    as verify_points).  Returns (record, inlier bytes of the queries: cap of them when cap is given, else len(matches))."""
     p = defaults(**params)
     sel = vr.candidates(matches, len(t_corners), p["max_distance"], p["ratio"])
     x0, y0 = vr.level0(q_corners[sel])
     x1, y1 = vr.level0(t_corners[matches["index"][sel].astype(np.int64)])
-    rec, inl = verify_points(x0, y0, x1, y1, W, H, pair=pair, **params)
+    rec, inl = verify_points(x0, y0, x1, y1, W, H, pair=pair, trace=trace, **params)
     mask = np.zeros(len(matches) if cap is None else cap, dtype=np.uint8)
     mask[sel[inl]] = 1
     return rec, mask
