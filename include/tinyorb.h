@@ -1341,6 +1341,114 @@ extern int orb_localize_keyframes(OrbProgram *p, uint32_t n, const OrbLoopParams
 /* As orb_loop_pairs_read, for entry `entry` of the last orb_localize_keyframes call. */
 extern int orb_localize_keyframes_read(OrbProgram *p, uint32_t entry, OrbKeyframeFix *fix, uint8_t *inliers, size_t n);
 
+/* ---- a batch's path and landmarks in the stored map (NOT in the reference; definition AN-1..AN-7 in DESIGN.md section 33) ----
+ * An OrbKeyframeFix is one camera of the batch in the frame and unit of one keyframe's segment; the batch's trajectory and
+ * landmarks stay in the batch's own frames and units.  This stage is orb_join_pairs with a keyframe on the far side: entry
+ * (q, s) of the last orb_localize_keyframes gives camera q in the keyframe's segment (pose_r, pose_t) and, from the trajectory,
+ * in its own segment b = the origin of frame q's record; an inlier keypoint of q whose matched keypoint of the slot carries a
+ * stored point and which a landmark of b owns has a depth in each unit, and the lower median of the ratios is the scale (TJ-3,
+ * TJ-4 on this call's parameters).  Every segment of the batch takes, among its entries that hold, the one with the most
+ * consistent ratios (then the lowest index) and hangs directly under that keyframe's segment -- there is no chain.  Every frame
+ * of an anchored segment is written in the map's frame and unit, and every GOOD landmark of such a segment carried along.
+ * Binary32 arithmetic in a fixed order, no fused operations: a CPU restatement gives the same bits.  Nothing is fed back into
+ * another stage, and neither another stage's results nor the store are written. */
+#define ORB_ANCHOR_USE_MINIMAL 1u       /* flags: a fix of status ORB_LOCALIZE_MINIMAL qualifies too */
+#define ORB_ANCHOR_FREE 0u              /* OrbAnchorPose::status: r, t, scale of the trajectory bit for bit, gain 1, slot 0xffffffff */
+#define ORB_ANCHOR_ANCHORED 1u          /* the frame in the frame and unit of the segment of keyframe `slot` */
+#define ORB_ANCHOR_SEGMENT_NONE 0u      /* the frame slot is no segment's origin */
+#define ORB_ANCHOR_SEGMENT_FREE 1u      /* an origin without a chosen entry */
+#define ORB_ANCHOR_SEGMENT_ANCHORED 2u  /* an origin hung under a keyframe's segment */
+#define ORB_ANCHOR_LINK_HOLDS 0u        /* the entry gives a similarity between its segment and the keyframe's */
+#define ORB_ANCHOR_LINK_STATUS 1u       /* the fix is not OK (nor MINIMAL under ORB_ANCHOR_USE_MINIMAL); a NOMAP keyframe */
+#define ORB_ANCHOR_LINK_FEW 2u          /* inliers < min_inliers */
+#define ORB_ANCHOR_LINK_RANGE 3u        /* q outside the trajectory's or the landmarks' frames, or q without an origin */
+#define ORB_ANCHOR_LINK_NONFINITE 4u    /* an entry of r, t, pose_r, pose_t, of camera q's record or of the similarity is not finite */
+#define ORB_ANCHOR_LINK_RATIO_FEW 5u    /* fewer than min_shared ratios */
+#define ORB_ANCHOR_LINK_RATIO_SPREAD 6u /* fewer than consistent_permille of them within scale_tolerance of their median */
+#define ORB_ANCHOR_NONE 0xffffffffu     /* no slot, no entry, no origin */
+typedef struct {            /* zero-initialised = the defaults; OrbJoinParams' fields */
+    uint32_t min_inliers;   /* a fix qualifies with at least this many inliers (0: 12) */
+    uint32_t min_shared;    /* ratios an entry needs (0: 8) */
+    float scale_tolerance;  /* a ratio is consistent within this share of the median (0: 0.1); finite, >= 0 */
+    uint32_t consistent_permille; /* consistent ratios an entry needs, per thousand (0: 500; <= 1000) */
+    uint32_t flags;         /* ORB_ANCHOR_USE_MINIMAL or 0 */
+    uint32_t reserved[3];   /* must be 0 (ORB_EINVAL otherwise) */
+} OrbAnchorParams;          /* 32 bytes */
+
+typedef struct {
+    float r[9];             /* row-major R, X_f = R X_map + t: the camera in the frame of the keyframe's segment (FREE: of its own) */
+    float t[3];             /* in units of that segment */
+    float scale;            /* gain * the trajectory's scale */
+    float gain;             /* units of the map per unit of the frame's segment; 1 when FREE */
+    uint32_t slot;          /* the keyframe the frame's segment hangs under; ORB_ANCHOR_NONE when FREE */
+    uint32_t status;        /* ORB_ANCHOR_FREE, ORB_ANCHOR_ANCHORED */
+} OrbAnchorPose;            /* 64 bytes */
+
+typedef struct {
+    float r[9];             /* gamma X_b = R X_map + t: the map's coordinates in this origin's frame (the identity unless ANCHORED) */
+    float t[3];
+    float gamma;            /* units of the map per unit of this segment (1 unless ANCHORED) */
+    uint32_t slot;          /* the chosen entry's slot; ORB_ANCHOR_NONE unless ANCHORED, as link, map_origin and map_frame */
+    uint32_t link;          /* the list index of the chosen entry */
+    uint32_t map_origin;    /* OrbKeyframe::origin, frame and user of that slot: which stored map the segment landed in */
+    uint32_t map_frame;
+    uint32_t user[2];       /* 0 unless ANCHORED */
+    uint32_t status;        /* ORB_ANCHOR_SEGMENT_* */
+    uint32_t reserved[4];   /* 0 */
+} OrbAnchorSegment;         /* 96 bytes */
+
+typedef struct {
+    uint32_t verdict;       /* ORB_ANCHOR_LINK_*: the first of AN-3 that applies */
+    uint32_t query_origin;  /* the origin word of frame q's record, as read; 0 when q lies outside the trajectory's frames */
+    uint32_t slot;          /* the entry's slot */
+    uint32_t shared;        /* the entry's ratios; 0 unless HOLDS, RATIO_FEW or RATIO_SPREAD */
+    uint32_t consistent;    /* ... those within scale_tolerance of gamma */
+    float gamma;            /* their lower median: units of the keyframe's segment per unit of `query_origin` */
+    uint32_t chosen;        /* 1: this entry anchors its segment */
+    uint32_t reserved;
+} OrbAnchorLink;            /* 32 bytes */
+
+typedef struct {
+    uint32_t good;          /* records with ORB_POINT_GOOD among the pair's max_features slots */
+    uint32_t moved;         /* of them, those written in the map's frame with finite coordinates */
+    uint32_t dropped;       /* of them, those the step left with a coordinate that is not finite: written with x, y, z, flags 0 */
+    uint32_t origin;        /* the landmark row's origin, as it is */
+    uint32_t slot;          /* the keyframe that origin hangs under, ORB_ANCHOR_NONE when it is not ANCHORED */
+    uint32_t map_origin;    /* OrbKeyframe::origin of that slot, ORB_ANCHOR_NONE likewise */
+    uint32_t reserved[2];   /* 0 */
+} OrbAnchorRow;             /* 32 bytes */
+
+/* Entries 0 .. n - 1 of the last orb_localize_keyframes.  ORB_EINVAL for a NULL program, a scale_tolerance that is not finite
+ * or negative, consistent_permille > 1000, an unknown flag or a reserved word that is not 0 (params NULL: the defaults); then
+ * ORB_ESTATE unless the last orb_match_consecutive, orb_trajectory_consecutive, orb_landmarks_consecutive, orb_match_keyframes
+ * and orb_localize_keyframes are all of the current batch and output set and no orb_keyframes_reserve, _insert, _load or _remove
+ * came after that orb_match_keyframes; then ORB_EINVAL for n outside 1 .. the entries of the last orb_localize_keyframes, or
+ * when the landmarks call's frames * max_features reaches 2^32 - 1.  Asynchronous on `stream` (NULL: as orb_match_guided
+ * chooses; the call does not change it), ordered behind those five stages' last calls, the store's last insert and the last call
+ * of its own when they ran on another stream; they wait for such a call on another stream before they overwrite what it reads,
+ * and orb_keyframes_load and _remove wait for it on the host.  Result buffers of its own (allocated by the first call: about
+ * 36 + 4 ORB_PAIRS_PER_FRAME bytes per keypoint slot of max_batch).  A landmark record keeps its origin word: the row says where
+ * the pair's segment went. */
+int orb_anchor_frames(OrbProgram *p, uint32_t n, const OrbAnchorParams *params, void *stream);
+/* Copy the record of frame `frame` of the last orb_anchor_frames call to the host (synchronises); ORB_ESTATE before any call,
+ * ORB_EINVAL for a frame outside the frames of the trajectory call it read or pose NULL. */
+int orb_anchor_read(OrbProgram *p, uint32_t frame, OrbAnchorPose *pose);
+/* Copy the segment records of frame slots 0 .. n - 1 of the last orb_anchor_frames call (synchronises); ORB_ESTATE before any
+ * call, ORB_EINVAL for n above its frames or dst NULL with n > 0. */
+int orb_anchor_segments(OrbProgram *p, OrbAnchorSegment *dst, size_t n);
+/* Copy the link records of entries 0 .. n - 1 of the last orb_anchor_frames call (synchronises); ORB_ESTATE before any call,
+ * ORB_EINVAL for n above its entries or dst NULL with n > 0. */
+int orb_anchor_links(OrbProgram *p, OrbAnchorLink *dst, size_t n);
+/* Copy the row of pair `pair` of the last orb_anchor_frames call (row may be NULL) and its first n landmark records (indexed as
+ * orb_landmarks_read) to the host (synchronises); ORB_ESTATE before any call, ORB_EINVAL for a pair outside the pairs it covered
+ * (LC-1's frames - 1) or landmarks NULL with n > 0. */
+int orb_anchor_landmarks(OrbProgram *p, uint32_t pair, OrbAnchorRow *row, OrbLandmark *landmarks, size_t n);
+/* For tests: the device addresses of the rows [ORB_PAIRS_PER_FRAME * max_batch][max_features] OrbMatch that orb_match_keyframes
+ * writes, and of the records [ORB_PAIRS_PER_FRAME * max_batch] OrbKeyframeFix and the inlier bytes [ORB_PAIRS_PER_FRAME *
+ * max_batch][max_features] that orb_localize_keyframes writes; orb_anchor_frames reads all three.  Each pointer may be NULL.  The
+ * caller orders its own writes.  ORB_ESTATE until a localize_keyframes call has run. */
+int orb_debug_keyframe_buffers(OrbProgram *p, void **rows, void **fixes, void **mask);
+
 /* Keypoint coordinates are in the octave's own pixel grid (fast.wgsl:143-150).  Centre of that pixel in level-0
  * pixel units, for consumers that work across octaves: a level-m texel covers 2^m level-0
  * pixels (exact halving; for odd sizes the blit's own mapping, blit.wgsl:17-36, differs by less than a pixel). */

@@ -43,6 +43,7 @@
 #include "orb_kernels_join.h"
 #include "orb_kernels_remap.h"
 #include "orb_kernels_keyframes.h"
+#include "orb_kernels_anchor.h"
 #include "orb_kernels_track.h"
 
 using namespace orb;
@@ -78,7 +79,7 @@ struct ProfSpan {
 // the caller passes, so a call is ordered (stage_begin) behind the last call of: the stage itself, whose buffers it overwrites; the
 // stages whose results it reads, a subset of its row of kStages; and the stages that read what it overwrites, kReaders.of[stage],
 // which is that table transposed.
-enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_JOIN, ST_REMAP, ST_PLACE, ST_PAIRS, ST_KEYFRAMES, ST_KF_MATCH, ST_KF_LOC, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
+enum StageId { ST_MATCH = 0, ST_VERIFY, ST_EPI, ST_GUIDE, ST_TRACK, ST_BAND, ST_POSE, ST_TRAJ, ST_LOCALIZE, ST_LANDMARK, ST_BRIDGE, ST_ADJUST, ST_GRAPH, ST_JOIN, ST_REMAP, ST_ANCHOR, ST_PLACE, ST_PAIRS, ST_KEYFRAMES, ST_KF_MATCH, ST_KF_LOC, ST_PAIRS_VERIFY, ST_LOOP, ST_COUNT };
 
 // A stage, said once: what messages call it and its read call, and every stage whose results a call of it may read (bits 1 << StageId)
 struct StageInfo {
@@ -137,6 +138,13 @@ constexpr StageInfo kStages[ST_COUNT] = {
      1u << ST_LANDMARK |  // d_mland, d_mrow: the records it moves
      1u << ST_GRAPH |     // d_gpose (ORB_REMAP_GRAPH)
      1u << ST_JOIN},      // d_sseg (ORB_REMAP_JOIN)
+    {"anchor_frames", "anchor_read",
+     1u << ST_MATCH |     // d_matches: the owners' walk
+     1u << ST_TRAJ |      // d_jframe: the segments and camera q in its own
+     1u << ST_LANDMARK |  // d_mland, d_mrow: the landmark of a ratio, the records it moves
+     1u << ST_KF_MATCH |  // d_kmlist, d_kmrows: q, the slot and the matched keypoint
+     1u << ST_KF_LOC |    // kfloc.fix, kfloc.mask: camera q in the keyframe's segment, the inliers
+     1u << ST_KEYFRAMES}, // d_khead, d_kpoints: the stored points and where the slot came from
     {"place_frames", "place_read",
      1u << ST_TRACK},     // d_tframe: the keyframe column (ORB_PLACE_KEYFRAMES)
     {"match_pairs", "match_pairs_read", 0u},
@@ -219,6 +227,18 @@ static_assert(sizeof(OrbRemapPose) == kRmPoseWords * sizeof(uint32_t) && sizeof(
                   kRmFromGraph == ORB_REMAP_FROM_GRAPH && kRmMoved == ORB_REMAP_MOVED && kRmSegLinked == ORB_JOIN_SEGMENT_LINKED &&
                   kRmGraphRefined == ORB_GRAPH_REFINED && kRmGraphFailed == ORB_GRAPH_FAILED && ORB_GRAPH_STALLED == 3u,
               "remap layouts");
+static_assert(sizeof(OrbAnchorPose) == kAnPoseWords * sizeof(uint32_t) && sizeof(OrbAnchorSegment) == kAnSegWords * sizeof(uint32_t) &&
+                  sizeof(OrbAnchorLink) == kAnLinkWords * sizeof(uint32_t) && sizeof(OrbAnchorRow) == kAnRowWords * sizeof(uint32_t) && sizeof(OrbAnchorParams) == 32 &&
+                  offsetof(OrbAnchorPose, slot) == 14 * sizeof(uint32_t) && offsetof(OrbAnchorSegment, gamma) == 12 * sizeof(uint32_t) &&
+                  offsetof(OrbAnchorSegment, map_origin) == 15 * sizeof(uint32_t) && offsetof(OrbAnchorSegment, status) == 19 * sizeof(uint32_t) &&
+                  offsetof(OrbAnchorLink, gamma) == 5 * sizeof(uint32_t) && offsetof(OrbAnchorRow, origin) == 3 * sizeof(uint32_t) &&
+                  kAnFrameWords * sizeof(uint32_t) == sizeof(OrbFramePose) && kAnFixWords * sizeof(uint32_t) == sizeof(OrbKeyframeFix) &&
+                  kAnLmRowWords * sizeof(uint32_t) == sizeof(OrbLandmarkRow) && offsetof(OrbKeyframeFix, inliers) == 28 * sizeof(uint32_t) &&
+                  offsetof(OrbKeyframeFix, pose_r) == 13 * sizeof(uint32_t) && offsetof(OrbKeyframeFix, status) == 30 * sizeof(uint32_t) &&
+                  offsetof(OrbKeyframe, frame) == 15 * sizeof(uint32_t) && offsetof(OrbKeyframe, user) == 17 * sizeof(uint32_t) &&
+                  kAnSegAnchored == ORB_ANCHOR_SEGMENT_ANCHORED && kAnSegFree == ORB_ANCHOR_SEGMENT_FREE && kAnAnchored == ORB_ANCHOR_ANCHORED &&
+                  kAnRatioSpread == ORB_ANCHOR_LINK_RATIO_SPREAD && kAnNonfinite == ORB_ANCHOR_LINK_NONFINITE && kAnNone == ORB_ANCHOR_NONE,
+              "anchor layouts");
 
 // The last call of a stage
 struct Stage {
@@ -352,6 +372,8 @@ struct OrbProgram {
     uint64_t kf_gen = 0;                  // store generation: bumped by reserve, insert, load and remove
     uint64_t kf_match_gen = 0;            // the generation the last orb_match_keyframes read
     uint64_t kf_desc4_gen = 0;            // the generation the slots' rows of d_kdesc4 were expanded at (0: never)
+    uint64_t kf_match_call = 0;           // orb_match_keyframes calls so far
+    uint64_t kf_loc_call = 0;             // kf_match_call of the rows the last orb_localize_keyframes read
     std::vector<uint8_t> kf_filled;       // [S] host mirror: the slot is not EMPTY
     uint32_t* d_khead = nullptr;          // [S] OrbKeyframe
     CornerData* d_kcorners = nullptr;     // [S][max_features]
@@ -389,6 +411,17 @@ struct OrbProgram {
     float4* d_rland = nullptr;            // [max_batch][max_features][2] OrbLandmark
     uint32_t remap_pairs = 0;             // the pairs of the last call (its Stage's extent is the frames)
     int remap_slots = 0;                  // slots per thread of k_rm_land: two (TINYORB_REMAP_SLOTS=1: one); 0 until the first call
+    // orb_anchor_frames (orb_kernels_anchor.h)
+    uint32_t* d_nowner = nullptr;         // [max_batch][max_features] the owner of every keypoint slot, of this call's landmarks
+    uint32_t* d_nratio = nullptr;         // [P][max_features] the bits of an entry's ratios
+    uint32_t* d_nlink = nullptr;          // [P][8] OrbAnchorLink
+    unsigned long long* d_nkey = nullptr; // [max_batch] the best entry of every segment
+    uint32_t* d_nseg = nullptr;           // [max_batch][24] OrbAnchorSegment
+    uint32_t* d_npose = nullptr;          // [max_batch][16] OrbAnchorPose
+    uint32_t* d_nrow = nullptr;           // [max_batch][8] OrbAnchorRow
+    float4* d_nland = nullptr;            // [max_batch][max_features][2] OrbLandmark
+    uint32_t anchor_entries = 0;          // n of the last call (its Stage's extent is the frames)
+    uint32_t anchor_pairs = 0;            // the pairs of the last call
     // orb_track_consecutive (orb_kernels_track.h)
     uint32_t* d_tkeys = nullptr;          // [max_batch][max_features] link keys (global form of k_track_link)
     uint32_t* d_tprev = nullptr;          // [max_batch][max_features]
@@ -698,6 +731,18 @@ StageBufs stage_buffers(OrbProgram* p, int which) {
         add(&p->d_rrow, B * sizeof(OrbRemapRow));
         add(&p->d_rland, B * cap * sizeof(OrbLandmark));
         break;
+    case ST_ANCHOR: {
+        const size_t P = (size_t)ORB_PAIRS_PER_FRAME * B;
+        add(&p->d_nowner, B * cap * sizeof(uint32_t));
+        add(&p->d_nratio, P * cap * sizeof(uint32_t));
+        add(&p->d_nlink, P * sizeof(OrbAnchorLink));
+        add(&p->d_nkey, B * sizeof(unsigned long long));
+        add(&p->d_nseg, B * sizeof(OrbAnchorSegment));
+        add(&p->d_npose, B * sizeof(OrbAnchorPose));
+        add(&p->d_nrow, B * sizeof(OrbAnchorRow));
+        add(&p->d_nland, B * cap * sizeof(OrbLandmark));
+        break;
+    }
     }
     return l;
 }
@@ -2472,7 +2517,7 @@ static int keyframes_host_access(OrbProgram* p, const char* who, uint32_t slot) 
     if (!p->kf_slots) return fail(p, ORB_ESTATE, "%s before orb_keyframes_reserve", who);
     if (slot >= p->kf_slots) return fail(p, ORB_EINVAL, "%s: slot %u of %u", who, slot, p->kf_slots);
     HIP_TRY(p, hipSetDevice(p->device));
-    for (int st : {ST_KEYFRAMES, ST_KF_MATCH, ST_KF_LOC})
+    for (int st : {ST_KEYFRAMES, ST_KF_MATCH, ST_KF_LOC, ST_ANCHOR})
         if (p->stage[st].stream) HIP_TRY(p, hipEventSynchronize(p->stage[st].done));
     return ORB_OK;
 }
@@ -2666,6 +2711,7 @@ int orb_match_keyframes(OrbProgram* p, const OrbKeyframePair* list, uint32_t n, 
                            (uint32_t)B, p->d_kcounts, p->d_kdesc, (uint32_t)cap, p->d_kmrows);
     }
     p->kf_match_gen = p->kf_gen;
+    p->kf_match_call++;
     return stage_end(p, ST_KF_MATCH, s, n);  // p->last_stream stays, as after a guided call
 }
 
@@ -2697,6 +2743,7 @@ int orb_localize_keyframes(OrbProgram* p, uint32_t n, const OrbLoopParams* param
     hipLaunchKernelGGL(k_kf_gather, dim3(n), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_loc_score, dim3(n, (g.hypotheses + kVerifyHypPerWg - 1u) / kVerifyHypPerWg), dim3(256), 0, s, a.loc);
     hipLaunchKernelGGL(k_kf_refine, dim3(n), dim3(256), 0, s, a);
+    p->kf_loc_call = p->kf_match_call;
     return stage_end(p, ST_KF_LOC, s, n);  // p->last_stream stays, as after a guided call
 }
 
@@ -2849,11 +2896,11 @@ int orb_join_read(OrbProgram* p, uint32_t frame, OrbJoinPose* pose) {
     return read_stage(p, ST_JOIN, frame, pose, p->d_spose, sizeof(OrbJoinPose), nullptr, nullptr, 0, 0);
 }
 
-// The first n records of one of the stage's tables, behind its last call
-static int join_copy(OrbProgram* p, const char* who, void* dst, const void* src, size_t n, size_t have, size_t bytes) {
+// The first n records of one of stage `which`'s tables, behind its last call (the join's and the anchor's segments and links)
+static int table_copy(OrbProgram* p, int which, const char* who, void* dst, const void* src, size_t n, size_t have, size_t bytes) {
     if (!p) return ORB_EINVAL;
-    const Stage& last = p->stage[ST_JOIN];
-    if (!last.extent) return fail(p, ORB_ESTATE, "%s before join_pairs", who);
+    const Stage& last = p->stage[which];
+    if (!last.extent) return fail(p, ORB_ESTATE, "%s before %s", who, kStages[which].name);
     if (n > have || (!dst && n)) return fail(p, ORB_EINVAL, "%s: %zu records of %zu, or the destination is NULL", who, n, have);
     HIP_TRY(p, hipSetDevice(p->device));
     HIP_TRY(p, hipEventSynchronize(last.done));
@@ -2862,11 +2909,11 @@ static int join_copy(OrbProgram* p, const char* who, void* dst, const void* src,
 }
 
 int orb_join_segments(OrbProgram* p, OrbJoinSegment* dst, size_t n) {
-    return p ? join_copy(p, "join_segments", dst, p->d_sseg, n, p->stage[ST_JOIN].extent, sizeof(OrbJoinSegment)) : ORB_EINVAL;
+    return p ? table_copy(p, ST_JOIN, "join_segments", dst, p->d_sseg, n, p->stage[ST_JOIN].extent, sizeof(OrbJoinSegment)) : ORB_EINVAL;
 }
 
 int orb_join_links(OrbProgram* p, OrbJoinLink* dst, size_t n) {
-    return p ? join_copy(p, "join_links", dst, p->d_slink, n, p->join_pairs, sizeof(OrbJoinLink)) : ORB_EINVAL;
+    return p ? table_copy(p, ST_JOIN, "join_links", dst, p->d_slink, n, p->join_pairs, sizeof(OrbJoinLink)) : ORB_EINVAL;
 }
 
 int orb_remap_frames(OrbProgram* p, const OrbRemapParams* params, void* stream) {
@@ -2930,6 +2977,117 @@ int orb_remap_landmarks(OrbProgram* p, uint32_t pair, OrbRemapRow* row, OrbLandm
     // the stage's extent is the frames; the pairs it covered are kept beside it
     if (p->stage[ST_REMAP].extent && pair >= p->remap_pairs) return fail(p, ORB_EINVAL, "remap_landmarks: pair %u of %u", pair, p->remap_pairs);
     return read_stage(p, ST_REMAP, pair, row, p->d_rrow, sizeof(OrbRemapRow), landmarks, p->d_rland, sizeof(OrbLandmark), n);
+}
+
+// ---- the batch in the stored map ----
+
+int orb_anchor_frames(OrbProgram* p, uint32_t n, const OrbAnchorParams* params, void* stream) {
+    if (!p) return ORB_EINVAL;
+    OrbAnchorParams g{};
+    if (params) g = *params;
+    if (g.reserved[0] | g.reserved[1] | g.reserved[2]) return fail(p, ORB_EINVAL, "anchor_frames: reserved words must be 0");
+    if (g.consistent_permille > 1000u || (g.flags & ~ORB_ANCHOR_USE_MINIMAL))
+        return fail(p, ORB_EINVAL, "anchor_frames: consistent_permille 0..1000, flags ORB_ANCHOR_USE_MINIMAL or 0");
+    if (!(std::isfinite(g.scale_tolerance) && g.scale_tolerance >= 0.0f)) return fail(p, ORB_EINVAL, "anchor_frames: scale_tolerance must be finite and >= 0");
+    if (int rc = stages_fresh(p, ST_ANCHOR, kStages[ST_ANCHOR].reads)) return rc;
+    if (p->kf_match_gen != p->kf_gen) return fail(p, ORB_ESTATE, "anchor_frames: the store has changed since the last orb_match_keyframes");
+    if (p->kf_loc_call != p->kf_match_call) return fail(p, ORB_ESTATE, "anchor_frames: the last orb_localize_keyframes read the rows of an earlier orb_match_keyframes");
+    const Stage* const st = p->stage;
+    if (n < 1u || n > st[ST_KF_LOC].extent) return fail(p, ORB_EINVAL, "anchor_frames: need 1..%u entries (the last orb_localize_keyframes')", st[ST_KF_LOC].extent);
+    // AN-1: L is LC-1's, the frames of the last landmarks call (a later matcher or trajectory call of fewer frames lowers it)
+    const uint32_t F = st[ST_TRAJ].extent;
+    const uint32_t L = std::min(st[ST_LANDMARK].extent + 1u, std::min(st[ST_MATCH].extent, F));
+    const size_t cap = p->cfg.max_features;
+    if ((unsigned long long)L * cap >= 0xffffffffull)  // LC-2: a key p * cap + i below the "no owner" word
+        return fail(p, ORB_EINVAL, "anchor_frames: the landmarks call's frames * max_features must be below 2^32 - 1");
+    hipStream_t s;
+    if (int rc = stage_open(p, ST_ANCHOR, stream, kStages[ST_ANCHOR].reads, &s)) return rc;
+    LcArgs o{};  // AN-2: k_lc_index reads the capacity, the counters, the consecutive records, the frames, the landmarks, L and the owners
+    o.loc.cap = (uint32_t)cap;
+    o.loc.counts = p->d_counts;
+    o.loc.matches = p->d_matches;
+    o.frames = p->d_jframe;
+    o.lms = p->d_mland;
+    o.n_frames = L;
+    o.traj_frames = F;
+    o.owner = p->d_nowner;
+    const uint32_t pairs = L - 1u;  // L >= 1: the stages are fresh
+    AnArgs a{};
+    a.counts = p->d_counts;
+    a.cap = (uint32_t)cap;
+    a.list = (const uint2*)p->d_kmlist;
+    a.rows = p->d_kmrows;
+    a.frames = p->d_jframe;
+    a.lms = p->d_mland;
+    a.lrows = p->d_mrow;
+    a.fixes = p->kfloc.fix;
+    a.mask = p->kfloc.mask;
+    a.heads = p->d_khead;
+    a.kpoints = p->d_kpoints;
+    a.owner = p->d_nowner;
+    a.n_frames = F;
+    a.map_frames = L;
+    a.n_pairs = pairs;
+    a.n_entries = n;
+    a.min_inliers = g.min_inliers ? g.min_inliers : 12u;
+    a.use_minimal = g.flags & ORB_ANCHOR_USE_MINIMAL;
+    a.min_shared = g.min_shared ? g.min_shared : 8u;
+    a.tol = g.scale_tolerance == 0.0f ? 0.1f : g.scale_tolerance;
+    a.permille = g.consistent_permille ? g.consistent_permille : 500u;
+    a.ratios = p->d_nratio;
+    a.links = p->d_nlink;
+    a.keys = p->d_nkey;
+    a.segs = p->d_nseg;
+    a.poses = p->d_npose;
+    a.out_rows = p->d_nrow;
+    a.out = p->d_nland;
+    // the owners of all F frames: rows L .. F - 1 have none
+    HIP_TRY(p, hipMemsetAsync(p->d_nowner, 0xff, (size_t)F * cap * sizeof(uint32_t), s));
+    HIP_TRY(p, hipMemsetAsync(p->d_nkey, 0, (size_t)F * sizeof(unsigned long long), s));
+    HIP_TRY(p, hipMemsetAsync(p->d_nseg, 0, (size_t)F * sizeof(OrbAnchorSegment), s));
+    const unsigned fblocks = (F + kAnThreads - 1u) / kAnThreads;
+    if (L > 1u) hipLaunchKernelGGL(k_lc_index, dim3(L - 1u, (unsigned)((cap + kLcThreads - 1u) / kLcThreads)), dim3(kLcThreads), 0, s, o);
+    hipLaunchKernelGGL(k_an_ratio, dim3(n), dim3(kAnThreads), 0, s, a);
+    hipLaunchKernelGGL(k_an_segment, dim3(fblocks), dim3(kAnThreads), 0, s, a);
+    hipLaunchKernelGGL(k_an_write, dim3(fblocks), dim3(kAnThreads), 0, s, a);
+    if (pairs) {
+        const uint32_t per_wg = kAnThreads * kAnLandSlots;
+        hipLaunchKernelGGL(k_an_land<kAnLandSlots>, dim3((unsigned)((cap + per_wg - 1u) / per_wg), pairs), dim3(kAnThreads), 0, s, a);
+    }
+    if (int rc = stage_end(p, ST_ANCHOR, s, F)) return rc;  // p->last_stream stays, as after a guided call
+    p->anchor_entries = n;
+    p->anchor_pairs = pairs;
+    return ORB_OK;
+}
+
+int orb_anchor_read(OrbProgram* p, uint32_t frame, OrbAnchorPose* pose) {
+    if (!p) return ORB_EINVAL;
+    if (p->stage[ST_ANCHOR].extent && !pose) return fail(p, ORB_EINVAL, "anchor_read: pose is NULL");
+    return read_stage(p, ST_ANCHOR, frame, pose, p->d_npose, sizeof(OrbAnchorPose), nullptr, nullptr, 0, 0);
+}
+
+int orb_anchor_segments(OrbProgram* p, OrbAnchorSegment* dst, size_t n) {
+    return p ? table_copy(p, ST_ANCHOR, "anchor_segments", dst, p->d_nseg, n, p->stage[ST_ANCHOR].extent, sizeof(OrbAnchorSegment)) : ORB_EINVAL;
+}
+
+int orb_anchor_links(OrbProgram* p, OrbAnchorLink* dst, size_t n) {
+    return p ? table_copy(p, ST_ANCHOR, "anchor_links", dst, p->d_nlink, n, p->anchor_entries, sizeof(OrbAnchorLink)) : ORB_EINVAL;
+}
+
+int orb_anchor_landmarks(OrbProgram* p, uint32_t pair, OrbAnchorRow* row, OrbLandmark* landmarks, size_t n) {
+    if (!p) return ORB_EINVAL;
+    // the stage's extent is the frames; the pairs it covered are kept beside it
+    if (p->stage[ST_ANCHOR].extent && pair >= p->anchor_pairs) return fail(p, ORB_EINVAL, "anchor_landmarks: pair %u of %u", pair, p->anchor_pairs);
+    return read_stage(p, ST_ANCHOR, pair, row, p->d_nrow, sizeof(OrbAnchorRow), landmarks, p->d_nland, sizeof(OrbLandmark), n);
+}
+
+int orb_debug_keyframe_buffers(OrbProgram* p, void** rows, void** fixes, void** mask) {
+    if (!p) return ORB_EINVAL;
+    if (!p->stage[ST_KF_LOC].extent) return fail(p, ORB_ESTATE, "debug_keyframe_buffers before orb_localize_keyframes");
+    if (rows) *rows = p->d_kmrows;
+    if (fixes) *fixes = p->kfloc.fix;
+    if (mask) *mask = p->kfloc.mask;
+    return ORB_OK;
 }
 
 int orb_match_guided(OrbProgram* p, uint32_t n_frames, const OrbGuideParams* params, const float* models_host, void* stream) {

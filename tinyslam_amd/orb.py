@@ -148,6 +148,22 @@ KEYFRAME_FIX_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("step", 
 ORB_KEYFRAME_SLOTS_MAX = 1024
 ORB_KEYFRAME_NONE = 0xFFFFFFFF
 ORB_KEYFRAME_EMPTY, ORB_KEYFRAME_STORED, ORB_KEYFRAME_NOMAP = 0, 1, 2
+# a batch's path and landmarks in the stored map (orb_anchor_frames): OrbAnchorPose (64 B) and its status,
+# OrbAnchorSegment (96 B) and its status, OrbAnchorLink (32 B) and its verdict, OrbAnchorRow (32 B), the flag of OrbAnchorParams; the
+# landmarks come back as LANDMARK_DTYPE
+ANCHOR_POSE_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4"), ("gain", "<f4"), ("slot", "<u4"), ("status", "<u4")])
+ANCHOR_SEGMENT_DTYPE = np.dtype([("r", "<f4", (9,)), ("t", "<f4", (3,)), ("gamma", "<f4"), ("slot", "<u4"), ("link", "<u4"), ("map_origin", "<u4"),
+                                 ("map_frame", "<u4"), ("user", "<u4", (2,)), ("status", "<u4"), ("reserved", "<u4", (4,))])
+ANCHOR_LINK_DTYPE = np.dtype([("verdict", "<u4"), ("query_origin", "<u4"), ("slot", "<u4"), ("shared", "<u4"), ("consistent", "<u4"),
+                              ("gamma", "<f4"), ("chosen", "<u4"), ("reserved", "<u4")])
+ANCHOR_ROW_DTYPE = np.dtype([("good", "<u4"), ("moved", "<u4"), ("dropped", "<u4"), ("origin", "<u4"), ("slot", "<u4"), ("map_origin", "<u4"),
+                             ("reserved", "<u4", (2,))])
+ORB_ANCHOR_FREE, ORB_ANCHOR_ANCHORED = 0, 1
+ORB_ANCHOR_SEGMENT_NONE, ORB_ANCHOR_SEGMENT_FREE, ORB_ANCHOR_SEGMENT_ANCHORED = 0, 1, 2
+(ORB_ANCHOR_LINK_HOLDS, ORB_ANCHOR_LINK_STATUS, ORB_ANCHOR_LINK_FEW, ORB_ANCHOR_LINK_RANGE, ORB_ANCHOR_LINK_NONFINITE, ORB_ANCHOR_LINK_RATIO_FEW,
+ ORB_ANCHOR_LINK_RATIO_SPREAD) = 0, 1, 2, 3, 4, 5, 6
+ORB_ANCHOR_USE_MINIMAL = 1
+ORB_ANCHOR_NONE = 0xFFFFFFFF
 
 # Names every build of libtinyorb.so must export (checked by tests against include/tinyorb.h).
 EXPORTS = [
@@ -182,6 +198,7 @@ EXPORTS = [
     "orb_remap_frames", "orb_remap_read", "orb_remap_landmarks",
     "orb_keyframes_reserve", "orb_keyframes_insert", "orb_keyframes_read", "orb_keyframes_load", "orb_keyframes_remove",
     "orb_match_keyframes", "orb_match_keyframes_read", "orb_localize_keyframes", "orb_localize_keyframes_read",
+    "orb_anchor_frames", "orb_anchor_read", "orb_anchor_segments", "orb_anchor_links", "orb_anchor_landmarks", "orb_debug_keyframe_buffers",
 ]
 
 
@@ -308,6 +325,15 @@ class _JoinParams(ctypes.Structure):
 
 
 OrbJoinParams = _JoinParams
+
+
+class _AnchorParams(ctypes.Structure):
+    """OrbAnchorParams (32 bytes; zero fields = the defaults)"""
+    _fields_ = [("min_inliers", ctypes.c_uint32), ("min_shared", ctypes.c_uint32), ("scale_tolerance", ctypes.c_float),
+                ("consistent_permille", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+OrbAnchorParams = _AnchorParams
 
 
 class _RemapParams(ctypes.Structure):
@@ -458,6 +484,12 @@ def load_library(path=None):
     L.orb_match_keyframes_read.argtypes = [vp, u32, vp, sz]
     L.orb_localize_keyframes.argtypes = [vp, u32, ctypes.POINTER(_LoopParams), vp]
     L.orb_localize_keyframes_read.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_anchor_frames.argtypes = [vp, u32, ctypes.POINTER(_AnchorParams), vp]
+    L.orb_anchor_read.argtypes = [vp, u32, vp]
+    L.orb_anchor_segments.argtypes = [vp, vp, sz]
+    L.orb_anchor_links.argtypes = [vp, vp, sz]
+    L.orb_anchor_landmarks.argtypes = [vp, u32, vp, vp, sz]
+    L.orb_debug_keyframe_buffers.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.orb_track_consecutive.argtypes = [vp, u32, ctypes.POINTER(_TrackParams), vp]
     L.orb_track_read.argtypes = [vp, u32, vp, sz]
     L.orb_track_frames.argtypes = [vp, vp, sz]
@@ -1261,6 +1293,52 @@ class OrbProgram:
         mask = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=np.uint8)
         self._check(self._lib.orb_localize_keyframes_read(self._handle(), entry, _ptr(rec), _ptr(mask) if len(mask) else None, len(mask)))
         return rec, mask
+
+    def anchor_frames(self, n, min_inliers=0, min_shared=0, scale_tolerance=0.0, consistent_permille=0, flags=0, stream=None,
+                      reserved=(0, 0, 0)):
+        """The last batch's trajectory and landmarks in the stored map (not in the reference):
+        entries 0 .. n - 1 of the last localize_keyframes give the similarity between the query's segment and the keyframe's, its
+        scale the lower median of the depth ratios of the inlier keypoints that a stored point and a landmark of the batch both
+        own; every segment takes its most consistent entry and hangs directly under that keyframe's segment, and its frames and
+        GOOD landmarks are written in the map's frame and unit.  Zero parameters are the defaults.  Raises OrbError(ORB_ESTATE)
+        when the store has changed since the last match_keyframes.  Asynchronous on `stream` (None: as match_guided chooses)."""
+        prm = _AnchorParams(min_inliers, min_shared, float(np.float32(scale_tolerance)), consistent_permille, flags,
+                            (ctypes.c_uint32 * 3)(*reserved))
+        self._check(self._lib.orb_anchor_frames(self._handle(), n, ctypes.byref(prm), ctypes.c_void_p(stream) if stream else None))
+
+    def anchor_read(self, frame):
+        """The record of ANCHOR_POSE_DTYPE of frame `frame` of the last anchor_frames -- synchronises."""
+        rec = np.zeros((), dtype=ANCHOR_POSE_DTYPE)
+        self._check(self._lib.orb_anchor_read(self._handle(), frame, _ptr(rec)))
+        return rec
+
+    def anchor_segments(self, n):
+        """ANCHOR_SEGMENT_DTYPE records of frame slots 0 .. n - 1 of the last anchor_frames -- synchronises."""
+        out = np.zeros(n, dtype=ANCHOR_SEGMENT_DTYPE)
+        self._check(self._lib.orb_anchor_segments(self._handle(), _ptr(out) if n else None, n))
+        return out
+
+    def anchor_links(self, n):
+        """ANCHOR_LINK_DTYPE records of entries 0 .. n - 1 of the last anchor_frames -- synchronises."""
+        out = np.zeros(n, dtype=ANCHOR_LINK_DTYPE)
+        self._check(self._lib.orb_anchor_links(self._handle(), _ptr(out) if n else None, n))
+        return out
+
+    def anchor_landmarks(self, pair, n=None):
+        """(row of ANCHOR_ROW_DTYPE, LANDMARK_DTYPE[min(n, max_features)]; n None: max_features) of pair `pair` of the last
+        anchor_frames, indexed as landmarks_read -- synchronises."""
+        row = np.zeros((), dtype=ANCHOR_ROW_DTYPE)
+        out = np.zeros(self.config.max_features if n is None else min(n, self.config.max_features), dtype=LANDMARK_DTYPE)
+        self._check(self._lib.orb_anchor_landmarks(self._handle(), pair, _ptr(row), _ptr(out) if len(out) else None, len(out)))
+        return row, out
+
+    def debug_keyframe_buffers(self):
+        """For tests: the device addresses (rows, fixes, inlier bytes) of what match_keyframes and localize_keyframes write --
+        [ORB_PAIRS_PER_FRAME * max_batch][max_features] MATCH_DTYPE, [ORB_PAIRS_PER_FRAME * max_batch] KEYFRAME_FIX_DTYPE and
+        [ORB_PAIRS_PER_FRAME * max_batch][max_features] bytes -- and anchor_frames reads.  The caller orders its own writes."""
+        r, f, m = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.orb_debug_keyframe_buffers(self._handle(), ctypes.byref(r), ctypes.byref(f), ctypes.byref(m)))
+        return r.value, f.value, m.value
 
     def track_consecutive(self, n_frames, source=ORB_TRACK_VERIFIED, max_distance=0, ratio=0.0, min_gap=0, max_gap=0, keep_permille=0,
                           min_shared=0, stream=None, reserved=0):
